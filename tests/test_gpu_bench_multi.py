@@ -47,8 +47,8 @@ _BLOCK = {}
 def _bench_with_sharded_block():
     """bench.py at N = 1 with the `sharded` block forced on, once for the two tests below."""
     if not _BLOCK:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8", "--log-n", "16", "--no-paths",
-               "--no-cpu-baseline", "--sharded-block", "--sharded-batch", "4", "--sharded-steps", "2", "--sharded-timeout", "90"]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--log-n", "16",
+               "--no-paths", "--no-cpu-baseline", "--sharded-block", "--sharded-batch", "4", "--sharded-steps", "2", "--sharded-timeout", "90"]
         r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=280)
         _BLOCK.update(rc=r.returncode, stderr=r.stderr[-2000:], lines=[ln for ln in r.stdout.splitlines() if ln.startswith("{")],
                       stdout=r.stdout[-2000:])
@@ -101,7 +101,8 @@ def test_bench_line_carries_live_pmc_traffic():
     """roofline.traffic: HBM bytes per launch of the dominant kernel from the PMC counters, collected DURING the bench run by two
     child rocprofv3 passes (FETCH_SIZE, WRITE_SIZE; gfx950 correction) -- not a number copied from profiles/.  Small size here;
     the figure must be a positive byte count of the order of (table rows x 128 B + 4 B) per sorted entry."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8", "--log-n", "16", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--log-n", "16",
+           "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -134,10 +135,10 @@ def _torchrun(nproc, port, bench_args, timeout=280):
 @pytest.mark.gpu
 @pytest.mark.limit(300)
 def test_bench_default_line_at_two_ranks_carries_the_sharded_block():
-    """What the driver's `bench.py --gpus N` run prints at N > 1, executed with two ranks: value = replicas, and the `sharded` block
+    """What `bench.py --gpus N --full` prints at N > 1, executed with two ranks: value = replicas, and the `sharded` block
     (strong: each commitment split over the ranks; config5: 2^21 terms per rank) measured through the device group at world 2 with
     every commitment of each mode's last step checked against [p(tau)]G."""
-    d = _torchrun(2, 29641, ["--steps", "2", "--warmup", "1", "--batch", "8", "--log-n", "16", "--no-paths", "--sharded-batch", "4",
+    d = _torchrun(2, 29641, ["--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--log-n", "16", "--no-paths", "--sharded-batch", "4",
                              "--sharded-steps", "2"])
     assert d["n_gpus"] == 2 and d["config"]["mode"] == "replicas"
     assert d["timed_results_checked"]["ok"] is True and d["timed_results_checked"]["every_rank"] is True   # the unconditional sample
@@ -162,3 +163,33 @@ def test_bench_sharded_modes_as_the_timed_region(nproc, flag):
     assert d["all_results_match_known_tau"] is True and d["timed_results_checked"]["ok"] is True
     assert d["value"] > 0
 
+
+
+@pytest.mark.gpu
+@pytest.mark.limit(200)
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) is the timed region and the line: --steps timed steps, ms_per_step, none of the --full readings, and
+    --dump-outputs writes the commitments of the last timed step -- checked here against [p_b(tau)]G by the oracle, p_b being the
+    SplitMix64 counter stream the bench fills polynomial b with."""
+    from oracle import c_oracle as C
+    from kzg_amd.api import splitmix_scalar
+    from tools.benchlib.common import SEED, TAU, dump_commitments
+    import numpy as np
+    log_n, batch, steps = 12, 4, 3
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--batch", str(batch),
+           "--log-n", str(log_n), "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=180)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == 1 and d["unit"] == "commitments/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - batch * steps / (d["ms_per_step"] * steps / 1e3)) / d["value"] < 0.02
+    for key in ("roofline", "paths", "cpu_baseline", "sharded", "timed_results_checked"):
+        assert key not in d, key
+    got = np.load(str(tmp_path / "out" / "commitments.npy"))
+    assert got.dtype == np.float64 and got.shape == (batch, 2, 12)
+    want = b"".join(C.g1_mul(C.g1_generator(), C.poly_eval([splitmix_scalar(SEED + 1000 * b, i) for i in range(1 << log_n)], TAU))
+                    for b in range(batch))
+    dump_commitments(str(tmp_path / "want"), want, batch)
+    assert np.array_equal(got, np.load(str(tmp_path / "want" / "commitments.npy")))

@@ -444,7 +444,11 @@ def test_prover_context_and_device_group_share_one_stream_pool():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "engine_and_group_ab.py"), "20", "32"], capture_output=True, text=True, timeout=280)
+    # the children get the queue pool kzg_init_hw_queues(0) asks for (24), whatever GPU_MAX_HW_QUEUES the runner exported (the library
+    # keeps an exported value, and a small one narrows every plan below)
+    env = dict(os.environ, GPU_MAX_HW_QUEUES="24")
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "engine_and_group_ab.py"), "20", "32"], capture_output=True, text=True, timeout=280,
+                       env=env)
     res = {d["scenario"]: d for d in (json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{"))}
     assert set(res) == {"engine", "group", "engine_then_group", "both"}, r.stdout[-2000:] + r.stderr[-2000:]
     for sc, d in res.items():

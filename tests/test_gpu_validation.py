@@ -279,7 +279,10 @@ def test_pipeline_narrowing_is_reported_not_silent():
             "a = e.msm_batch(p.gs, buf, n, 24); print('FULL', e.info())\n"
             "e.set_option('hw_queues', 4); b = e.msm_batch(p.gs, buf, n, 24); print('NARROW', e.info()); assert a == b\n"
             "e.set_option('hw_queues', 0); c = e.msm_batch(p.gs, buf, n, 24); print('AGAIN', e.info()); assert a == c\n" % root)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    # the child gets the queue pool kzg_init_hw_queues(0) asks for (24), whatever GPU_MAX_HW_QUEUES the runner exported: an exported
+    # value is kept by the library, and a small one would narrow the FULL plan below before the forced narrowing could be seen
+    env = dict(os.environ, GPU_MAX_HW_QUEUES="24")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = {ln.split(" ", 1)[0]: ln for ln in r.stdout.splitlines() if ln.split(" ", 1)[0] in ("BEFORE", "FULL", "NARROW", "AGAIN")}
     assert "lanes=0 accum_streams=0" in lines["BEFORE"] and "narrowed_from=none" in lines["BEFORE"]

@@ -4,7 +4,7 @@
 for round in 1 2 3; do
   for v in "$@"; do
     echo -n "[$v] "
-    timeout 300 python3 bench.py $v --no-cpu-baseline --no-paths --steps 8 --warmup 2 --check 2>/dev/null | python3 -c "
+    timeout 300 python3 bench.py --full $v --no-cpu-baseline --no-paths --steps 8 --warmup 2 --check 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(d['value'], d['single_commit_latency_ms'], d['roofline']['alone']['avg_kernel_ms'], d.get('check'))"

@@ -6,4 +6,4 @@
 N=$1; shift
 cd "${GRAFT_REPO_ROOT:-.}"
 export KZG_BENCH_SHARED_GPU=1 KZG_TEST_SHM_TRANSPORT=1 KZG_AMD_LIBRARY=$PWD/kzg_amd/libkzg_mi355x_hooks.so MASTER_ADDR=127.0.0.1
-exec python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus $N "$@"
+exec python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus $N --full "$@"

@@ -26,6 +26,29 @@ TAU = 0x5EED5EED5EED5EED       # known secret for the synthetic SRS (setup(s, n)
 SEED = 1
 
 
+FQ_MODULUS = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_commitments(dirname, raw, batch):
+    """--dump-outputs: the `batch` G1 points of `raw` (KZG_G1_AFFINE_MONT_96, what the timed path hands its caller) as
+    DIR/commitments.npy, float64 [batch, 2 (x, y), 12 little-endian 32-bit limbs] of the canonical affine coordinates (identity:
+    all zero).  Every limb is exact in float64.  Above DUMP_MAX_BYTES a fixed sample of the commitments (seed 0, in order)."""
+    import random
+    import numpy as np
+    rinv = pow(1 << 384, -1, FQ_MODULUS)
+    rows = list(range(batch))
+    if batch * 2 * 12 * 8 > DUMP_MAX_BYTES:
+        rows = sorted(random.Random(0).sample(rows, DUMP_MAX_BYTES // (2 * 12 * 8)))
+    a = np.zeros((len(rows), 2, 12), dtype=np.float64)
+    for i, b in enumerate(rows):
+        for j in range(2):
+            v = int.from_bytes(raw[96 * b + 48 * j:96 * b + 48 * (j + 1)], "little") * rinv % FQ_MODULUS
+            a[i, j] = [(v >> (32 * k)) & 0xFFFFFFFF for k in range(12)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "commitments.npy"), a)
+
+
 def g1_adds_per_msm(n, c, W):
     """algorithmic G1 additions, n*W bucket accumulations + bucket reduction (W: digits per scalar; positional
     tables, c = 18: the measured average number of NAF digits, 2^16 buckets)."""

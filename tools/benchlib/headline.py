@@ -1,6 +1,8 @@
 """The timed region of bench.py and the JSON line built around it: BASELINE configs[1] (degree-2^20 coeff-form commit, batches of
 kzg_msm_g1_batch on scalars and an SRS already resident in HBM), the roofline of its dominant kernel from HIP events on the engine's
-streams, and the other readings (`paths`, `cpu_baseline`, `sharded`) attached after the timer has stopped.
+streams, and the other readings (`paths`, `cpu_baseline`, `sharded`) attached after the timer has stopped.  A plain run is the
+timed region and the line alone; everything besides it runs with --full (--check, --callers and --sharded-block ask for their part
+on their own).
 
 Nothing in this module imports oracle/: the timed results are checked, after the timed region, through tools.benchlib.checks, and the
 CPU baseline runs in tools.benchlib.cpu_pool's worker processes."""
@@ -51,7 +53,8 @@ def run(args):
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     sharded = args.sharded or (world > 1 and (args.strong or args.config5 or args.weak) and not args.replicas)
-    want_block = (args.sharded_block or (world > 1 and not args.no_sharded_block)) and not sharded
+    full = args.full
+    want_block = (args.sharded_block or (world > 1 and full and not args.no_sharded_block)) and not sharded
 
     # stdout carries exactly ONE line, the JSON record.  RCCL prints a banner (ROCm version / hostname / library path) through C
     # stdio when a communicator is created, and that buffer is flushed at process exit -- after anything Python printed.  So
@@ -61,12 +64,12 @@ def run(args):
     real_stdout = os.dup(1)
     os.dup2(2, 1)
 
-    # The sharded-SRS + RCCL modes (north_star's design; at N > 1 part of the default run), measured by the ranks' CHILD processes
+    # The sharded-SRS + RCCL modes (north_star's design; at N > 1 part of a --full run), measured by the ranks' CHILD processes
     # before this process initialises HIP (run_sharded_block_in_children); the result joins the line at the end.
     sharded_res = run_sharded_block_in_children(args, rank, local_rank, world) if want_block else None
 
     cpu = None
-    if rank == 0 and world == 1 and not sharded and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not sharded and not args.no_cpu_baseline:
         try:
             cpu = CpuBaseline()
             cpu.start()          # before HIP: the workers are spawned from a process that has not touched the GPU
@@ -181,7 +184,7 @@ def run(args):
     for _ in range(args.warmup):
         step()
     barrier()
-    if rank == 0 and not os.environ.get("KZG_BENCH_NO_PROF"):   # (the variable: what do the events themselves cost? profiles/r04_prof_overhead.txt)
+    if full and rank == 0 and not os.environ.get("KZG_BENCH_NO_PROF"):   # (the variable: what do the events themselves cost? profiles/r04_prof_overhead.txt)
         # HIP events on the engine's streams over the timed region, around the dominant kernel only: events around all ~14 kernels
         # of every MSM cost 1.4 % of `value` (profiles/r04_prof_overhead.txt); the other kernels' durations come from one more,
         # untimed, fully instrumented step below
@@ -192,23 +195,27 @@ def run(args):
         step()
     barrier()
     dt = job.max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_commitments(args.dump_outputs, out.raw, args.batch)
 
     # known-tau identity for the commitments of the last timed step: C_b == [p_b(tau)]G, p_b(tau) = sum_r tau^(lo_r) p_{b,r}(tau).
     # Checker = the oracle throughout: each rank downloads its coefficient slices, the oracle's Horner loop evaluates them, the
-    # oracle multiplies G.  No HIP kernel on the right-hand side.  Always a sample of four (first, last, two in between: ~0.5 s
+    # oracle multiplies G.  No HIP kernel on the right-hand side.  --full: a sample of four (first, last, two in between: ~0.5 s
     # at 2^20); --check: every commitment of the step.  Outside the timed region.
     which = list(range(args.batch)) if args.check else sorted({0, args.batch // 3, 2 * args.batch // 3, args.batch - 1})
-    try:
-        checked_ok = checks.check_known_tau(kzg_amd, job, scal, n_local, lo, out.raw, which, spans_ranks=sharded)
-    except Exception as e:  # noqa: BLE001
-        checked_ok = "check failed to run: %s" % e
+    checked_ok = None
+    if full or args.check:
+        try:
+            checked_ok = checks.check_known_tau(kzg_amd, job, scal, n_local, lo, out.raw, which, spans_ranks=sharded)
+        except Exception as e:  # noqa: BLE001
+            checked_ok = "check failed to run: %s" % e
     check = checked_ok if args.check else None
 
     # ---- roofline of the dominant kernel: HIP events recorded on the engine's streams over the timed region ----
     roofline = None
     latency_ms = None
     mad_peak = MAD_PEAK_TLANE_S
-    if rank == 0:
+    if rank == 0 and full:
         prof = engine.prof_all()
         if prof.get("k_accum_affine", (0, 0.0))[0] and not sharded:   # (a sharded step is collective: rank 0 cannot take one alone)
             engine.prof_enable(True)     # one untimed step with events around every kernel (kernel_ms_per_msm of the pipeline)
@@ -345,14 +352,15 @@ def run(args):
         }
         if check is not None:
             res["all_results_match_known_tau"] = check
-        res["timed_results_checked"] = {"against": "[p(tau)]G, p(tau) by the oracle's Horner loop on the downloaded coefficients",
-                                        "commitments_of_last_step": which if len(which) <= 8 else "all %d" % len(which),
-                                        "every_rank": world > 1, "ok": checked_ok}
+        if checked_ok is not None:
+            res["timed_results_checked"] = {"against": "[p(tau)]G, p(tau) by the oracle's Horner loop on the downloaded coefficients",
+                                            "commitments_of_last_step": which if len(which) <= 8 else "all %d" % len(which),
+                                            "every_rank": world > 1, "ok": checked_ok}
         res["hip_runtime"] = job.runtime(L)
         if roofline:
             res["roofline"] = roofline
         t_extra = time.perf_counter()
-        if mode == "single" and not args.no_paths:
+        if mode == "single" and full and not args.no_paths:
             try:
                 res["paths"] = measure_paths(kzg_amd, L, engine, params, scal, n_poly, args.log_n, mad_peak=mad_peak)
                 per_s, same = measure_blocking_callers(kzg_amd, L, engine, srs, scal, n_poly, args.batch)
@@ -412,7 +420,7 @@ def run(args):
                 else:
                     nr["traffic"] = None
                     nr["traffic_note"] = note
-        if mode == "single" and not args.no_cpu_baseline:
+        if mode == "single" and full and not args.no_cpu_baseline:
             if cpu is not None:
                 try:
                     n_s = 1 << min(args.log_n, 20)

@@ -5,8 +5,8 @@ cd /tmp && export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/pmc_batch
 rm -rf $O; mkdir -p $O
-timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $O/u64 -o p --output-format csv -- python3 bench.py --u64 --steps 1 --warmup 1 --batch 32 --no-cpu-baseline --no-paths > $O/u64.json 2> $O/u64.log
-timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $O/uniform -o p --output-format csv -- python3 bench.py --steps 1 --warmup 1 --batch 32 --no-cpu-baseline --no-paths > $O/uniform.json 2> $O/uniform.log
+timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $O/u64 -o p --output-format csv -- python3 bench.py --full --u64 --steps 1 --warmup 1 --batch 32 --no-cpu-baseline --no-paths > $O/u64.json 2> $O/u64.log
+timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $O/uniform -o p --output-format csv -- python3 bench.py --full --steps 1 --warmup 1 --batch 32 --no-cpu-baseline --no-paths > $O/uniform.json 2> $O/uniform.log
 for d in u64 uniform; do python3 tools/pmc_summary.py $O/$d > $O/$d.summary.json; done
 python3 - <<'PY'
 import json
