@@ -65,6 +65,7 @@ extern "C" {
  *   kzg_witness_coeff_batched,
  *   kzg_verify_eval_batched                 k <= 16384 opening points         (the interpolation works on a k x k matrix: 8.6 GB there)
  *   kzg_srs_lagrange_from_monomial_g1       d <= 2^24;  _g2: d <= 1024
+ *   kzg_fk20_setup                          log_n <= 22                      (the plan holds 2N points of 224 B: 1.9 GB there)
  *   MSM                                     table rows x points < 2^31       (the sorted entry is a 31-bit table index + sign);
  *                                           window_bits 18, 19 (option), and 20 with option sort_single_pass: windows x points < 2^27
  *   kzg_g1_sum_batch                        count <= 2^20, groups <= 2^24
@@ -354,6 +355,28 @@ int kzg_witness_eval(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals, s
  * Not a reference method: equivalent to calling KZGProverEvalForm::create_witness count times. */
 int kzg_witness_eval_many(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals, size_t d, const size_t *indices,
                           size_t count, int sfmt, int flags, void *out, int ofmt);
+/* ---- all openings over the domain (FK20, single-point case; not a reference method) ---------------------------------
+ * Every witness of a polynomial at every point w^m of its size-N domain (w = compute_omega(N).omega) in O(N log N) group
+ * operations instead of N MSMs: two G1 DFTs, 2N variable-base scalar multiplications and one Fr NTT per polynomial, against a
+ * plan that holds DFT_2N of the reversed monomial SRS.  Witness m equals kzg_witness_coeff_many at (w^m, p(w^m)) and
+ * KZGProverEvalForm::create_witness(evals, m) (src/eval_form.rs:124-140) when the Lagrange SRS comes from the same tau.
+ * A kzg_fk20 holds that transform and the twiddle tables for one monomial SRS and one domain 2^log_n; it is immutable after
+ * creation and may be used from any thread and every kzg_ctx on its device.  Setup: KZG_ERR_DEGREE_TOO_LARGE if log_n + 1 reaches
+ * the two-adicity of Fr, KZG_ERR_SHAPE for log_n > 22 (Limits) or an SRS on another GPU.  SRS points past len(srs) count as the
+ * identity, which is exact for every polynomial the calls below accept. */
+typedef struct kzg_fk20 kzg_fk20;
+int kzg_fk20_setup(kzg_ctx *ctx, const kzg_srs *monomial, uint32_t log_n, kzg_fk20 **out);
+void kzg_fk20_free(kzg_ctx *ctx, kzg_fk20 *plan);
+size_t kzg_fk20_domain(const kzg_fk20 *plan); /* N */
+/* `batch` polynomials of n coefficients each (stride n); out: batch x N witnesses, witness m of polynomial b at w^m.  KZG_ERR_SHAPE
+ * if n == 0, n > N, n - 1 > len(srs) (the reference's slice panic) or the plan lives on another GPU.  N == 1: the identity.  Takes
+ * the context exclusively; works in chunks of at most 2^21 / 2N polynomials, so the workspace does not grow with `batch`. */
+int kzg_witness_all_coeff(kzg_ctx *ctx, const kzg_fk20 *plan, const void *coeffs, size_t n, size_t batch, int sfmt, int flags,
+                          void *out, int ofmt);
+/* `batch` evaluation vectors of length d == N (else KZG_ERR_SHAPE): iNTT in Fr, then the above; witness m ==
+ * KZGProverEvalForm::create_witness(evals, m). */
+int kzg_witness_all_eval(kzg_ctx *ctx, const kzg_fk20 *plan, const void *evals, size_t d, size_t batch, int sfmt, int flags,
+                         void *out, int ofmt);
 /* KZGVerifierEvalForm::verify_poly (:162-171): ifft then monomial MSM, compare. */
 int kzg_verify_poly_eval(kzg_ctx *ctx, const kzg_srs *monomial, const void *commitment, int pfmt,
                          const void *evals, size_t d, int sfmt, int flags, int *ok);

@@ -20,6 +20,11 @@ int kzg_test_fq_mul(kzg_ctx *ctx, const void *a, const void *b, size_t n, void *
 int kzg_test_fr_inv(kzg_ctx *ctx, const void *a, size_t n, void *out);
 int kzg_test_g1_add(kzg_ctx *ctx, const void *a, const void *b, size_t n, void *out);   /* affine mont 96 */
 int kzg_test_g1_mul(kzg_ctx *ctx, const void *p, const void *k_canonical, size_t n, void *out);
+/* [k]P through the GLV split of the FK20 butterflies (g1ntt.hip): k = k2 lambda + k1, signed 4-bit digits over P and phi(P) */
+int kzg_test_g1_mul_glv(kzg_ctx *ctx, const void *p, const void *k_canonical, size_t n, void *out);
+/* one G1 DFT of 2^log_n points over compute_omega(2^log_n): out_m = sum_j w^(jm) P_j, or w^(-jm) with `inverse` (NOT scaled by
+ * 1 / 2^log_n); affine Montgomery in and out, natural order */
+int kzg_test_g1_ntt(kzg_ctx *ctx, const void *pts, uint32_t log_n, int inverse, void *out);
 /* pretend `srs` is resident on GPU `device` (the "SRS of another GPU" error of every MSM entry point, on a one-GPU box) */
 int kzg_test_srs_set_device(struct kzg_srs *srs, int device);
 /* the next sharded call of this group fails locally on local GPU 0 with `code` (status agreement across ranks, mgpu.hip) */

@@ -111,6 +111,11 @@ def load(path=None):
         "kzg_witness_eval_many": (i32, [vp, vp, vp, sz, ctypes.POINTER(sz), sz, i32, i32, vp, i32]),
         "kzg_witness_eval": (i32, [vp, vp, vp, sz, sz, i32, i32, vp, i32]),
         "kzg_verify_poly_eval": (i32, [vp, vp, vp, i32, vp, sz, i32, i32, ctypes.POINTER(i32)]),
+        "kzg_fk20_setup": (i32, [vp, vp, u32, c_void_pp]),
+        "kzg_fk20_free": (None, [vp, vp]),
+        "kzg_fk20_domain": (sz, [vp]),
+        "kzg_witness_all_coeff": (i32, [vp, vp, vp, sz, sz, i32, i32, vp, i32]),
+        "kzg_witness_all_eval": (i32, [vp, vp, vp, sz, sz, i32, i32, vp, i32]),
         "kzg_srs_setup_g2": (i32, [vp, vp, i32, sz, c_void_pp]),
         "kzg_srs_setup_lagrange_g2": (i32, [vp, vp, i32, sz, c_void_pp]),
         "kzg_srs_lagrange_from_monomial_g2": (i32, [vp, vp, c_void_pp]),

@@ -348,6 +348,37 @@ class Srs:
         return Srs(engine, h)
 
 
+class FK20Plan:
+    """kzg_fk20: the per-domain tables of FK20 (every opening of a polynomial over its size-2^log_n domain in one call) for one
+    monomial SRS.  Not a reference type."""
+
+    def __init__(self, engine, srs, log_n):
+        self.engine = engine
+        h = ctypes.c_void_p()
+        rc = engine.lib.kzg_fk20_setup(engine.ctx, srs.handle, log_n, ctypes.byref(h))
+        if rc:
+            _raise(engine, rc)
+        self.handle = h
+
+    def domain(self):
+        return self.engine.lib.kzg_fk20_domain(self.handle)
+
+    def free(self):
+        if self.handle:
+            self.engine.lib.kzg_fk20_free(self.engine.ctx, self.handle)
+            self.handle = None
+
+
+def _witness_all(engine, fn, plan, blob, n, batch, ofmt):
+    N = plan.domain()
+    psz = L.POINT_BYTES[ofmt]
+    out = ctypes.create_string_buffer(psz * N * max(batch, 1))
+    rc = fn(engine.ctx, plan.handle, blob, n, batch, L.FR_CANONICAL, 0, out, ofmt)
+    if rc:
+        _raise(engine, rc)
+    return [[out.raw[(b * N + m) * psz:(b * N + m + 1) * psz] for m in range(N)] for b in range(batch)]
+
+
 class SrsG2:
     """Resident G2 points (kzg_srs_g2): the `hs` half of KZGParams or a G2 Lagrange basis."""
 
@@ -862,6 +893,17 @@ class KZGProver:
         psz = L.POINT_BYTES[ofmt]
         return [out.raw[j * psz:(j + 1) * psz] for j in range(k)], [status[j] == 0 for j in range(k)]
 
+    def create_witness_all_points(self, polynomial, plan, ofmt=L.G1_AFFINE_MONT):
+        """Every witness over the plan's domain (FK20; not a reference method): element m is create_witness(polynomial,
+        (w^m, p(w^m))) with w = compute_omega(N).omega."""
+        return self.create_witness_all_points_batch([polynomial], plan, ofmt)[0]
+
+    def create_witness_all_points_batch(self, polynomials, plan, ofmt=L.G1_AFFINE_MONT):
+        """create_witness_all_points for several polynomials (zero-padded to the longest): one list of N witnesses each."""
+        n = max(p.num_coeffs() for p in polynomials)
+        blob = b"".join(pack_scalars(p.slice_coeffs() + [0] * (n - p.num_coeffs())) for p in polynomials)
+        return _witness_all(self.engine, self.engine.lib.kzg_witness_all_coeff, plan, blob, n, len(polynomials), ofmt)
+
     def create_witness_batched(self, polynomial, xs, ys, ofmt=L.G1_AFFINE_MONT):  # :83-111
         e = self.engine
         assert len(xs) == len(ys)
@@ -976,6 +1018,18 @@ class KZGProverEvalForm:
             _raise(e, rc)
         psz = L.POINT_BYTES[ofmt]
         return [out.raw[j * psz:(j + 1) * psz] for j in range(k)]
+
+    def create_witness_all_points(self, evals, plan, ofmt=L.G1_AFFINE_MONT):
+        """Every witness over the domain (FK20 against `plan`, built from the monomial SRS; not a reference method): element m
+        equals create_witness(evals, m)."""
+        return self.create_witness_all_points_batch([evals], plan, ofmt)[0]
+
+    def create_witness_all_points_batch(self, evals_list, plan, ofmt=L.G1_AFFINE_MONT):
+        d = len(evals_list[0])
+        if any(len(ev) != d for ev in evals_list):
+            raise ReferencePanic("assert!(self.d == evals.d): evaluation vectors of different lengths")
+        blob = b"".join(pack_scalars(ev.coeffs) for ev in evals_list)
+        return _witness_all(self.engine, self.engine.lib.kzg_witness_all_eval, plan, blob, d, len(evals_list), ofmt)
 
     def create_witness_all(self):  # :142-146: identity
         return bytes(96)

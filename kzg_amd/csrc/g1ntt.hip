@@ -1,0 +1,469 @@
+// g1ntt.hip -- FK20 (Feist-Khovratovich, single-point case): every opening of one polynomial over its whole evaluation domain in
+// O(N log N) group operations, and the reusable G1 DFT it is built on.
+//
+// Domain N = 2^k, w = compute_omega(N).omega, coefficients c_0..c_{N-1} (zero-padded from n <= N), s_i = [tau^i]G.  The witness
+// at w^m is pi_m = [q_m(tau)] with q_m = (p - p(w^m)) / (X - w^m), and pi = DFT_N(H) with H_k = sum_{i <= N-2-k} c_{i+k+1} s_i
+// (H_{N-1} = O).  H is the first half of the length-2N cyclic convolution of
+//     x_j = s_{N-2-j} (j <= N-2), O (j >= N-1)          (per plan: Xh = DFT_2N(x) over G1, stored bit-reversed)
+//     y_0 = c_{N-1}, y_1..y_N = 0, y_t = c_{t-N-1}        (per polynomial, in Fr: yh = DFT_2N(y) / 2N, permuted bit-reversed)
+// so per polynomial:  Hh_j = yh_j Xh_j (bit-reversed),  H = iDFT_2N(Hh) as DIT (bit-reversed in, natural out, first half only),
+// pi = DFT_N(H) as DIF (natural in, bit-reversed out), read out bit-reversed by the emit kernel.  No 224-byte point is permuted
+// and no G1 stage carries a scale factor (the 1/2N is folded into yh).  s_i beyond the SRS is the identity: exact for every
+// polynomial with n - 1 <= len(srs), because c_{i+k+1} s_i is non-zero only for i <= n - 2.
+//
+// Butterflies multiply by a fixed twiddle, so each twiddle is split once per plan by the GLV endomorphism of BLS12-381 G1:
+// lambda = z^2 - 1 (r = lambda^2 + lambda + 1), phi(x, y) = (beta x, y) = [lambda](x, y); k = k2 lambda + k1 with k1, k2 < 2^128
+// by plain division.  Both halves are recoded into signed 4-bit digits in [-8, 7] (add 0x88..8, read nibbles, subtract 8): one
+// joint double-and-add over P and phi(P) costs 128 doublings and <= 64 additions against 256 and 64 for a 4-bit window over the
+// full scalar, and the eight multiples P..8P are the whole per-thread table (phi and the sign are applied on the fly: one Fq
+// product per phi digit).  The table lives in an HBM scratch slot per thread of a grid-stride launch, entries strided by the
+// thread count so that a wave's reads and writes are coalesced.  The stage with half-size 1 has trivial twiddles only and its own
+// kernel of two additions per butterfly.  The point-wise products (varying scalars) use the same signed digits over 256 bits.
+#include <algorithm>
+
+#include "common.h"
+#include "emit.h"
+#include "glv.h"
+
+namespace kzg {
+
+constexpr size_t G1NTT_MAX_THREADS = (size_t)1 << 18;  // grid-stride launches: bounds the scratch table (2^18 x 8 x 224 B = 470 MB)
+constexpr size_t FK20_CHUNK_POINTS = (size_t)1 << 21;  // polynomials per chunk: chunk x 2N points of workspace at most (470 MB)
+constexpr size_t FK20_MAX_CHUNK = 4096;
+constexpr uint32_t FK20_MAX_LOG = 22;
+
+__device__ __forceinline__ size_t brev(size_t i, uint32_t bits) {
+    return bits ? (size_t)(__brevll((unsigned long long)i) >> (64 - bits)) : 0;
+}
+
+// ---- G1 DFT stages over `batch` arrays of d points (array b at P + b * pstride) -------------------------------------------
+// tw: recoded w_D^e, e < D / 2, for a transform of size D >= d; tws = D / d (so w_d^e = tw[e * tws]).
+// DIF, natural in -> bit-reversed out, half-size m = d/2 .. 2:  (x, y) -> (x + y, [w^e](x - y)),  e = i d / 2m
+__global__ __launch_bounds__(256) void k_g1ntt_dif(MsmPoint *P, size_t pstride, size_t d, size_t m, const GlvTw *tw, size_t tws,
+                                                   size_t batch, MsmPoint *scratch, Fq30 beta) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t half = d / 2, work = batch * half;
+    for (size_t u = tid; u < work; u += nt) {
+        const size_t b = u / half, t = u % half;
+        const size_t j = t / m, i = t % m;
+        MsmPoint *A = P + b * pstride;
+        const size_t i0 = j * 2 * m + i, i1 = i0 + m;
+        const MsmPoint x = A[i0], y = A[i1];
+        A[i0] = g1_add30(x, y);
+        MsmPoint D = y;
+        D.y = neg30(D.y);
+        D = g1_add30(x, D);
+        A[i1] = glv_mul(D, tw[i * (d / (2 * m)) * tws], scratch + tid, nt, beta);
+    }
+}
+
+// DIT, bit-reversed in -> natural out, half-size m = 2 .. d/2:  t = [w^e] y, (x, y) -> (x + t, x - t).  half_out: the last stage
+// of a transform of which only the first half is wanted (x + t only).
+__global__ __launch_bounds__(256) void k_g1ntt_dit(MsmPoint *P, size_t pstride, size_t d, size_t m, const GlvTw *tw, size_t tws,
+                                                   size_t batch, MsmPoint *scratch, Fq30 beta, int half_out) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t half = d / 2, work = batch * half;
+    for (size_t u = tid; u < work; u += nt) {
+        const size_t b = u / half, t = u % half;
+        const size_t j = t / m, i = t % m;
+        MsmPoint *A = P + b * pstride;
+        const size_t i0 = j * 2 * m + i, i1 = i0 + m;
+        const MsmPoint x = A[i0];
+        MsmPoint T = glv_mul(A[i1], tw[i * (d / (2 * m)) * tws], scratch + tid, nt, beta);
+        A[i0] = g1_add30(x, T);
+        if (!half_out) {
+            T.y = neg30(T.y);
+            A[i1] = g1_add30(x, T);
+        }
+    }
+}
+
+// half-size 1, both directions (the twiddle is 1): (x, y) -> (x + y, x - y)
+__global__ __launch_bounds__(256) void k_g1ntt_trivial(MsmPoint *P, size_t pstride, size_t d, size_t batch, int half_out) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t half = d / 2, work = batch * half;
+    for (size_t u = tid; u < work; u += nt) {
+        const size_t b = u / half, t = u % half;
+        MsmPoint *A = P + b * pstride;
+        const MsmPoint x = A[2 * t], y = A[2 * t + 1];
+        A[2 * t] = g1_add30(x, y);
+        if (!half_out) {
+            MsmPoint D = y;
+            D.y = neg30(D.y);
+            A[2 * t + 1] = g1_add30(x, D);
+        }
+    }
+}
+
+// recoded twiddles from a Montgomery power table
+__global__ __launch_bounds__(256) void k_glv_twiddles(const Fr *pw, size_t count, GlvTw *out) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const Fr k = from_mont(pw[i]);
+    out[i] = glv_recode(k.v);
+}
+
+// x_j = s_{N-2-j} (j <= N-2 and inside the SRS), O otherwise; j < 2N
+__global__ __launch_bounds__(256) void k_fk20_load_x(const G1Affine *srs, size_t srs_n, size_t N, MsmPoint *X) {
+    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= 2 * N) return;
+    const size_t i = N - 2 - j;  // wraps for j >= N - 1
+    X[j] = (j + 2 <= N && i < srs_n) ? g1_from_affine30(g1_affine_to30(srs[i]), false) : MsmPoint::infinity();
+}
+
+// y (2N Montgomery scalars per polynomial) from n coefficients per polynomial (stride n) in sfmt
+__global__ __launch_bounds__(256) void k_fk20_build_y(const Fr *c, size_t n, size_t N, size_t batch, int sfmt, Fr *y) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    const size_t two = 2 * N, work = batch * two;
+    for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < work; u += nt) {
+        const size_t b = u / two, t = u % two;
+        const size_t idx = t == 0 ? N - 1 : (t > N ? t - N - 1 : (size_t)-1);
+        Fr v = Fr::zero();
+        if (idx < n) {
+            v = c[b * n + idx];
+            if (sfmt == KZG_FR_CANONICAL_LE_32) v = to_mont(v);
+        }
+        y[u] = v;
+    }
+}
+
+// yh (natural, Montgomery) -> canonical yh / 2N, bit-reversed
+__global__ __launch_bounds__(256) void k_fk20_scale_brev(const Fr *yn, uint32_t log2n, Fr scale, size_t batch, Fr *out) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    const size_t two = (size_t)1 << log2n, work = batch * two;
+    for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < work; u += nt) {
+        const size_t b = u / two, j = u % two;
+        out[u] = from_mont(mul(yn[b * two + brev(j, log2n)], scale));
+    }
+}
+
+// P[b][j] = [yh[b][j]] Xh[j]
+__global__ __launch_bounds__(256) void k_fk20_pointwise(MsmPoint *P, const MsmPoint *Xh, const Fr *yh, size_t two, size_t batch,
+                                                        MsmPoint *scratch, Fq30 beta) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t work = batch * two;
+    for (size_t u = tid; u < work; u += nt) P[u] = mul256(Xh[u % two], yh[u], scratch + tid, nt, beta);
+}
+
+// out[b][m] = P[b][brev(m)] in fmt (P == nullptr: the identity)
+__global__ __launch_bounds__(64) void k_fk20_emit(const MsmPoint *P, size_t pstride, uint32_t logn, size_t batch, uint8_t *out,
+                                                  int fmt, size_t psz) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    const size_t N = (size_t)1 << logn, work = batch * N;
+    for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < work; u += nt) {
+        const size_t b = u / N, m = u % N;
+        emit_one(P ? P[b * pstride + brev(m, logn)] : MsmPoint::infinity(), out + u * psz, fmt);
+    }
+}
+
+static unsigned grid_for(size_t work, size_t block) {
+    size_t t = std::min(work, G1NTT_MAX_THREADS);
+    size_t g = (t + block - 1) / block;
+    return (unsigned)(g ? g : 1);
+}
+static size_t scratch_points(size_t work) { return (size_t)grid_for(work, 256) * 256 * G1NTT_TAB; }
+
+static Fq30 beta30() {
+    Fq b;
+    for (int i = 0; i < 12; i++) b.v[i] = GLV_BETA[i];
+    return to30(to_mont(b));
+}
+
+// recoded twiddles base^e (Montgomery base), e < count, into d_out; d_pw: count Fr of scratch
+static int glv_table(kzg_ctx *ctx, hipStream_t st, const Fr &base, size_t count, Fr *d_pw, GlvTw *d_out) {
+    KZG_TRY(pow_table(ctx, st, base, Fr::one(), count, d_pw));
+    KZG_LAUNCH(ctx, st, "k_glv_twiddles", k_glv_twiddles, (unsigned)((count + 255) / 256), 256, 0, d_pw, count, d_out);
+    return KZG_OK;
+}
+
+// one G1 DFT of size d = 2^logd over `batch` arrays.  forward: DIF (natural -> bit-reversed); else DIT with inverse twiddles
+// (bit-reversed -> natural), half_out: only the first half of the last stage.  tw: recoded twiddles of a size-D table, tws = D / d.
+static int g1_dft(kzg_ctx *ctx, hipStream_t st, MsmPoint *P, size_t pstride, uint32_t logd, size_t batch, const GlvTw *tw, size_t tws,
+                  bool forward, bool half_out, MsmPoint *scratch, const Fq30 &beta) {
+    const size_t d = (size_t)1 << logd;
+    if (d < 2) return KZG_OK;
+    const unsigned g = grid_for(batch * d / 2, 256);
+    if (forward) {
+        for (size_t m = d / 2; m >= 2; m /= 2)
+            KZG_LAUNCH(ctx, st, "k_g1ntt_dif", k_g1ntt_dif, g, 256, 0, P, pstride, d, m, tw, tws, batch, scratch, beta);
+        KZG_LAUNCH(ctx, st, "k_g1ntt_trivial", k_g1ntt_trivial, g, 256, 0, P, pstride, d, batch, 0);
+    } else {
+        KZG_LAUNCH(ctx, st, "k_g1ntt_trivial", k_g1ntt_trivial, g, 256, 0, P, pstride, d, batch, (half_out && d == 2) ? 1 : 0);
+        for (size_t m = 2; m <= d / 2; m *= 2)
+            KZG_LAUNCH(ctx, st, "k_g1ntt_dit", k_g1ntt_dit, g, 256, 0, P, pstride, d, m, tw, tws, batch, scratch, beta,
+                       (half_out && m == d / 2) ? 1 : 0);
+    }
+    return KZG_OK;
+}
+
+}  // namespace kzg
+
+using namespace kzg;
+
+struct kzg_fk20 {
+    int device = 0;
+    uint32_t log_n = 0;
+    size_t N = 0;
+    size_t srs_n = 0;               // length of the monomial SRS the plan was built from
+    MsmPoint *xhat = nullptr;       // DFT_2N(x), bit-reversed (2N points)
+    GlvTw *tw_fwd = nullptr;        // w_2N^e, e < N
+    GlvTw *tw_inv = nullptr;        // w_2N^-e, e < N
+    Fr inv2n;                       // 1 / 2N, Montgomery
+    Fq30 beta;
+};
+
+static void fk20_release(kzg_fk20 *p) {
+    if (!p) return;
+    if (p->xhat) hipFree(p->xhat);
+    if (p->tw_fwd) hipFree(p->tw_fwd);
+    if (p->tw_inv) hipFree(p->tw_inv);
+    delete p;
+}
+
+extern "C" int kzg_fk20_setup(kzg_ctx *ctx, const kzg_srs *monomial, uint32_t log_n, kzg_fk20 **out) {
+    if (!ctx || !monomial || !out) return KZG_ERR_SHAPE;
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (monomial->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "SRS resident on another GPU");
+    if (log_n + 1 >= FR_TWO_ADICITY) return fail(ctx, KZG_ERR_DEGREE_TOO_LARGE, "domain too large");
+    if (log_n > FK20_MAX_LOG) return fail(ctx, KZG_ERR_SHAPE, "kzg_fk20_setup: log_n <= 22 (documented limit)");
+    kzg_fk20 *p = new kzg_fk20();
+    p->device = ctx->device;
+    p->log_n = log_n;
+    p->N = (size_t)1 << log_n;
+    p->srs_n = monomial->n;
+    p->beta = beta30();
+    const size_t N = p->N, two = 2 * N;
+    const Fr w = host_omega(log_n + 1);  // w_2N, w_2N^2 = w_N = compute_omega(N).omega
+    p->inv2n = inv(from_u64<FrParams>((uint64_t)two));
+    hipStream_t st = ctx->lanes[0].stream;
+    int rc = KZG_OK;
+    Fr *pw = nullptr;
+    MsmPoint *scratch = nullptr;
+    const size_t scr = scratch_points(N);
+    if (hipMalloc((void **)&p->xhat, two * sizeof(MsmPoint)) != hipSuccess || hipMalloc((void **)&p->tw_fwd, N * sizeof(GlvTw)) != hipSuccess ||
+        hipMalloc((void **)&p->tw_inv, N * sizeof(GlvTw)) != hipSuccess || hipMalloc((void **)&pw, N * sizeof(Fr)) != hipSuccess ||
+        hipMalloc((void **)&scratch, scr * sizeof(MsmPoint)) != hipSuccess)
+        rc = fail(ctx, KZG_ERR_ALLOC, "hipMalloc(FK20 plan)");
+    if (rc == KZG_OK) rc = glv_table(ctx, st, w, N, pw, p->tw_fwd);
+    if (rc == KZG_OK) rc = glv_table(ctx, st, inv(w), N, pw, p->tw_inv);
+    if (rc == KZG_OK) {
+        KZG_LAUNCH(ctx, st, "k_fk20_load_x", k_fk20_load_x, (unsigned)((two + 255) / 256), 256, 0, monomial->table, monomial->n, N,
+                   p->xhat);
+        rc = g1_dft(ctx, st, p->xhat, two, log_n + 1, 1, p->tw_fwd, 1, true, false, scratch, p->beta);
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "FK20 plan kernels failed");
+    if (hipGetLastError() != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "FK20 plan kernels failed");
+    if (pw) hipFree(pw);
+    if (scratch) hipFree(scratch);
+    if (ctx->prof) prof_collect(ctx);
+    if (rc != KZG_OK) {
+        fk20_release(p);
+        return rc;
+    }
+    *out = p;
+    return KZG_OK;
+}
+
+extern "C" void kzg_fk20_free(kzg_ctx *ctx, kzg_fk20 *plan) {
+    if (!plan) return;
+    if (ctx) {
+        Guard g(ctx);
+        hipSetDevice(plan->device);
+        hipDeviceSynchronize();
+        fk20_release(plan);
+        return;
+    }
+    hipSetDevice(plan->device);
+    hipDeviceSynchronize();
+    fk20_release(plan);
+}
+
+extern "C" size_t kzg_fk20_domain(const kzg_fk20 *plan) { return plan ? plan->N : 0; }
+
+namespace kzg {
+
+// every witness of `batch` polynomials of n coefficients (eval: N evaluations each), in chunks
+static int fk20_run(kzg_ctx *ctx, const kzg_fk20 *p, const void *in, size_t n, size_t batch, int sfmt, int flags, void *out, int ofmt,
+                    bool eval) {
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (sfmt != KZG_FR_MONT_LE_32 && sfmt != KZG_FR_CANONICAL_LE_32) return fail(ctx, KZG_ERR_SHAPE, "unknown scalar format");
+    const size_t psz = point_format_bytes(ofmt);
+    if (!psz) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 output format");
+    if (p->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "FK20 plan resident on another GPU");
+    const size_t N = p->N, two = 2 * N;
+    if (eval && n != N) return fail(ctx, KZG_ERR_SHAPE, "assert!(self.d == evals.d): evaluations must cover the plan's domain");
+    if (n == 0) return fail(ctx, KZG_ERR_SHAPE, "empty polynomial");
+    if (n > N) return fail(ctx, KZG_ERR_SHAPE, "polynomial longer than the plan's domain");
+    if (n - 1 > p->srs_n) return fail(ctx, KZG_ERR_SHAPE, "quotient longer than the SRS (reference: slice index panic)");
+    if (batch == 0) return KZG_OK;
+    if (batch > SIZE_MAX / (N * 144)) return fail(ctx, KZG_ERR_SHAPE, "batch too large");
+    if (!in || !out) return KZG_ERR_SHAPE;
+    const int lane = 0;
+    hipStream_t st = ctx->lanes[lane].stream;
+    const bool out_dev = (flags & KZG_OUT_DEVICE) != 0, in_dev = (flags & KZG_IN_DEVICE) != 0;
+    const uint8_t *src = (const uint8_t *)in;
+    uint8_t *dst = (uint8_t *)out;
+    if (N == 1) {  // every quotient is zero: the identity, as kzg_witness_eval / kzg_witness_coeff_many write it
+        const size_t chunk = std::min(batch, FK20_CHUNK_POINTS);
+        KZG_TRY(lane_reserve(ctx, lane, out_dev ? 4096 : chunk * psz + 4096));
+        for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+            const size_t B = std::min(chunk, batch - b0);
+            uint8_t *d_out = out_dev ? dst + b0 * psz : (uint8_t *)ctx->lanes[lane].arena;
+            KZG_LAUNCH(ctx, st, "k_fk20_emit", k_fk20_emit, (unsigned)std::min<size_t>((B + 63) / 64, 4096), 64, 0, (const MsmPoint *)nullptr,
+                       (size_t)0, 0u, B, d_out, ofmt, psz);
+            if (!out_dev) KZG_HIP_CHECK(ctx, hipMemcpyAsync(dst + b0 * psz, d_out, B * psz, hipMemcpyDeviceToHost, st));
+        }
+        KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        KZG_HIP_CHECK(ctx, hipGetLastError());
+        return KZG_OK;
+    }
+    const uint32_t logn = p->log_n, log2n = logn + 1;
+    const size_t chunk = std::max<size_t>(1, std::min(FK20_MAX_CHUNK, FK20_CHUNK_POINTS / two));
+    const size_t B0 = std::min(chunk, batch);
+    const size_t in_bytes = B0 * n * 32;
+    const size_t scr = scratch_points(B0 * two);
+    size_t need = align_up(B0 * two * sizeof(MsmPoint), 256) + 2 * align_up(B0 * two * 32, 256) + align_up(scr * sizeof(MsmPoint), 256) +
+                  (in_dev ? 0 : align_up(in_bytes, 256)) + (out_dev ? 0 : align_up(B0 * N * psz, 256)) +
+                  ntt_workspace_bytes(log2n) + 65536;
+    KZG_TRY(lane_reserve(ctx, lane, need));
+    MsmPoint *P = (MsmPoint *)lane_alloc(ctx, lane, B0 * two * sizeof(MsmPoint));
+    Fr *y = (Fr *)lane_alloc(ctx, lane, B0 * two * 32);
+    Fr *yh = (Fr *)lane_alloc(ctx, lane, B0 * two * 32);
+    MsmPoint *scratch = (MsmPoint *)lane_alloc(ctx, lane, scr * sizeof(MsmPoint));
+    uint8_t *d_in = in_dev ? nullptr : (uint8_t *)lane_alloc(ctx, lane, in_bytes);
+    uint8_t *d_stage = out_dev ? nullptr : (uint8_t *)lane_alloc(ctx, lane, B0 * N * psz);
+    if (!P || !y || !yh || !scratch || (!in_dev && !d_in) || (!out_dev && !d_stage)) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    const size_t ntt_mark = ctx->lanes[lane].arena_used;  // every ntt_run below takes its scratch from here (stream-ordered reuse)
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t B = std::min(chunk, batch - b0);
+        const uint8_t *d_src = src + b0 * n * 32;
+        if (!in_dev) {
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_in, d_src, B * n * 32, hipMemcpyHostToDevice, st));
+            d_src = d_in;
+        }
+        const Fr *coeffs = (const Fr *)d_src;
+        int csfmt = sfmt;
+        if (eval) {
+            // iNTT_N of each evaluation vector (Montgomery) into the first N slots of yh, then the coefficients' form is Montgomery
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(yh, d_src, B * N * 32, hipMemcpyDeviceToDevice, st));
+            if (sfmt == KZG_FR_CANONICAL_LE_32) KZG_TRY(fr_convert(ctx, st, yh, B * N, 1));
+            for (size_t b = 0; b < B; b++) {
+                ctx->lanes[lane].arena_used = ntt_mark;
+                KZG_TRY(ntt_run(ctx, lane, yh + b * N, logn, 1));
+            }
+            coeffs = yh;
+            csfmt = KZG_FR_MONT_LE_32;
+        }
+        const unsigned gw = (unsigned)std::min<size_t>((B * two + 255) / 256, 8192);
+        KZG_LAUNCH(ctx, st, "k_fk20_build_y", k_fk20_build_y, gw, 256, 0, coeffs, n, N, B, csfmt, y);
+        for (size_t b = 0; b < B; b++) {
+            ctx->lanes[lane].arena_used = ntt_mark;
+            KZG_TRY(ntt_run(ctx, lane, y + b * two, log2n, 0));
+        }
+        KZG_LAUNCH(ctx, st, "k_fk20_scale_brev", k_fk20_scale_brev, gw, 256, 0, y, log2n, p->inv2n, B, yh);
+        KZG_LAUNCH(ctx, st, "k_fk20_pointwise", k_fk20_pointwise, grid_for(B * two, 256), 256, 0, P, p->xhat, yh, two, B, scratch, p->beta);
+        KZG_TRY(g1_dft(ctx, st, P, two, log2n, B, p->tw_inv, 1, false, true, scratch, p->beta));  // H = iDFT_2N, first half
+        KZG_TRY(g1_dft(ctx, st, P, two, logn, B, p->tw_fwd, 2, true, false, scratch, p->beta));   // pi = DFT_N(H), bit-reversed
+        uint8_t *d_out = out_dev ? dst + b0 * N * psz : d_stage;
+        KZG_LAUNCH(ctx, st, "k_fk20_emit", k_fk20_emit, (unsigned)std::min<size_t>((B * N + 63) / 64, 16384), 64, 0, (const MsmPoint *)P,
+                   two, logn, B, d_out, ofmt, psz);
+        if (!out_dev) KZG_HIP_CHECK(ctx, hipMemcpyAsync(dst + b0 * N * psz, d_stage, B * N * psz, hipMemcpyDeviceToHost, st));
+    }
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    KZG_HIP_CHECK(ctx, hipGetLastError());
+    if (ctx->prof) prof_collect(ctx);
+    return KZG_OK;
+}
+
+}  // namespace kzg
+
+extern "C" int kzg_witness_all_coeff(kzg_ctx *ctx, const kzg_fk20 *plan, const void *coeffs, size_t n, size_t batch, int sfmt,
+                                     int flags, void *out, int ofmt) {
+    if (!ctx || !plan) return KZG_ERR_SHAPE;
+    return fk20_run(ctx, plan, coeffs, n, batch, sfmt, flags, out, ofmt, false);
+}
+
+extern "C" int kzg_witness_all_eval(kzg_ctx *ctx, const kzg_fk20 *plan, const void *evals, size_t d, size_t batch, int sfmt,
+                                    int flags, void *out, int ofmt) {
+    if (!ctx || !plan) return KZG_ERR_SHAPE;
+    return fk20_run(ctx, plan, evals, d, batch, sfmt, flags, out, ofmt, true);
+}
+
+#ifdef KZG_TEST_HOOKS
+#include "../../include/kzg_mi355x_test.h"
+
+namespace kzg {
+__global__ __launch_bounds__(256) void k_test_g1_mul_glv(const G1Affine *p, const Fr *k, size_t n, MsmPoint *scratch, Fq30 beta,
+                                                         G1Affine *o) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (size_t i = tid; i < n; i += nt) {
+        const MsmPoint P = g1_from_affine30(g1_affine_to30(p[i]), false);
+        const GlvTw w = glv_recode(k[i].v);
+        emit_one(glv_mul(P, w, scratch + tid, nt, beta), (uint8_t *)(o + i), KZG_G1_AFFINE_MONT_96);
+    }
+}
+
+// affine in, natural order (inverse: loaded bit-reversed for the DIT)
+__global__ __launch_bounds__(256) void k_test_g1ntt_load(const G1Affine *in, size_t d, uint32_t bits, int rev, MsmPoint *P) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= d) return;
+    P[i] = g1_from_affine30(g1_affine_to30(in[rev ? brev(i, bits) : i]), false);
+}
+}  // namespace kzg
+
+extern "C" int kzg_test_g1_mul_glv(kzg_ctx *ctx, const void *p, const void *k_canonical, size_t n, void *out) {
+    if (!ctx || !p || !k_canonical || !out || !n) return KZG_ERR_SHAPE;
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const size_t scr = scratch_points(n);
+    KZG_TRY(lane_reserve(ctx, 0, n * (96 + 32 + 96) + scr * sizeof(MsmPoint) + 65536));
+    hipStream_t st = ctx->lanes[0].stream;
+    void *dp = lane_alloc(ctx, 0, n * 96), *dk = lane_alloc(ctx, 0, n * 32), *dout = lane_alloc(ctx, 0, n * 96);
+    MsmPoint *scratch = (MsmPoint *)lane_alloc(ctx, 0, scr * sizeof(MsmPoint));
+    if (!dp || !dk || !dout || !scratch) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(dp, p, n * 96, hipMemcpyHostToDevice, st));
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(dk, k_canonical, n * 32, hipMemcpyHostToDevice, st));
+    KZG_LAUNCH(ctx, st, "k_test_g1_mul_glv", k_test_g1_mul_glv, grid_for(n, 256), 256, 0, (const G1Affine *)dp, (const Fr *)dk, n,
+               scratch, beta30(), (G1Affine *)dout);
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(out, dout, n * 96, hipMemcpyDeviceToHost, st));
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    KZG_HIP_CHECK(ctx, hipGetLastError());
+    return KZG_OK;
+}
+
+// out_m = sum_j w^(+-jm) P_j over the size-2^log_n domain (the inverse is NOT scaled by 1 / d)
+extern "C" int kzg_test_g1_ntt(kzg_ctx *ctx, const void *pts, uint32_t log_n, int inverse, void *out) {
+    if (!ctx || !pts || !out || log_n > FK20_MAX_LOG) return KZG_ERR_SHAPE;
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const size_t d = (size_t)1 << log_n, half = d > 1 ? d / 2 : 1;
+    const size_t scr = scratch_points(half);
+    KZG_TRY(lane_reserve(ctx, 0, d * (96 + 96 + sizeof(MsmPoint)) + half * (32 + sizeof(GlvTw)) + scr * sizeof(MsmPoint) + 65536));
+    hipStream_t st = ctx->lanes[0].stream;
+    void *din = lane_alloc(ctx, 0, d * 96), *dout = lane_alloc(ctx, 0, d * 96);
+    MsmPoint *P = (MsmPoint *)lane_alloc(ctx, 0, d * sizeof(MsmPoint));
+    Fr *pw = (Fr *)lane_alloc(ctx, 0, half * 32);
+    GlvTw *tw = (GlvTw *)lane_alloc(ctx, 0, half * sizeof(GlvTw));
+    MsmPoint *scratch = (MsmPoint *)lane_alloc(ctx, 0, scr * sizeof(MsmPoint));
+    if (!din || !dout || !P || !pw || !tw || !scratch) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(din, pts, d * 96, hipMemcpyHostToDevice, st));
+    const Fr w = host_omega(log_n);
+    KZG_TRY(glv_table(ctx, st, inverse ? inv(w) : w, half, pw, tw));
+    KZG_LAUNCH(ctx, st, "k_test_g1ntt_load", k_test_g1ntt_load, (unsigned)((d + 255) / 256), 256, 0, (const G1Affine *)din, d, log_n,
+               inverse ? 1 : 0, P);
+    KZG_TRY(g1_dft(ctx, st, P, d, log_n, 1, tw, 1, !inverse, false, scratch, beta30()));
+    if (inverse) {  // natural order out: d "polynomials" of one point each
+        KZG_LAUNCH(ctx, st, "k_fk20_emit", k_fk20_emit, (unsigned)((d + 63) / 64), 64, 0, (const MsmPoint *)P, (size_t)1, 0u, d,
+                   (uint8_t *)dout, (int)KZG_G1_AFFINE_MONT_96, (size_t)96);
+    } else {
+        KZG_LAUNCH(ctx, st, "k_fk20_emit", k_fk20_emit, (unsigned)((d + 63) / 64), 64, 0, (const MsmPoint *)P, d, log_n, (size_t)1,
+                   (uint8_t *)dout, (int)KZG_G1_AFFINE_MONT_96, (size_t)96);
+    }
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(out, dout, d * 96, hipMemcpyDeviceToHost, st));
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    KZG_HIP_CHECK(ctx, hipGetLastError());
+    return KZG_OK;
+}
+#endif  // KZG_TEST_HOOKS
