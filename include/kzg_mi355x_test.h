@@ -25,6 +25,53 @@ int kzg_test_g1_mul_glv(kzg_ctx *ctx, const void *p, const void *k_canonical, si
 /* one G1 DFT of 2^log_n points over compute_omega(2^log_n): out_m = sum_j w^(jm) P_j, or w^(-jm) with `inverse` (NOT scaled by
  * 1 / 2^log_n); affine Montgomery in and out, natural order */
 int kzg_test_g1_ntt(kzg_ctx *ctx, const void *pts, uint32_t log_n, int inverse, void *out);
+/* kzg_test_arith: the device twin of the arithmetic shims of tests/host_math.cpp (kzg_amd/csrc/arith_hooks.hip).  One thread per
+ * record runs the same functions in the same order as the host shim, so on gfx950 it exercises the generated inline-asm branch
+ * (mul_gfx950.inc, mul30_gfx950.inc, mul29r_gfx950.inc) where the host build runs the portable C.  Record `i` of the input is the
+ * shim's arguments laid out back to back (in_rec bytes), record `i` of the output its output buffers (out_rec bytes).  An unknown
+ * op, n == 0, or an in_rec / out_rec that is not the op's returns KZG_ERR_SHAPE.  Fq: 12 x u32, Fr: 8 x u32, Fq30: 13 x i32,
+ * Fr29: 9 x u32, G1: affine Montgomery 96 B, all little-endian.  The contract of each op is the one its portable version is
+ * proven for (tests/test_host_math.py); outside it the result is unspecified.
+ *
+ *  op                          in_rec  out_rec  record (in -> out)                  contract
+ *  FQ_MUL / FQ_ADD / FQ_SUB     96      48      a, b -> a*b/R, a+b, a-b mod q       a, b < q
+ *  FR_MUL / FR_ADD / FR_SUB     64      32      a, b -> same mod r                  a, b < r
+ *  MUL30, MUL30U                104     52      a, b -> a*b/2^390 (balanced / unsigned digits)
+ *                                                                                   limbs 0..11 in [-2^29, 2^29] or one operand's in
+ *                                                                                   [0, 2^30); limb 12 below 2^27 (|value| < 80 q)
+ *  SQR30                        52      52      a -> a^2/2^390                      limbs 0..11 in [-2^29, 2^29); limb 12 below 2^27
+ *  MULADD30                     208     52      a, b, c, d -> (ab + cd)/2^390       as MUL30
+ *  MUL30_SUB                    156     52      a, b, c -> ab/2^390 - c             as MUL30; c likewise
+ *  SQR30_SUB2, SQR30_SUB2U      156     52      a, c, e -> a^2/2^390 - c - 2e       a as SQR30; c, e as MUL30's operands
+ *  NORMALIZE30                  52      52      a -> the balanced digits of a       limbs 0..11 below 3 * 2^29; limb 12 below 2^20
+ *  FROM30                       52      48      a -> a/2^390 * R mod q, canonical   normalised, |a| < 256 q
+ *  MADD30_CHAIN                 1552    96      u32 n, u32 0, u64 signs, 16 G1 ->   1 <= n <= 16; the points on the curve; the chain of
+ *                                               sum +-P_i (hm_madd30_chain_kernel_form, k_accum_affine's lazy accumulator)
+ *  ADD30                        192     96      P, Q -> P + Q via dbl30/madd30/add30  points on the curve
+ *  MUL30_SCALAR                 128     96      P, k (8 x u32) -> [k]P (dbl30/add30) P on the curve
+ *  FR29_MUL                     64      32      x, w*2^256 mod r -> x*w mod r       x < 2^256, w < r
+ *  FR29_BUTTERFLIES             100     64      u, v, w_mont, i32 stages -> u', v'  u, v, w < r; 0 <= stages <= 12
+ *  FR29_SHOUP_RAW               68      108     x (9 limbs), w_mont -> x*w (9 limbs), w, wp
+ *                                                                                   x < 2^261, limbs below 1.5 * 2^30; w < r
+ *  FR29_RADIX4_CHAIN            1192    32      x0, 18 x Fr, 18 x Fr w_mont, i32 pairs, i32 which -> chain value
+ *                                                                                   0 <= pairs <= 6, 0 <= which <= 3, w < r
+ *  FR29_QUOTIENT_THREAD         716     68      a[8], x_mont, p_mont, nb[10] (9 limbs), i32 m, a_next -> o_scan, o_next, u32 top
+ *                                                                                   0 <= m <= 10, nb below 25 r normalised, a_next < r
+ *  MULSHOUP29X2                 136     72      (x, w_mont) twice -> both products via ONE interleaved mulshoup29x2 (no host twin:
+ *                                                                                   each half equals FR29_SHOUP_RAW's product); as FR29_SHOUP_RAW
+ *  EMIT                         132     144     P, k (8 x u32), i32 fmt -> emit_one of [k]P in `fmt` (bytes beyond the format's
+ *                                                                                   size are zero); P on the curve, fmt a KZG_G1_* format
+ */
+enum {
+    KZG_ARITH_FQ_MUL = 0, KZG_ARITH_FQ_ADD = 1, KZG_ARITH_FQ_SUB = 2, KZG_ARITH_FR_MUL = 3, KZG_ARITH_FR_ADD = 4, KZG_ARITH_FR_SUB = 5,
+    KZG_ARITH_MUL30 = 6, KZG_ARITH_SQR30 = 7, KZG_ARITH_MULADD30 = 8, KZG_ARITH_MUL30_SUB = 9, KZG_ARITH_MUL30U = 10,
+    KZG_ARITH_SQR30_SUB2 = 11, KZG_ARITH_SQR30_SUB2U = 12, KZG_ARITH_NORMALIZE30 = 13, KZG_ARITH_FROM30 = 14,
+    KZG_ARITH_MADD30_CHAIN = 15, KZG_ARITH_ADD30 = 16, KZG_ARITH_MUL30_SCALAR = 17,
+    KZG_ARITH_FR29_MUL = 18, KZG_ARITH_FR29_BUTTERFLIES = 19, KZG_ARITH_FR29_SHOUP_RAW = 20, KZG_ARITH_FR29_RADIX4_CHAIN = 21,
+    KZG_ARITH_FR29_QUOTIENT_THREAD = 22, KZG_ARITH_MULSHOUP29X2 = 23, KZG_ARITH_EMIT = 24,
+    KZG_ARITH_NUM_OPS = 25
+};
+int kzg_test_arith(kzg_ctx *ctx, int op, const void *in, size_t in_rec, size_t n, void *out, size_t out_rec);
 /* pretend `srs` is resident on GPU `device` (the "SRS of another GPU" error of every MSM entry point, on a one-GPU box) */
 int kzg_test_srs_set_device(struct kzg_srs *srs, int device);
 /* the next sharded call of this group fails locally on local GPU 0 with `code` (status agreement across ranks, mgpu.hip) */

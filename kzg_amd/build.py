@@ -2,8 +2,8 @@
 
 msm.hip (the bucket-accumulation kernel) and ntt.hip go through their assembly: hipcc -S for the device side, tools-free
 post-processing (strip_asm_nops below), then assembler, lld and the offload bundler exactly as hipcc itself would run them, and the
-host side compiled against that device image.  Everything else is a plain `hipcc -c`; so are those two when the compiler is not the
-one the post-processing was validated with (asm_path_ok)."""
+host side compiled against that device image; so does arith_hooks.hip, the arithmetic test kernels of the hooks library.  Everything
+else is a plain `hipcc -c`; so are those when the compiler is not the one the post-processing was validated with (asm_path_ok)."""
 import os
 import re
 import subprocess
@@ -16,12 +16,17 @@ OUT = os.path.join(HERE, "libkzg_mi355x.so")
 # the same library with the unit-test hooks of include/kzg_mi355x_test.h compiled in (-DKZG_TEST_HOOKS): loaded by tests/ only
 OUT_HOOKS = os.path.join(HERE, "libkzg_mi355x_hooks.so")
 HOOK_SOURCES = ["capi.hip", "mgpu.hip", "g1ntt.hip"]  # the translation units that hold hooks (runtime.hip holds none)
+# translation units of the hooks library only (no product counterpart): kzg_test_arith, the device twin of tests/host_math.cpp
+HOOK_ONLY_SOURCES = ["arith_hooks.hip"]
 SOURCES = ["capi.hip", "runtime.hip", "msm.hip", "srs.hip", "ntt.hip", "poly.hip", "witness.hip", "pairing.hip", "msm_wide.hip", "msm_tail.hip", "mgpu.hip", "gfft.hip", "g1ntt.hip"]
 # per-file extra flags (none at present; out-of-line multiplies for the tail kernels were measured: no gain)
 EXTRA_FLAGS = {}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
-# translation units whose device assembly is post-processed
-VIA_ASM = ["msm.hip", "ntt.hip"]
+# translation units whose device assembly is post-processed (arith_hooks.hip: so that the tests check the generated asm in the form
+# the hot kernels run it)
+VIA_ASM = ["msm.hip", "ntt.hip", "arith_hooks.hip"]
+# {translation unit: s_nop removed by strip_asm_nops} of the objects in the build directory (tests/test_generated_sources.py reads it)
+NOPS_FILE = "nops_removed.json"
 LLVM_BIN = os.environ.get("KZG_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 # the compiler the post-processing rule was validated with (its own nop placement and hazard model); any other compiler, or a
 # missing assembler / linker / bundler, gets the plain `hipcc -c` path with the nops in place
@@ -135,6 +140,7 @@ def build(force=False, verbose=False, out=None, defines=(), strip_nops=True, tag
         if strip_nops:
             text, removed = strip_asm_nops(text)
         open(base + "_dev_pp.s", "w").write(text)
+        nops[os.path.basename(src)] = removed
         if verbose:
             print(f"{os.path.basename(src)}: {removed} s_nop removed behind v_mad blocks", flush=True)
         run([os.path.join(LLVM_BIN, "clang"), "-target", "amdgcn-amd-amdhsa", "-mcpu=gfx950", "-c", base + "_dev_pp.s", "-o", base + "_dev.o"])
@@ -145,6 +151,7 @@ def build(force=False, verbose=False, out=None, defines=(), strip_nops=True, tag
              "-output=" + base + ".hipfb"])
         run([hipcc] + flags + extra + ["--cuda-host-only", "-Xclang", "-fcuda-include-gpubinary", "-Xclang", base + ".hipfb", "-c", src, "-o", obj])
 
+    nops = {}    # {translation unit: s_nop removed} of the objects built by this call
     jobs = []
     for s in srcs:
         src = os.path.join(CSRC, s)
@@ -155,10 +162,22 @@ def build(force=False, verbose=False, out=None, defines=(), strip_nops=True, tag
                 jobs.append(("asm", src, obj, extra))
             else:
                 jobs.append(("cc", [hipcc] + flags + extra + ["-c", src, "-o", obj]))
+                if s in VIA_ASM:
+                    nops[s] = 0      # built with the nops in place
         if s in HOOK_SOURCES and not variant:
             hobj = os.path.join(objdir, s.replace(".hip", "_hooks.o"))
             if force or _stale(hobj, [src] + hdrs):
                 jobs.append(("cc", [hipcc] + flags + extra + ["-DKZG_TEST_HOOKS", "-c", src, "-o", hobj]))
+    if not variant:
+        for s in HOOK_ONLY_SOURCES:
+            src = os.path.join(CSRC, s)
+            hobj = os.path.join(objdir, s.replace(".hip", ".o"))
+            if force or _stale(hobj, [src] + hdrs):
+                if s in VIA_ASM and asm_path_ok(hipcc):
+                    jobs.append(("asm", src, hobj, ["-DKZG_TEST_HOOKS"]))
+                else:
+                    jobs.append(("cc", [hipcc] + flags + ["-DKZG_TEST_HOOKS", "-c", src, "-o", hobj]))
+                    nops[s] = 0
 
     def do(job):
         if job[0] == "asm":
@@ -168,11 +187,22 @@ def build(force=False, verbose=False, out=None, defines=(), strip_nops=True, tag
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         list(ex.map(do, jobs))
+    if nops:     # merged with the record of the objects this build did not touch
+        import json
+        nf = os.path.join(objdir, NOPS_FILE)
+        try:
+            rec = json.load(open(nf))
+        except (OSError, ValueError):
+            rec = {}
+        rec.update(nops)
+        with open(nf, "w") as f:
+            json.dump(rec, f, indent=1, sort_keys=True)
     objs = [os.path.join(objdir, s.replace(".hip", ".o")) for s in srcs]
     if force or jobs or _stale(target, objs):
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs + ["-ldl", "-lpthread"])
     if not variant:
         hobjs = [os.path.join(objdir, s.replace(".hip", "_hooks.o" if s in HOOK_SOURCES else ".o")) for s in srcs]
+        hobjs += [os.path.join(objdir, s.replace(".hip", ".o")) for s in HOOK_ONLY_SOURCES]
         if force or jobs or _stale(OUT_HOOKS, hobjs):
             run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT_HOOKS] + hobjs + ["-ldl", "-lpthread"])
     return target

@@ -8,6 +8,7 @@ import subprocess
 import pytest
 
 from oracle import kzg_model as M, c_oracle as C
+from tests import arith_vectors as AV
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -52,6 +53,15 @@ def test_field_ops(L):
         assert call(L.hm_fr_sub, b(a, 32), b(c, 32), n=32) == (a - c) % M.R
         assert call(L.hm_fr_to_mont, b(a, 32), n=32) == a * Rr % M.R
         assert call(L.hm_fr_from_mont, b(a, 32), n=32) == a * pow(Rr, -1, M.R) % M.R
+    # explicit edges (tests/arith_vectors.py: 0, 1, p-1, p-2, R mod p, sums of p, p-1 and 2p-2, a = b, a borrow from every limb,
+    # all-ones limb patterns)
+    for p, nl, fns in ((M.Q, 12, (L.hm_fq_mul, L.hm_fq_add, L.hm_fq_sub)), (M.R, 8, (L.hm_fr_mul, L.hm_fr_add, L.hm_fr_sub))):
+        rinv = pow(1 << (32 * nl), -1, p)
+        for a, c in AV.saturated_edges(p, nl):
+            args = (b(a, 4 * nl), b(c, 4 * nl))
+            assert call(fns[0], *args, n=4 * nl) == a * c * rinv % p
+            assert call(fns[1], *args, n=4 * nl) == (a + c) % p
+            assert call(fns[2], *args, n=4 * nl) == (a - c) % p
     # inv() = safegcd (Bernstein-Yang divsteps), inv_bgcd() = binary extended GCD, inv_fermat() = a^(p-2):
     # all three against python, incl. edge values and values around the 30-bit limb boundaries
     for a in [1, 2, 3, M.Q - 1, M.Q - 2, (M.Q + 1) // 2, 1 << 380, 2 ** 30, 2 ** 30 - 1, 2 ** 60 + 1] + \
@@ -183,122 +193,65 @@ def test_fq30_raw_limb_bounds(L):
     64-bit column accumulators must survive (26 products of 2^58 per column; the fused multiply-add sets the
     high part aside in the five columns that hold more than 30): results are exact Montgomery quotients,
     normalised, and inside the documented magnitude bound."""
-    import struct
     rng = random.Random(3030)
-    N, B = 13, 30
-    R30, H = 1 << (N * B), 1 << (B - 1)
-
-    def val(l):
-        return sum(v << (B * i) for i, v in enumerate(l))
-
-    def raw(l):
-        return struct.pack("<13i", *l)
+    H, val, limbs, check = AV.H30, AV.val30, (lambda kind: AV.limbs30(rng, kind)), AV.check_mont30
 
     def out(fn, *args):
         o = ctypes.create_string_buffer(52)
-        fn(*[raw(a) for a in args], o)
-        return list(struct.unpack("<13i", o.raw))
+        fn(*[AV.raw30(a) for a in args], o)
+        return AV.unraw30(o.raw)
 
-    def limbs(kind):
-        if kind == "max":
-            l = [H - 1] * 12
-        elif kind == "min":
-            l = [-H] * 12
-        elif kind == "neg_of_min":          # limb-wise negation of a normalised value: +2^29 digits
-            l = [H] * 12
-        elif kind == "alt":
-            l = [(-H if i & 1 else H - 1) for i in range(12)]
-        else:
-            l = [rng.randrange(-H, H) for _ in range(12)]
-        return l + [rng.randrange(-(1 << 27), 1 << 27)]   # |value| < 2^387 ~ 80 q
-
-    def check(r, num, bound_q):
-        assert all(-H <= v < H for v in r[:12]), r                       # normalised
-        x = val(r)
-        assert (x * R30 - num) % M.Q == 0                                 # exact Montgomery quotient
-        assert abs(x) * 1000 <= M.Q * int(bound_q * 1000), (abs(x) / M.Q, bound_q)
-
-    kinds = ["max", "min", "neg_of_min", "alt", "rnd", "rnd", "rnd"]
-    qr = M.Q / R30
+    kinds = AV.KINDS30
     for ka in kinds:
         for kb in kinds:
             a, c = limbs(ka), limbs(kb)
             A, Cv = val(a), val(c)
-            check(out(L.hm_mul30_raw, a, c), A * Cv, 0.5001 + abs(A * Cv) / M.Q / M.Q * qr)
+            check(out(L.hm_mul30_raw, a, c), A * Cv, AV.mont30_bound(abs(A * Cv)))
             e, f = limbs(kb), limbs(ka)
             E, F = val(e), val(f)
-            check(out(L.hm_muladd30_raw, a, c, e, f), A * Cv + E * F, 0.5001 + (abs(A * Cv) + abs(E * F)) / M.Q / M.Q * qr)
+            check(out(L.hm_muladd30_raw, a, c, e, f), A * Cv + E * F, AV.mont30_bound(abs(A * Cv) + abs(E * F)))
         if ka != "neg_of_min":                 # sqr30 doubles its operand: needs the normalised range
             a = limbs(ka)
-            check(out(L.hm_sqr30_raw, a), val(a) ** 2, 0.5001 + val(a) ** 2 / M.Q / M.Q * qr)
+            check(out(L.hm_sqr30_raw, a), val(a) ** 2, AV.mont30_bound(val(a) ** 2))
     # merged subtractions (mul30_sub, sqr30_sub2): exact a*b/R - c and a^2/R - c - 2e as integers mod q, normalised output
     for ka in kinds:
         for kb in kinds:
             a, c, u = limbs(ka), limbs(kb), limbs(kb if ka == "rnd" else ka)
-            r = out(L.hm_mul30_sub_raw, a, c, u)
-            assert all(-H <= v < H for v in r[:12]), r
-            assert ((val(r) + val(u)) * R30 - val(a) * val(c)) % M.Q == 0
-            assert abs(val(r)) <= abs(val(a) * val(c)) // R30 + M.Q // 2 + abs(val(u)) + 2
+            AV.check_mul30_sub(out(L.hm_mul30_sub_raw, a, c, u), a, c, u)
             if ka != "neg_of_min":
                 e = limbs(kb)
-                r = out(L.hm_sqr30_sub2_raw, a, u, e)
-                assert all(-H <= v < H for v in r[:12]), r
-                assert ((val(r) + val(u) + 2 * val(e)) * R30 - val(a) ** 2) % M.Q == 0
-                assert abs(val(r)) <= val(a) ** 2 // R30 + M.Q // 2 + abs(val(u)) + 2 * abs(val(e)) + 2
+                AV.check_sqr30_sub2(out(L.hm_sqr30_sub2_raw, a, u, e), a, u, e)
     # unsigned-digit outputs (mul30u, sqr30_sub2u) and their use as ONE operand of the next product: balanced x unsigned at the
     # extremes (every unsigned digit 2^30 - 1 against every balanced digit +-2^29: the column bound 2^62.93 of field30.h)
-    U = (1 << B) - 1
-
     def ulimbs(kind):
-        if kind == "umax":
-            l = [U] * 12
-        elif kind == "uzero":
-            l = [0] * 12
-        else:
-            l = [rng.randrange(0, 1 << B) for _ in range(12)]
-        return l + [rng.randrange(-(1 << 23), 1 << 23)]
+        return AV.ulimbs30(rng, kind)
 
     for ka in kinds:
-        for ku in ("umax", "umax", "urnd", "urnd", "uzero"):
+        for ku in AV.UKINDS30:
             a, u = limbs(ka), ulimbs(ku)
             for fn in (L.hm_mul30u_raw, L.hm_mul30_raw):            # unsigned operand into both output flavours
-                r = out(fn, a, u)
-                assert ((val(r)) * R30 - val(a) * val(u)) % M.Q == 0, (ka, ku)
-                assert abs(val(r)) <= abs(val(a) * val(u)) // R30 + M.Q // 2 + 2
-                if fn is L.hm_mul30u_raw:
-                    assert all(0 <= v < (1 << B) for v in r[:12]), r
-                else:
-                    assert all(-H <= v < H for v in r[:12]), r
+                AV.check_mul30_any(out(fn, a, u), a, u, unsigned=fn is L.hm_mul30u_raw)
             r = out(L.hm_mul30_sub_raw, a, u, ulimbs("umax"))       # unsigned operand and unsigned subtrahend
-            assert all(-H <= v < H for v in r[:12])
+            assert AV.is_normalised30(r)
             if ka != "neg_of_min":
                 c, e = limbs(ka), ulimbs(ku)
-                r = out(L.hm_sqr30_sub2u_raw, a, c, e)
-                assert all(0 <= v < (1 << B) for v in r[:12]), r
-                assert ((val(r) + val(c) + 2 * val(e)) * R30 - val(a) ** 2) % M.Q == 0
+                AV.check_sqr30_sub2(out(L.hm_sqr30_sub2u_raw, a, c, e), a, c, e, unsigned=True)
     # same-sign worst case for every column at once
     a = [H] * 12 + [1 << 20]
-    check(out(L.hm_muladd30_raw, a, a, a, a), 2 * val(a) ** 2, 0.5001 + 2 * val(a) ** 2 / M.Q / M.Q * qr)
+    check(out(L.hm_muladd30_raw, a, a, a, a), 2 * val(a) ** 2, AV.mont30_bound(2 * val(a) ** 2))
     na = [-H] * 12 + [-(1 << 20)]
-    check(out(L.hm_muladd30_raw, a, na, a, na), 2 * val(a) * val(na), 0.5001 + 2 * val(a) ** 2 / M.Q / M.Q * qr)
+    check(out(L.hm_muladd30_raw, a, na, a, na), 2 * val(a) * val(na), AV.mont30_bound(2 * val(a) ** 2))
     # normalize30: any limbs below 2^31 - 2^29 in magnitude -> the unique normalised form of the same integer
     for _ in range(50):
-        l = [rng.randrange(-3 * H + 1, 3 * H) for _ in range(12)] + [rng.randrange(-(1 << 20), 1 << 20)]
+        l = AV.normalize30_input(rng)
         r = out(L.hm_normalize30_raw, l)
-        assert val(r) == val(l) and all(-H <= v < H for v in r[:12])
+        assert val(r) == val(l) and AV.is_normalised30(r)
     # from30 on lazy values up to 256 q in magnitude, either sign: canonical x / R30 * R384
-    Rq = M.FQ_MONT_R
     for _ in range(50):
-        x = rng.randrange(-255 * M.Q, 255 * M.Q)
-        l, t = [], x
-        for _i in range(12):
-            d = ((t + H) % (1 << B)) - H
-            l.append(d)
-            t = (t - d) >> B
-        l.append(t)
+        l, x = AV.from30_input(rng)
         o = ctypes.create_string_buffer(48)
-        L.hm_from30_raw(raw(l), o)
-        assert int.from_bytes(o.raw, "little") == x * pow(R30, -1, M.Q) * Rq % M.Q
+        L.hm_from30_raw(AV.raw30(l), o)
+        assert int.from_bytes(o.raw, "little") == AV.from30_want(x)
 
 
 def test_fr29_ntt_arithmetic(L):
@@ -333,26 +286,18 @@ def test_fr29_quotient_kernel_thread(L):
     canonical value, one output step -- against big-integer arithmetic, at random and at the largest operands."""
     rng = random.Random(291)
     R, R256 = M.R, 1 << 256
-    MASK = (1 << 29) - 1
     for it in range(300):
-        big = it < 6
-        a = [R256 - 1 if big else rng.randrange(R256) for _ in range(8)]
-        x = [R - 1, 1, 0, R - 2, 2, R - 1][it] if big else rng.randrange(R)
-        p = R - 1 if big else rng.randrange(R)
-        m = 10 if big else rng.randrange(0, 11)
-        nbv = [25 * R - 1 - i if big else rng.randrange(25 * R) for i in range(m)]
+        a, x, p, m, nbv, a_next = AV.quotient_case(rng, it)
         nb = (ctypes.c_uint32 * (9 * max(m, 1)))()
         for i, v in enumerate(nbv):         # normalised: limbs below 2^29, the excess in the top limb
-            for j in range(9):
-                nb[9 * i + j] = (v >> (29 * j)) & MASK if j < 8 else v >> 232
-        a_next = rng.randrange(R) if not big else R - 1
+            nb[9 * i: 9 * i + 9] = AV.nb_limbs(v)
         o_scan, o_next, top = ctypes.create_string_buffer(32), ctypes.create_string_buffer(32), ctypes.c_uint32()
         L.hm_fr29_quotient_thread(b"".join(b(v, 32) for v in a), b(x * R256 % R, 32), b(p * R256 % R, 32), nb, m, b(a_next, 32), o_scan, o_next,
                                   ctypes.byref(top))
-        want = (sum(c * pow(x, k, R) for k, c in enumerate(a)) + p * sum(nbv)) % R
+        want, want_next = AV.quotient_want(a, x, p, nbv, a_next)
         assert int.from_bytes(o_scan.raw, "little") == want, it
-        assert int.from_bytes(o_next.raw, "little") == (a_next + want * x) % R, it
-        assert top.value < 64 * (R >> 232), it      # what fr29_reduce_below_2r accepts
+        assert int.from_bytes(o_next.raw, "little") == want_next, it
+        assert top.value < AV.QUOTIENT_TOP_MAX, it      # what fr29_reduce_below_2r accepts
 
 
 def test_fr29_shoup_multiply_and_lazy_radix4(L):
@@ -361,57 +306,23 @@ def test_fr29_shoup_multiply_and_lazy_radix4(L):
     for unnormalised sums with every limb at the 1.5 * 2^30 bound, and for values up to 2^261 - 1; then six stage pairs (the 12
     stages of the largest LDS tile) along the never-multiplied element chain taking the fastest-growing output each time."""
     rng = random.Random(29)
-    R, R256, B261 = M.R, 1 << 256, 1 << 261
-    MASK = (1 << 29) - 1
-
-    def limbs(v):
-        return (ctypes.c_uint32 * 9)(*[(v >> (29 * i)) & MASK for i in range(9)])
-
-    def val(ls):
-        return sum(int(x) << (29 * i) for i, x in enumerate(ls))
+    R, R256 = M.R, 1 << 256
 
     for it in range(400):
-        w = rng.randrange(R) if it > 3 else [0, 1, R - 1, 7][it]
+        w = AV.shoup_twiddle(rng, it)
         out, wl, wpl = (ctypes.c_uint32 * 9)(), (ctypes.c_uint32 * 9)(), (ctypes.c_uint32 * 9)()
-        kind = it % 4
-        if kind == 0:      # normalised, below 2^256 (what a tile load produces)
-            x = rng.randrange(R256)
-            xl = limbs(x)
-        elif kind == 1:    # any value below 2^261
-            x = rng.randrange(B261) if it > 8 else B261 - 1
-            xl = limbs(x)
-        elif kind == 2:    # unnormalised: every limb up to 1.5 * 2^30 (u + 4r - t), value kept below 2^261
-            raw = [rng.randrange(3 << 29) for _ in range(8)] + [rng.randrange(1 << 27)]
-            if it < 12:
-                raw = [(3 << 29) - 1] * 8 + [(1 << 27) - 1]
-            xl = (ctypes.c_uint32 * 9)(*raw)
-            x = val(raw)
-            assert x < B261
-        else:
-            x = rng.randrange(R)
-            xl = limbs(x)
+        raw, x = AV.shoup_operand(rng, it)
+        xl = (ctypes.c_uint32 * 9)(*raw)
         L.hm_fr29_shoup_raw(xl, b(w * R256 % R, 32), out, wl, wpl)
-        assert val(wl) == w and val(wpl) == (w << 261) // R
-        assert all(v <= MASK for v in out)
-        got = val(out)
-        assert got % R == x * w % R and got < 2 * R, (it, kind)
+        assert (AV.val29(wl), AV.val29(wpl)) == AV.shoup_pair(w)
+        AV.check_shoup(list(out), x, w)
     for which in (3, 0, 1, 2):
         for pairs in (1, 5, 6):
             for _ in range(6):
-                x0 = rng.randrange(R256)
-                xs = [rng.randrange(R256) for _ in range(3 * pairs)]
-                ws = [rng.randrange(R) for _ in range(3 * pairs)]
+                x0, xs, ws = AV.radix4_chain_case(rng, pairs)
                 o = ctypes.create_string_buffer(32)
                 L.hm_fr29_radix4_chain(b(x0, 32), b"".join(b(v, 32) for v in xs), b"".join(b(v * R256 % R, 32) for v in ws), pairs, which, o)
-                X0 = x0
-                for p in range(pairs):
-                    x1, x2, x3 = xs[3 * p: 3 * p + 3]
-                    a, bb, c = ws[3 * p: 3 * p + 3]
-                    t1, t3 = x1 * a, x3 * a
-                    s0, y1, s2, y3 = X0 + t1, X0 - t1, x2 + t3, x2 - t3
-                    t2, t3b = s2 * bb, y3 * c
-                    X0 = [s0 + t2, y1 + t3b, s0 - t2, y1 - t3b][which] % R
-                assert int.from_bytes(o.raw, "little") == X0
+                assert int.from_bytes(o.raw, "little") == AV.radix4_chain_ref(x0, xs, ws, pairs, which)
 
 
 def test_naf18_recoding(L):
