@@ -66,6 +66,7 @@ extern "C" {
  *   kzg_verify_eval_batched                 k <= 16384 opening points         (the interpolation works on a k x k matrix: 8.6 GB there)
  *   kzg_srs_lagrange_from_monomial_g1       d <= 2^24;  _g2: d <= 1024
  *   kzg_fk20_setup                          log_n <= 22                      (the plan holds 2N points of 224 B: 1.9 GB there)
+ *   kzg_fk20_cosets_setup                   log_n <= 22, 1 <= log_l <= log_n (the plan holds 8 x 2N rows of 128 B: 8.6 GB there)
  *   MSM                                     table rows x points < 2^31       (the sorted entry is a 31-bit table index + sign);
  *                                           window_bits 18, 19 (option), and 20 with option sort_single_pass: windows x points < 2^27
  *   kzg_g1_sum_batch                        count <= 2^20, groups <= 2^24
@@ -144,6 +145,7 @@ int kzg_sync(kzg_ctx *ctx);
  * "naf_window" (0 / 18, applies to SRSs created afterwards: 18 = positional tables, 2^j P for every bit position j = 255 rows of
  * 128 B per point, scalars recoded in width-18 non-adjacent form -- 13.9 instead of 15 bucket additions per scalar for 17x the
  * table: 34 GB at 2^20; measured +3.7 % batched throughput at 2^20, nothing below 2^19, +1.3 ms on a lone commit: opt-in);
+ * "fk20_cosets_combine" (0 = the shared-doubling Straus kernel, default; 1 = one mul256 per term: the same bytes, for comparison),
  * unknown keys -> KZG_ERR_SHAPE */
 int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value);
 /* "device=<d> lanes=<n> accum_streams=<m> hw_queues_found=<q> narrowed_from=<L>+<A>|none witness_cache_slots=<s>": the plan of the
@@ -377,6 +379,35 @@ int kzg_witness_all_coeff(kzg_ctx *ctx, const kzg_fk20 *plan, const void *coeffs
  * KZGProverEvalForm::create_witness(evals, m). */
 int kzg_witness_all_eval(kzg_ctx *ctx, const kzg_fk20 *plan, const void *evals, size_t d, size_t batch, int sfmt, int flags,
                          void *out, int ofmt);
+/* ---- all coset openings over the domain (FK20, multi-point case; not a reference method) -------------------------------
+ * The domain of N = 2^log_n points split into K = N / l cosets of l = 2^log_l points: C_i = { w^(i + tK) : t < l }, i < K, with
+ * vanishing polynomial X^l - w^(il).  One call computes, for every coset, what create_witness_batched(p, C_i, p(C_i))
+ * (src/coeff_form.rs:83-111, kzg_witness_coeff_batched) returns: w = [(p - I_i) / (X^l - w^(il))]_1 and r = I_i, in O(N log N)
+ * group operations instead of K MSMs.  Per polynomial: 2l Fr NTTs of sizes 2K and K, one l-term linear combination of G1
+ * points at each of 2K frequencies (2N scalar multiplications sharing one doubling chain per frequency), an inverse G1 DFT of
+ * size 2K and a forward one of size K.  The witness bytes equal kzg_witness_coeff_batched's in every format; r equals its l
+ * interpolant scalars (for n <= l: the witness is the identity and r is p zero-padded, as there).
+ * A kzg_fk20_cosets holds, for one monomial SRS, one domain and one coset size, the multiples 1..8 of DFT_2K of the l residue
+ * classes of the reversed SRS in affine form (8 x 2N rows of 128 B: 2.1 GB at 2^20) and the twiddle tables; it is immutable
+ * after creation and may be used from any thread and every kzg_ctx on its device.  Setup: KZG_ERR_DEGREE_TOO_LARGE if
+ * log_n + 1 reaches the two-adicity of Fr; KZG_ERR_SHAPE for log_n > 22 (Limits), log_l == 0 (single points: kzg_fk20_setup),
+ * log_l > log_n or an SRS on another GPU.  SRS points past len(srs) count as the identity, exact for every accepted polynomial. */
+typedef struct kzg_fk20_cosets kzg_fk20_cosets;
+int kzg_fk20_cosets_setup(kzg_ctx *ctx, const kzg_srs *monomial, uint32_t log_n, uint32_t log_l, kzg_fk20_cosets **out);
+void kzg_fk20_cosets_free(kzg_ctx *ctx, kzg_fk20_cosets *plan);
+/* *domain = N, *coset_size = l (either may be NULL); KZG_ERR_SHAPE for a NULL plan */
+int kzg_fk20_cosets_shape(const kzg_fk20_cosets *plan, size_t *domain, size_t *coset_size);
+/* `batch` polynomials of n coefficients each (stride n).  out_w: batch x K points in ofmt, witness i of polynomial b at index
+ * b K + i, opening C_i (cosets in natural order).  out_r (optional, NULL skips it): batch x K x l scalars in sfmt, coset i's
+ * interpolant coefficients r_0 .. r_{l-1} at (b K + i) l.  KZG_IN_DEVICE applies to the input, KZG_OUT_DEVICE to both outputs.
+ * KZG_ERR_SHAPE if n == 0, n > N, n > l with n - l > len(srs) (the reference's slice panic), an unknown format, a NULL pointer or
+ * a plan on another GPU; batch == 0 returns KZG_OK.  Takes the context exclusively; works in chunks of at most 2^21 / 2N
+ * polynomials, so the workspace does not grow with `batch`. */
+int kzg_witness_cosets_coeff(kzg_ctx *ctx, const kzg_fk20_cosets *plan, const void *coeffs, size_t n, size_t batch, int sfmt,
+                             int flags, void *out_w, int ofmt, void *out_r);
+/* `batch` evaluation vectors of length d == N (else KZG_ERR_SHAPE), natural domain order: iNTT in Fr, then the above */
+int kzg_witness_cosets_eval(kzg_ctx *ctx, const kzg_fk20_cosets *plan, const void *evals, size_t d, size_t batch, int sfmt,
+                            int flags, void *out_w, int ofmt, void *out_r);
 /* KZGVerifierEvalForm::verify_poly (:162-171): ifft then monomial MSM, compare. */
 int kzg_verify_poly_eval(kzg_ctx *ctx, const kzg_srs *monomial, const void *commitment, int pfmt,
                          const void *evals, size_t d, int sfmt, int flags, int *ok);

@@ -25,6 +25,11 @@ int kzg_test_g1_mul_glv(kzg_ctx *ctx, const void *p, const void *k_canonical, si
 /* one G1 DFT of 2^log_n points over compute_omega(2^log_n): out_m = sum_j w^(jm) P_j, or w^(-jm) with `inverse` (NOT scaled by
  * 1 / 2^log_n); affine Montgomery in and out, natural order */
 int kzg_test_g1_ntt(kzg_ctx *ctx, const void *pts, uint32_t log_n, int inverse, void *out);
+/* the coset combination of kzg_witness_cosets_* alone: out_j = sum_{r < l} k_{r,j} B_{r,j}, j < m.  bases: l x m affine Montgomery
+ * (B_{r,j} at r m + j), k_canonical: l x m scalars < r likewise, out: m affine Montgomery.  route 0 = Straus, 1 = mul256 per term;
+ * slices: the residue slices (a power of two <= l), 0 = the rule of the calls.  l a power of two, l x m <= 2^22 */
+int kzg_test_fk20_cosets_combine(kzg_ctx *ctx, const void *bases, const void *k_canonical, size_t l, size_t m, int route,
+                                 size_t slices, void *out);
 /* kzg_test_arith: the device twin of the arithmetic shims of tests/host_math.cpp (kzg_amd/csrc/arith_hooks.hip).  One thread per
  * record runs the same functions in the same order as the host shim, so on gfx950 it exercises the generated inline-asm branch
  * (mul_gfx950.inc, mul30_gfx950.inc, mul29r_gfx950.inc) where the host build runs the portable C.  Record `i` of the input is the

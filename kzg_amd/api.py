@@ -379,6 +379,71 @@ def _witness_all(engine, fn, plan, blob, n, batch, ofmt):
     return [[out.raw[(b * N + m) * psz:(b * N + m + 1) * psz] for m in range(N)] for b in range(batch)]
 
 
+class FK20CosetPlan:
+    """kzg_fk20_cosets: the per-domain tables of multi-point FK20 (every opening of a polynomial at every coset of 2^log_l points
+    of its size-2^log_n domain in one call) for one monomial SRS.  Coset i is {w^(i + tK) : t < l}, K = N / l.  Not a reference
+    type."""
+
+    def __init__(self, engine, srs, log_n, log_l):
+        self.engine = engine
+        h = ctypes.c_void_p()
+        rc = engine.lib.kzg_fk20_cosets_setup(engine.ctx, srs.handle, log_n, log_l, ctypes.byref(h))
+        if rc:
+            _raise(engine, rc)
+        self.handle = h
+        self._shape = None
+
+    def _dims(self):
+        if self._shape is None:
+            N, l = ctypes.c_size_t(), ctypes.c_size_t()
+            rc = self.engine.lib.kzg_fk20_cosets_shape(self.handle, ctypes.byref(N), ctypes.byref(l))
+            if rc:
+                _raise(self.engine, rc)
+            self._shape = (N.value, l.value)
+        return self._shape
+
+    def domain(self):
+        return self._dims()[0]
+
+    def coset_size(self):
+        return self._dims()[1]
+
+    def num_cosets(self):
+        N, l = self._dims()
+        return N // l
+
+    def coset_points(self, i):
+        """the l points of coset i, in the order t = 0 .. l-1: w^(i + tK)"""
+        N, l = self._dims()
+        K = N // l
+        w = compute_omega(N)[2]
+        return [pow(w, i + t * K, R_MODULUS) for t in range(l)]
+
+    def free(self):
+        if self.handle:
+            self.engine.lib.kzg_fk20_cosets_free(self.engine.ctx, self.handle)
+            self.handle = None
+
+
+def _witness_cosets(engine, fn, plan, blob, n, batch, ofmt):
+    N, l = plan.domain(), plan.coset_size()
+    K = N // l
+    psz = L.POINT_BYTES[ofmt]
+    out = ctypes.create_string_buffer(psz * K * max(batch, 1))
+    rbuf = ctypes.create_string_buffer(32 * N * max(batch, 1))
+    rc = fn(engine.ctx, plan.handle, blob, n, batch, L.FR_CANONICAL, 0, out, ofmt, rbuf)
+    if rc:
+        _raise(engine, rc)
+    res = []
+    for b in range(batch):
+        ws = []
+        for i in range(K):
+            r = unpack_scalars(rbuf.raw[((b * K + i) * l) * 32:((b * K + i + 1) * l) * 32])
+            ws.append(KZGBatchWitness(Polynomial.new_from_coeffs(r, l - 1), out.raw[(b * K + i) * psz:(b * K + i + 1) * psz]))
+        res.append(ws)
+    return res
+
+
 class SrsG2:
     """Resident G2 points (kzg_srs_g2): the `hs` half of KZGParams or a G2 Lagrange basis."""
 
@@ -904,6 +969,17 @@ class KZGProver:
         blob = b"".join(pack_scalars(p.slice_coeffs() + [0] * (n - p.num_coeffs())) for p in polynomials)
         return _witness_all(self.engine, self.engine.lib.kzg_witness_all_coeff, plan, blob, n, len(polynomials), ofmt)
 
+    def create_witness_all_cosets(self, polynomial, plan, ofmt=L.G1_AFFINE_MONT):
+        """Every coset opening over the plan's domain (multi-point FK20; not a reference method): element i is
+        create_witness_batched(polynomial, plan.coset_points(i), their values), as a KZGBatchWitness."""
+        return self.create_witness_all_cosets_batch([polynomial], plan, ofmt)[0]
+
+    def create_witness_all_cosets_batch(self, polynomials, plan, ofmt=L.G1_AFFINE_MONT):
+        """create_witness_all_cosets for several polynomials (zero-padded to the longest): one list of K witnesses each."""
+        n = max(p.num_coeffs() for p in polynomials)
+        blob = b"".join(pack_scalars(p.slice_coeffs() + [0] * (n - p.num_coeffs())) for p in polynomials)
+        return _witness_cosets(self.engine, self.engine.lib.kzg_witness_cosets_coeff, plan, blob, n, len(polynomials), ofmt)
+
     def create_witness_batched(self, polynomial, xs, ys, ofmt=L.G1_AFFINE_MONT):  # :83-111
         e = self.engine
         assert len(xs) == len(ys)
@@ -1030,6 +1106,13 @@ class KZGProverEvalForm:
             raise ReferencePanic("assert!(self.d == evals.d): evaluation vectors of different lengths")
         blob = b"".join(pack_scalars(ev.coeffs) for ev in evals_list)
         return _witness_all(self.engine, self.engine.lib.kzg_witness_all_eval, plan, blob, d, len(evals_list), ofmt)
+
+    def create_witness_all_cosets(self, evals, plan, ofmt=L.G1_AFFINE_MONT):
+        """Every coset opening over the domain (multi-point FK20 against `plan`, built from the monomial SRS; not a reference
+        method): element i opens plan.coset_points(i), as a KZGBatchWitness."""
+        d = len(evals)
+        blob = pack_scalars(evals.coeffs)
+        return _witness_cosets(self.engine, self.engine.lib.kzg_witness_cosets_eval, plan, blob, d, 1, ofmt)[0]
 
     def create_witness_all(self):  # :142-146: identity
         return bytes(96)

@@ -391,6 +391,401 @@ extern "C" int kzg_witness_all_eval(kzg_ctx *ctx, const kzg_fk20 *plan, const vo
     return fk20_run(ctx, plan, evals, d, batch, sfmt, flags, out, ofmt, true);
 }
 
+// ---- multi-point FK20: every coset opening ------------------------------------------------------------------------------
+// Coset size l = 2^j, K = N / l cosets, C_i = { w^(i + tK) : t < l }, Z_i = X^l - w^(il) (w^l = w_K).  With the residue split
+// c^(r)_t = c_{r + tl}, s^(r)_v = s_{r + vl} (r < l), the witness of coset i is pi_i = DFT_K(h)_i with h = sum_r h^(r) and
+// h^(r)_u = sum_{v <= K-2-u} c^(r)_{u+1+v} s^(r)_v: the single-point layout above with N -> K, once per residue, the l products
+// summed in the frequency domain before the one inverse transform:
+//     x^(r)_j = s_{r + (K-2-j) l} (j <= K-2), O otherwise      (per plan: Xh^(r) = DFT_2K(x^(r)), bit-reversed, l arrays)
+//     y^(r) = (c^(r)_{K-1}, 0 x K, c^(r)_0 .. c^(r)_{K-2})       (per polynomial: yh^(r) = DFT_2K(y^(r)) / 2K, bit-reversed)
+//     hh_j = sum_r yh^(r)_j Xh^(r)_j,   h = iDFT_2K(hh) first half (DIT),   pi = DFT_K(h) (DIF), read out bit-reversed.
+// The interpolant I_i = p mod Z_i has coefficient r = sum_t c^(r)_t w_K^(it) = DFT_K(c^(r))_i: Fr only.  SRS points past len(srs)
+// count as the identity, exact whenever n <= l or n - l <= len(srs) (q_i has n - l coefficients).
+//
+// The combination (2N scalar multiplications per polynomial) is the hot kernel.  The bases are fixed per plan, so the plan keeps
+// their multiples 1..8 in affine 30-bit form (G1Affine30, one 128-byte row each), and one thread runs ONE doubling chain per
+// frequency over the signed 4-bit digits of all its terms (Straus): 256 doublings for the whole sum plus ~60 mixed additions per
+// term.  The per-term route (option "fk20_cosets_combine" = 1) runs mul256 on every term -- 256 doublings, the table build and
+// ~60 additions each -- and is kept for comparison.  Both split the residues into S slices whose partial sums k_coset_reduce adds.
+namespace kzg {
+
+constexpr size_t COSET_TARGET_THREADS = (size_t)1 << 17;  // combination threads per chunk the slicing aims for
+
+// X[r][j] = x^(r)_j = s_{r + (K-2-j) l} (j <= K-2 and inside the SRS), O otherwise; r < l, j < 2K
+__global__ __launch_bounds__(256) void k_coset_load_x(const G1Affine *srs, size_t srs_n, size_t K, size_t l, MsmPoint *X) {
+    const size_t two = 2 * K, u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= l * two) return;
+    const size_t r = u / two, j = u % two;
+    const bool in = j + 2 <= K && r + (K - 2 - j) * l < srs_n;
+    X[u] = in ? g1_from_affine30(g1_affine_to30(srs[r + (K - 2 - j) * l]), false) : MsmPoint::infinity();
+}
+
+// tab[e * count + u] = (e + 1) X[u] in affine 30-bit form, e < 8 (the identity: all limbs zero)
+__global__ __launch_bounds__(256) void k_coset_table(const MsmPoint *X, size_t count, G1Affine30 *tab) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < count; u += nt) {
+        const MsmPoint P = X[u];
+        MsmPoint Q = P;
+#pragma nounroll
+        for (int e = 0; e < G1NTT_TAB; e++) {
+            if (e == 1) Q = g1_dbl30(P);
+            else if (e > 1) Q = g1_add30(Q, P);  // (e + 1) P != e P: the group has prime order
+            tab[(size_t)e * count + u] = g1_affine_to30(g1_to_affine(g1_xyzz_from30(Q)));
+        }
+    }
+}
+
+// y[(b l + r) 2K + t] = y^(r)_t of polynomial b, from n coefficients per polynomial (stride n) in sfmt; Montgomery out
+__global__ __launch_bounds__(256) void k_coset_build_y(const Fr *c, size_t n, size_t K, size_t l, size_t batch, int sfmt, Fr *y) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    const size_t two = 2 * K, work = batch * l * two;
+    for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < work; u += nt) {
+        const size_t a = u / two, t = u % two, b = a / l, r = a % l;
+        const bool has = t == 0 || t > K;
+        const size_t ci = r + (t == 0 ? K - 1 : t - K - 1) * l;
+        Fr v = Fr::zero();
+        if (has && ci < n) {
+            v = c[b * n + ci];
+            if (sfmt == KZG_FR_CANONICAL_LE_32) v = to_mont(v);
+        }
+        y[u] = v;
+    }
+}
+
+// z[(b l + r) K + t] = c^(r)_t of polynomial b (Montgomery), the input of the interpolants' NTTs
+__global__ __launch_bounds__(256) void k_coset_gather_r(const Fr *c, size_t n, size_t K, size_t l, size_t batch, int sfmt, Fr *z) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    const size_t work = batch * l * K;
+    for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < work; u += nt) {
+        const size_t a = u / K, t = u % K, b = a / l, r = a % l;
+        const size_t ci = r + t * l;
+        Fr v = Fr::zero();
+        if (ci < n) {
+            v = c[b * n + ci];
+            if (sfmt == KZG_FR_CANONICAL_LE_32) v = to_mont(v);
+        }
+        z[u] = v;
+    }
+}
+
+// out[(b K + i) l + r] = DFT_K(c^(r))_i of polynomial b, in sfmt: coset i's interpolant coefficients r_0 .. r_{l-1}
+__global__ __launch_bounds__(256) void k_coset_emit_r(const Fr *z, size_t K, size_t l, size_t batch, int sfmt, Fr *out) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    const size_t work = batch * K * l;
+    for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < work; u += nt) {
+        const size_t r = u % l, i = (u / l) % K, b = u / (l * K);
+        const Fr v = z[(b * l + r) * K + i];
+        out[u] = sfmt == KZG_FR_CANONICAL_LE_32 ? from_mont(v) : v;
+    }
+}
+
+// canonical scalars (arrays of `two`) -> k + 0x88..8 (< 2^256: 64 signed digits, no carry out), word q of array a at
+// rec[(a 8 + q) two + j] so that a wave's reads of one digit are coalesced
+__global__ __launch_bounds__(256) void k_coset_recode(const Fr *k, size_t arrays, size_t two, uint32_t *rec) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    const size_t work = arrays * two;
+    for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < work; u += nt) {
+        const size_t a = u / two, j = u % two;
+        uint32_t v[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) v[q] = k[u].v[q];
+        recode_add(v, 8);
+#pragma unroll
+        for (int q = 0; q < 8; q++) rec[(a * 8 + q) * two + j] = v[q];
+    }
+}
+
+// Straus: P[(b S + s) two + j] = sum over the l / S residues r of slice s of [k_{b,r,j}] T_{r,j}.  tab: the multiples 1..8 of T_{r,j}
+// at tab[(e l + r) two + j]; rec: the recoded scalars of the (b, r) arrays (k_coset_recode).  One doubling chain per thread.
+__global__ __launch_bounds__(256) void k_coset_straus(const G1Affine30 *tab, size_t l, size_t two, const uint32_t *rec, size_t batch,
+                                                      size_t S, MsmPoint *P) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    const size_t work = batch * S * two, rs = l / S;
+    for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < work; u += nt) {
+        const size_t j = u % two, s = (u / two) % S, b = u / (two * S);
+        const uint32_t *rw = rec + (b * l + s * rs) * 8 * two + j;
+        const G1Affine30 *tb = tab + s * rs * two + j;
+        MsmPoint acc = MsmPoint::infinity();
+#pragma nounroll
+        for (int nib = 63; nib >= 0; nib--) {
+#pragma nounroll
+            for (int i = 0; i < 4; i++) acc = g1_dbl30(acc);
+            const int q = nib >> 3, sh = 4 * (nib & 7);
+#pragma nounroll
+            for (size_t rr = 0; rr < rs; rr++) {
+                const int d = (int)((rw[(rr * 8 + q) * two] >> sh) & 15u) - 8;
+                if (d) acc = g1_madd30(acc, tb[((size_t)((d < 0 ? -d : d) - 1) * l + rr) * two], d < 0);
+            }
+        }
+        P[u] = acc;
+    }
+}
+
+// per-term route, same contract: mul256 on every term (the multiple 1 of the table is the base itself)
+__global__ __launch_bounds__(256) void k_coset_perterm(const G1Affine30 *tab, size_t l, size_t two, const uint32_t *rec, size_t batch,
+                                                       size_t S, MsmPoint *P, MsmPoint *scratch, Fq30 beta) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t work = batch * S * two, rs = l / S;
+    for (size_t u = tid; u < work; u += nt) {
+        const size_t j = u % two, s = (u / two) % S, b = u / (two * S);
+        MsmPoint acc = MsmPoint::infinity();
+#pragma nounroll
+        for (size_t rr = 0; rr < rs; rr++) {
+            const size_t r = s * rs + rr;
+            Fr k;  // undo the recoding: k = rec - 0x88..8
+            uint64_t br = 0;
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const uint64_t d = (uint64_t)rec[((b * l + r) * 8 + q) * two + j] - 0x88888888u - br;
+                k.v[q] = (uint32_t)d;
+                br = (d >> 32) & 1u;
+            }
+            acc = g1_add30(acc, mul256(g1_from_affine30(tab[r * two + j], false), k, scratch + tid, nt, beta));
+        }
+        P[u] = acc;
+    }
+}
+
+// P[b S two + j] = sum_s P[(b S + s) two + j]
+__global__ __launch_bounds__(256) void k_coset_reduce(MsmPoint *P, size_t two, size_t S, size_t batch) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x;
+    for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < batch * two; u += nt) {
+        MsmPoint *base = P + (u / two) * S * two + u % two;
+        MsmPoint acc = base[0];
+        for (size_t s = 1; s < S; s++) acc = g1_add30(acc, base[s * two]);
+        base[0] = acc;
+    }
+}
+
+// residue slices of a combination over `batch` x two frequencies: enough threads to fill the chip, at most l
+static size_t coset_slices(size_t l, size_t two, size_t batch) {
+    size_t S = 1;
+    while (S < l && batch * S * two < COSET_TARGET_THREADS) S *= 2;
+    return S;
+}
+
+// the combination and its slice reduction; route 0 Straus, 1 per-term (scratch: scratch_points(batch * S * two) points)
+static int coset_combine(kzg_ctx *ctx, hipStream_t st, int route, const G1Affine30 *tab, size_t l, size_t two, const uint32_t *rec,
+                         size_t batch, size_t S, MsmPoint *P, MsmPoint *scratch, const Fq30 &beta) {
+    const unsigned g = grid_for(batch * S * two, 256);
+    if (route == 1)
+        KZG_LAUNCH(ctx, st, "k_coset_perterm", k_coset_perterm, g, 256, 0, tab, l, two, rec, batch, S, P, scratch, beta);
+    else
+        KZG_LAUNCH(ctx, st, "k_coset_straus", k_coset_straus, g, 256, 0, tab, l, two, rec, batch, S, P);
+    if (S > 1) KZG_LAUNCH(ctx, st, "k_coset_reduce", k_coset_reduce, grid_for(batch * two, 256), 256, 0, P, two, S, batch);
+    return KZG_OK;
+}
+
+}  // namespace kzg
+
+struct kzg_fk20_cosets {
+    int device = 0;
+    uint32_t log_n = 0, log_l = 0;
+    size_t N = 0, l = 0, K = 0;
+    size_t srs_n = 0;               // length of the monomial SRS the plan was built from
+    G1Affine30 *tab = nullptr;      // (e + 1) Xh^(r)_j at tab[(e l + r) 2K + j], e < 8: 8 x 2N rows of 128 B
+    GlvTw *tw_fwd = nullptr;        // w_2K^e, e < K
+    GlvTw *tw_inv = nullptr;        // w_2K^-e, e < K
+    Fr inv2k;                       // 1 / 2K, Montgomery
+    Fq30 beta;
+};
+
+static void cosets_release(kzg_fk20_cosets *p) {
+    if (!p) return;
+    if (p->tab) hipFree(p->tab);
+    if (p->tw_fwd) hipFree(p->tw_fwd);
+    if (p->tw_inv) hipFree(p->tw_inv);
+    delete p;
+}
+
+extern "C" int kzg_fk20_cosets_setup(kzg_ctx *ctx, const kzg_srs *monomial, uint32_t log_n, uint32_t log_l, kzg_fk20_cosets **out) {
+    if (!ctx || !monomial || !out) return KZG_ERR_SHAPE;
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (monomial->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "SRS resident on another GPU");
+    if (log_n + 1 >= FR_TWO_ADICITY) return fail(ctx, KZG_ERR_DEGREE_TOO_LARGE, "domain too large");
+    if (log_n > FK20_MAX_LOG) return fail(ctx, KZG_ERR_SHAPE, "kzg_fk20_cosets_setup: log_n <= 22 (documented limit)");
+    if (log_l == 0) return fail(ctx, KZG_ERR_SHAPE, "kzg_fk20_cosets_setup: log_l >= 1 (single points: kzg_fk20_setup)");
+    if (log_l > log_n) return fail(ctx, KZG_ERR_SHAPE, "kzg_fk20_cosets_setup: coset larger than the domain");
+    kzg_fk20_cosets *p = new kzg_fk20_cosets();
+    p->device = ctx->device;
+    p->log_n = log_n;
+    p->log_l = log_l;
+    p->N = (size_t)1 << log_n;
+    p->l = (size_t)1 << log_l;
+    p->K = p->N >> log_l;
+    p->srs_n = monomial->n;
+    p->beta = beta30();
+    const size_t K = p->K, two = 2 * K, rows = 2 * p->N;  // l arrays of 2K
+    const uint32_t logk = log_n - log_l;
+    const Fr w = host_omega(logk + 1);  // w_2K, w_2K^2 = w_K = w_N^l
+    p->inv2k = inv(from_u64<FrParams>((uint64_t)two));
+    hipStream_t st = ctx->lanes[0].stream;
+    int rc = KZG_OK;
+    Fr *pw = nullptr;
+    MsmPoint *X = nullptr, *scratch = nullptr;
+    const size_t scr = scratch_points(p->l * K);
+    if (hipMalloc((void **)&p->tab, G1NTT_TAB * rows * sizeof(G1Affine30)) != hipSuccess ||
+        hipMalloc((void **)&p->tw_fwd, K * sizeof(GlvTw)) != hipSuccess || hipMalloc((void **)&p->tw_inv, K * sizeof(GlvTw)) != hipSuccess ||
+        hipMalloc((void **)&pw, K * sizeof(Fr)) != hipSuccess || hipMalloc((void **)&X, rows * sizeof(MsmPoint)) != hipSuccess ||
+        hipMalloc((void **)&scratch, scr * sizeof(MsmPoint)) != hipSuccess)
+        rc = fail(ctx, KZG_ERR_ALLOC, "hipMalloc(FK20 coset plan)");
+    if (rc == KZG_OK) rc = glv_table(ctx, st, w, K, pw, p->tw_fwd);
+    if (rc == KZG_OK) rc = glv_table(ctx, st, inv(w), K, pw, p->tw_inv);
+    if (rc == KZG_OK) {
+        KZG_LAUNCH(ctx, st, "k_coset_load_x", k_coset_load_x, (unsigned)((rows + 255) / 256), 256, 0, monomial->table, monomial->n, K,
+                   p->l, X);
+        rc = g1_dft(ctx, st, X, two, logk + 1, p->l, p->tw_fwd, 1, true, false, scratch, p->beta);
+    }
+    if (rc == KZG_OK) KZG_LAUNCH(ctx, st, "k_coset_table", k_coset_table, grid_for(rows, 256), 256, 0, (const MsmPoint *)X, rows, p->tab);
+    if (hipStreamSynchronize(st) != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "FK20 coset plan kernels failed");
+    if (hipGetLastError() != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "FK20 coset plan kernels failed");
+    if (pw) hipFree(pw);
+    if (X) hipFree(X);
+    if (scratch) hipFree(scratch);
+    if (ctx->prof) prof_collect(ctx);
+    if (rc != KZG_OK) {
+        cosets_release(p);
+        return rc;
+    }
+    *out = p;
+    return KZG_OK;
+}
+
+extern "C" void kzg_fk20_cosets_free(kzg_ctx *ctx, kzg_fk20_cosets *plan) {
+    if (!plan) return;
+    if (ctx) {
+        Guard g(ctx);
+        hipSetDevice(plan->device);
+        hipDeviceSynchronize();
+        cosets_release(plan);
+        return;
+    }
+    hipSetDevice(plan->device);
+    hipDeviceSynchronize();
+    cosets_release(plan);
+}
+
+extern "C" int kzg_fk20_cosets_shape(const kzg_fk20_cosets *plan, size_t *domain, size_t *coset_size) {
+    if (!plan) return KZG_ERR_SHAPE;
+    if (domain) *domain = plan->N;
+    if (coset_size) *coset_size = plan->l;
+    return KZG_OK;
+}
+
+namespace kzg {
+
+// every coset witness (and optionally every interpolant) of `batch` polynomials of n coefficients (eval: N evaluations), in chunks
+static int cosets_run(kzg_ctx *ctx, const kzg_fk20_cosets *p, const void *in, size_t n, size_t batch, int sfmt, int flags, void *out_w,
+                      int ofmt, void *out_r, bool eval) {
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (sfmt != KZG_FR_MONT_LE_32 && sfmt != KZG_FR_CANONICAL_LE_32) return fail(ctx, KZG_ERR_SHAPE, "unknown scalar format");
+    const size_t psz = point_format_bytes(ofmt);
+    if (!psz) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 output format");
+    if (p->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "FK20 coset plan resident on another GPU");
+    const size_t N = p->N, l = p->l, K = p->K, two = 2 * K;
+    if (eval && n != N) return fail(ctx, KZG_ERR_SHAPE, "assert!(self.d == evals.d): evaluations must cover the plan's domain");
+    if (n == 0) return fail(ctx, KZG_ERR_SHAPE, "empty polynomial");
+    if (n > N) return fail(ctx, KZG_ERR_SHAPE, "polynomial longer than the plan's domain");
+    if (n > l && n - l > p->srs_n) return fail(ctx, KZG_ERR_SHAPE, "quotient longer than the SRS (reference: slice index panic)");
+    if (batch == 0) return KZG_OK;
+    if (batch > SIZE_MAX / (N * 144)) return fail(ctx, KZG_ERR_SHAPE, "batch too large");
+    if (!in || !out_w) return KZG_ERR_SHAPE;
+    const int lane = 0;
+    hipStream_t st = ctx->lanes[lane].stream;
+    const bool out_dev = (flags & KZG_OUT_DEVICE) != 0, in_dev = (flags & KZG_IN_DEVICE) != 0, want_r = out_r != nullptr;
+    const uint8_t *src = (const uint8_t *)in;
+    const uint32_t logn = p->log_n, logk = logn - p->log_l;
+    const size_t chunk = std::max<size_t>(1, std::min(FK20_MAX_CHUNK, FK20_CHUNK_POINTS / (2 * N)));
+    const size_t B0 = std::min(chunk, batch);
+    const size_t S = coset_slices(l, two, B0);
+    const int route = ctx->opt_fk20_cosets_combine;
+    const size_t in_bytes = B0 * n * 32;
+    const size_t scr = scratch_points(B0 * S * two);
+    size_t need = align_up(B0 * S * two * sizeof(MsmPoint), 256) + 2 * align_up(B0 * 2 * N * 32, 256) + align_up(scr * sizeof(MsmPoint), 256) +
+                  (want_r ? align_up(B0 * N * 32, 256) : 0) + (in_dev ? 0 : align_up(in_bytes, 256)) +
+                  (out_dev ? 0 : align_up(B0 * K * psz, 256) + (want_r ? align_up(B0 * N * 32, 256) : 0)) +
+                  ntt_workspace_bytes(std::max(logk + 1, logn)) + 65536;
+    KZG_TRY(lane_reserve(ctx, lane, need));
+    MsmPoint *P = (MsmPoint *)lane_alloc(ctx, lane, B0 * S * two * sizeof(MsmPoint));
+    Fr *y = (Fr *)lane_alloc(ctx, lane, B0 * 2 * N * 32);
+    Fr *yh = (Fr *)lane_alloc(ctx, lane, B0 * 2 * N * 32);
+    MsmPoint *scratch = (MsmPoint *)lane_alloc(ctx, lane, scr * sizeof(MsmPoint));
+    Fr *z = want_r ? (Fr *)lane_alloc(ctx, lane, B0 * N * 32) : nullptr;
+    uint8_t *d_in = in_dev ? nullptr : (uint8_t *)lane_alloc(ctx, lane, in_bytes);
+    uint8_t *d_stage = out_dev ? nullptr : (uint8_t *)lane_alloc(ctx, lane, B0 * K * psz);
+    uint8_t *d_stage_r = (out_dev || !want_r) ? nullptr : (uint8_t *)lane_alloc(ctx, lane, B0 * N * 32);
+    if (!P || !y || !yh || !scratch || (want_r && !z) || (!in_dev && !d_in) || (!out_dev && !d_stage) || (!out_dev && want_r && !d_stage_r))
+        return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    const size_t ntt_mark = ctx->lanes[lane].arena_used;  // every ntt_run below takes its scratch from here (stream-ordered reuse)
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t B = std::min(chunk, batch - b0);
+        const uint8_t *d_src = src + b0 * n * 32;
+        if (!in_dev) {
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_in, d_src, B * n * 32, hipMemcpyHostToDevice, st));
+            d_src = d_in;
+        }
+        const Fr *coeffs = (const Fr *)d_src;
+        int csfmt = sfmt;
+        if (eval) {  // iNTT_N of each evaluation vector (Montgomery) into yh, which the coefficients' only readers precede
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(yh, d_src, B * N * 32, hipMemcpyDeviceToDevice, st));
+            if (sfmt == KZG_FR_CANONICAL_LE_32) KZG_TRY(fr_convert(ctx, st, yh, B * N, 1));
+            for (size_t b = 0; b < B; b++) {
+                ctx->lanes[lane].arena_used = ntt_mark;
+                KZG_TRY(ntt_run(ctx, lane, yh + b * N, logn, 1));
+            }
+            coeffs = yh;
+            csfmt = KZG_FR_MONT_LE_32;
+        }
+        const unsigned gw = (unsigned)std::min<size_t>((B * 2 * N + 255) / 256, 8192);
+        if (want_r) {  // interpolants: DFT_K of every residue class, then transposed into coset-major order
+            KZG_LAUNCH(ctx, st, "k_coset_gather_r", k_coset_gather_r, gw, 256, 0, coeffs, n, K, l, B, csfmt, z);
+            if (logk)
+                for (size_t a = 0; a < B * l; a++) {
+                    ctx->lanes[lane].arena_used = ntt_mark;
+                    KZG_TRY(ntt_run(ctx, lane, z + a * K, logk, 0));
+                }
+            Fr *d_r = out_dev ? (Fr *)((uint8_t *)out_r + b0 * N * 32) : (Fr *)d_stage_r;
+            KZG_LAUNCH(ctx, st, "k_coset_emit_r", k_coset_emit_r, gw, 256, 0, (const Fr *)z, K, l, B, sfmt, d_r);
+            if (!out_dev)
+                KZG_HIP_CHECK(ctx, hipMemcpyAsync((uint8_t *)out_r + b0 * N * 32, d_stage_r, B * N * 32, hipMemcpyDeviceToHost, st));
+        }
+        KZG_LAUNCH(ctx, st, "k_coset_build_y", k_coset_build_y, gw, 256, 0, coeffs, n, K, l, B, csfmt, y);
+        for (size_t a = 0; a < B * l; a++) {
+            ctx->lanes[lane].arena_used = ntt_mark;
+            KZG_TRY(ntt_run(ctx, lane, y + a * two, logk + 1, 0));
+        }
+        KZG_LAUNCH(ctx, st, "k_fk20_scale_brev", k_fk20_scale_brev, gw, 256, 0, y, logk + 1, p->inv2k, B * l, yh);
+        KZG_LAUNCH(ctx, st, "k_coset_recode", k_coset_recode, gw, 256, 0, (const Fr *)yh, B * l, two, (uint32_t *)y);
+        KZG_TRY(coset_combine(ctx, st, route, p->tab, l, two, (const uint32_t *)y, B, S, P, scratch, p->beta));
+        KZG_TRY(g1_dft(ctx, st, P, S * two, logk + 1, B, p->tw_inv, 1, false, true, scratch, p->beta));  // h = iDFT_2K, first half
+        KZG_TRY(g1_dft(ctx, st, P, S * two, logk, B, p->tw_fwd, 2, true, false, scratch, p->beta));      // pi = DFT_K(h), bit-reversed
+        uint8_t *d_out = out_dev ? (uint8_t *)out_w + b0 * K * psz : d_stage;
+        KZG_LAUNCH(ctx, st, "k_fk20_emit", k_fk20_emit, (unsigned)std::min<size_t>((B * K + 63) / 64, 16384), 64, 0, (const MsmPoint *)P,
+                   S * two, logk, B, d_out, ofmt, psz);
+        if (!out_dev) KZG_HIP_CHECK(ctx, hipMemcpyAsync((uint8_t *)out_w + b0 * K * psz, d_stage, B * K * psz, hipMemcpyDeviceToHost, st));
+    }
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    KZG_HIP_CHECK(ctx, hipGetLastError());
+    if (ctx->prof) prof_collect(ctx);
+    return KZG_OK;
+}
+
+}  // namespace kzg
+
+extern "C" int kzg_witness_cosets_coeff(kzg_ctx *ctx, const kzg_fk20_cosets *plan, const void *coeffs, size_t n, size_t batch, int sfmt,
+                                        int flags, void *out_w, int ofmt, void *out_r) {
+    if (!ctx || !plan) return KZG_ERR_SHAPE;
+    return cosets_run(ctx, plan, coeffs, n, batch, sfmt, flags, out_w, ofmt, out_r, false);
+}
+
+extern "C" int kzg_witness_cosets_eval(kzg_ctx *ctx, const kzg_fk20_cosets *plan, const void *evals, size_t d, size_t batch, int sfmt,
+                                       int flags, void *out_w, int ofmt, void *out_r) {
+    if (!ctx || !plan) return KZG_ERR_SHAPE;
+    return cosets_run(ctx, plan, evals, d, batch, sfmt, flags, out_w, ofmt, out_r, true);
+}
+
 #ifdef KZG_TEST_HOOKS
 #include "../../include/kzg_mi355x_test.h"
 
@@ -462,6 +857,42 @@ extern "C" int kzg_test_g1_ntt(kzg_ctx *ctx, const void *pts, uint32_t log_n, in
                    (uint8_t *)dout, (int)KZG_G1_AFFINE_MONT_96, (size_t)96);
     }
     KZG_HIP_CHECK(ctx, hipMemcpyAsync(out, dout, d * 96, hipMemcpyDeviceToHost, st));
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    KZG_HIP_CHECK(ctx, hipGetLastError());
+    return KZG_OK;
+}
+
+// out_j = sum_r k_{r,j} B_{r,j}: the coset combination alone (tables, recoding, route, slices, reduction) on caller-given points
+extern "C" int kzg_test_fk20_cosets_combine(kzg_ctx *ctx, const void *bases, const void *k_canonical, size_t l, size_t m, int route,
+                                            size_t slices, void *out) {
+    if (!ctx || !bases || !k_canonical || !out || !l || !m || (l & (l - 1)) || (route != 0 && route != 1)) return KZG_ERR_SHAPE;
+    if (slices && (slices > l || (slices & (slices - 1)))) return KZG_ERR_SHAPE;
+    if (l * m > ((size_t)1 << 22)) return KZG_ERR_SHAPE;
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const size_t cnt = l * m, S = slices ? slices : coset_slices(l, m, 1);
+    const size_t scr = scratch_points(S * m);
+    KZG_TRY(lane_reserve(ctx, 0, cnt * (96 + 32 + 32 + sizeof(MsmPoint) + G1NTT_TAB * sizeof(G1Affine30)) + S * m * sizeof(MsmPoint) +
+                                     m * 96 + scr * sizeof(MsmPoint) + 65536));
+    hipStream_t st = ctx->lanes[0].stream;
+    void *db = lane_alloc(ctx, 0, cnt * 96), *dout = lane_alloc(ctx, 0, m * 96);
+    Fr *dk = (Fr *)lane_alloc(ctx, 0, cnt * 32);
+    uint32_t *rec = (uint32_t *)lane_alloc(ctx, 0, cnt * 32);
+    MsmPoint *X = (MsmPoint *)lane_alloc(ctx, 0, cnt * sizeof(MsmPoint));
+    G1Affine30 *tab = (G1Affine30 *)lane_alloc(ctx, 0, G1NTT_TAB * cnt * sizeof(G1Affine30));
+    MsmPoint *P = (MsmPoint *)lane_alloc(ctx, 0, S * m * sizeof(MsmPoint));
+    MsmPoint *scratch = (MsmPoint *)lane_alloc(ctx, 0, scr * sizeof(MsmPoint));
+    if (!db || !dout || !dk || !rec || !X || !tab || !P || !scratch) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(db, bases, cnt * 96, hipMemcpyHostToDevice, st));
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(dk, k_canonical, cnt * 32, hipMemcpyHostToDevice, st));
+    KZG_LAUNCH(ctx, st, "k_test_g1ntt_load", k_test_g1ntt_load, (unsigned)((cnt + 255) / 256), 256, 0, (const G1Affine *)db, cnt, 0u, 0,
+               X);
+    KZG_LAUNCH(ctx, st, "k_coset_table", k_coset_table, grid_for(cnt, 256), 256, 0, (const MsmPoint *)X, cnt, tab);
+    KZG_LAUNCH(ctx, st, "k_coset_recode", k_coset_recode, grid_for(cnt, 256), 256, 0, (const Fr *)dk, l, m, rec);
+    KZG_TRY(coset_combine(ctx, st, route, tab, l, m, rec, 1, S, P, scratch, beta30()));
+    KZG_LAUNCH(ctx, st, "k_fk20_emit", k_fk20_emit, (unsigned)((m + 63) / 64), 64, 0, (const MsmPoint *)P, (size_t)1, 0u, m,
+               (uint8_t *)dout, (int)KZG_G1_AFFINE_MONT_96, (size_t)96);
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(out, dout, m * 96, hipMemcpyDeviceToHost, st));
     KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
     KZG_HIP_CHECK(ctx, hipGetLastError());
     return KZG_OK;
