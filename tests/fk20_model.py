@@ -56,6 +56,20 @@ def fk20_model(coeffs, N, tau, srs_len=None):
     return dft(H, M.compute_omega(N)[2])                            # DIF + bit-reversed read-out = natural order
 
 
+def chunk_size(N):
+    """Polynomials per chunk of fk20_run and cosets_run in g1ntt.hip: max(1, min(FK20_MAX_CHUNK, FK20_CHUNK_POINTS / 2N))."""
+    return max(1, min(4096, (1 << 21) // (2 * N)))
+
+
+def coset_slices(l, two, batch):
+    """Residue slices of a coset combination over `batch` x two frequencies (g1ntt.hip coset_slices, COSET_TARGET_THREADS
+    = 2^17).  cosets_run takes S from its first chunk and keeps it for the ragged last one."""
+    S = 1
+    while S < l and batch * S * two < (1 << 17):
+        S *= 2
+    return S
+
+
 def direct_witnesses(coeffs, N, tau):
     """q_m(tau) = (p(tau) - p(w^m)) / (tau - w^m) by synthetic division at every w^m."""
     w = M.compute_omega(N)[2]

@@ -1,5 +1,7 @@
 """CPU checks of the FK20 layout (tests/fk20_model.py) and of the GLV constants of kzg_amd/csrc/g1ntt.hip."""
+import os
 import random
+import re
 
 import pytest
 
@@ -24,6 +26,24 @@ def test_short_srs_is_exact(N):
     for n in range(1, N + 1):
         coeffs = [rng.randrange(M.R) for _ in range(n)]
         assert F.fk20_model(coeffs, N, tau, srs_len=n - 1) == F.direct_witnesses(coeffs, N, tau), (N, n)
+
+
+def test_chunk_rules_match_the_source():
+    # the GPU chunk tests pick their shapes (a second chunk, a ragged last one, several residue slices) with F.chunk_size and
+    # F.coset_slices; if g1ntt.hip changes either rule, this fails instead of those tests quietly covering less
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "kzg_amd", "csrc", "g1ntt.hip")) as f:
+        src = f.read()
+    const = dict(re.findall(r"constexpr \w+ (\w+) = ([^;]+);", src))
+    assert (const["FK20_CHUNK_POINTS"], const["FK20_MAX_CHUNK"]) == ("(size_t)1 << 21", "4096")
+    assert const["COSET_TARGET_THREADS"] == "(size_t)1 << 17"
+    assert "chunk = std::max<size_t>(1, std::min(FK20_MAX_CHUNK, FK20_CHUNK_POINTS / two));" in src             # fk20_run
+    assert "chunk = std::max<size_t>(1, std::min(FK20_MAX_CHUNK, FK20_CHUNK_POINTS / (2 * N)));" in src         # cosets_run
+    assert "while (S < l && batch * S * two < COSET_TARGET_THREADS) S *= 2;" in src
+    assert "const size_t S = coset_slices(l, two, B0);" in src
+    assert [F.chunk_size(1 << k) for k in (0, 6, 12, 14, 16, 20, 22)] == [4096, 4096, 256, 64, 16, 1, 1]
+    assert [F.coset_slices(64, 512, b) for b in (64, 2, 1)] == [4, 64, 64]
+    assert F.coset_slices(64, 2 << 14, 1) == 4    # 2^20 / l = 64
 
 
 def test_glv_constants():

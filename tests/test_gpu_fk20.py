@@ -4,6 +4,7 @@ module-scoped Engine and HooksEngine instead of the session fixtures."""
 import ctypes
 import random
 import threading
+from types import SimpleNamespace
 
 import pytest
 
@@ -21,6 +22,8 @@ TAU = 0x5EED_F20
 SRS_LEN = 1 << 12
 VP, SZ, I32, U32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32
 FORMATS = [L.G1_AFFINE_MONT, L.G1_JACOBIAN_MONT, L.G1_ZCASH_UNCOMPRESSED, L.G1_ZCASH_COMPRESSED]
+MONT_R = pow(2, 256, M.R)
+SIZE_MAX = ctypes.c_size_t(-1).value
 
 
 @pytest.fixture(scope="module")
@@ -79,11 +82,13 @@ def same_point(a, b, fmt):
     return (X1 * Z2 * Z2 - X2 * Z1 * Z1) % q == 0 and (Y1 * Z2 ** 3 - Y2 * Z1 ** 3) % q == 0
 
 
-def all_coeff(eng, plan, blob, n, batch, ofmt=L.G1_AFFINE_MONT, sfmt=L.FR_CANONICAL, flags=0, out=None):
+def all_coeff(eng, plan, blob, n, batch, ofmt=L.G1_AFFINE_MONT, sfmt=L.FR_CANONICAL, flags=0, out=None, evals=False):
+    """kzg_witness_all_coeff, or kzg_witness_all_eval with evals=True (then n = N)"""
     N = plan.domain()
     psz = L.POINT_BYTES[ofmt]
     buf = out if out is not None else ctypes.create_string_buffer(psz * N * batch)
-    rc = eng.lib.kzg_witness_all_coeff(eng.ctx, plan.handle, blob, n, batch, sfmt, flags, buf, ofmt)
+    fn = eng.lib.kzg_witness_all_eval if evals else eng.lib.kzg_witness_all_coeff
+    rc = fn(eng.ctx, plan.handle, blob, n, batch, sfmt, flags, buf, ofmt)
     if rc:
         _raise(eng, rc)
     return buf
@@ -95,6 +100,53 @@ def split(raw, psz, count):
 
 def evals_at_domain(coeffs, N):
     return C.fft(list(coeffs) + [0] * (N - len(coeffs)))
+
+
+def mont(xs):
+    return [x * MONT_R % M.R for x in xs]
+
+
+def dev_buffer(eng, nbytes):
+    """a device allocation filled with 0xA5, so that a region no call writes cannot pass for a result"""
+    p = ctypes.c_void_p()
+    assert eng.lib.kzg_dev_alloc(eng.ctx, nbytes, ctypes.byref(p)) == 0
+    assert eng.lib.kzg_dev_upload(eng.ctx, p, b"\xa5" * nbytes, nbytes) == 0
+    return p
+
+
+def dev_download(eng, p, nbytes):
+    back = ctypes.create_string_buffer(nbytes)
+    assert eng.lib.kzg_dev_download(eng.ctx, back, p, nbytes) == 0
+    return back.raw
+
+
+def known_tau_check(eng, rng, coeffs, N, proofs, ys=None):
+    """All N affine proofs of `coeffs` over the size-N domain (an SRS of this file's TAU) at once, by a route that shares
+    nothing with how they were computed: the MSM sum_m r_m pi_m against [sum_m r_m (p(tau) - p(w^m)) / (tau - w^m)] G."""
+    srs = kzg_amd.Srs.upload(eng, proofs, N)
+    try:
+        r = [rng.randrange(M.R) for _ in range(N)]
+        got = eng.msm(srs, r)
+    finally:
+        srs.free()
+    ys = evals_at_domain(coeffs, N) if ys is None else ys
+    p_tau = C.poly_eval(coeffs, TAU)
+    w = M.compute_omega(N)[2]
+    # one batched inversion of the denominators
+    dens, x = [], 1
+    for m in range(N):
+        dens.append((TAU - x) % M.R)
+        x = x * w % M.R
+    pref = [1] * (N + 1)
+    for m in range(N):
+        pref[m + 1] = pref[m] * dens[m] % M.R
+    inv = pow(pref[N], M.R - 2, M.R)
+    total = 0
+    for m in range(N - 1, -1, -1):
+        inv_m = inv * pref[m] % M.R
+        inv = inv * dens[m] % M.R
+        total = (total + r[m] * (p_tau - ys[m]) % M.R * inv_m) % M.R
+    assert got == C.g1_mul(G(), total), N
 
 
 # ---- 1. GLV multiplication --------------------------------------------------------------------------------------------------
@@ -208,6 +260,31 @@ def test_eval_form_matches_many(eng, params, plans, log_n):
         lag.free()
 
 
+@pytest.mark.limit(300)
+@pytest.mark.parametrize("log_n", [3, 10])
+def test_scalar_forms_and_eval_form_through_the_abi(eng, plans, log_n):
+    # Montgomery coefficients, canonical and Montgomery evaluations: the same witnesses as canonical coefficients, in every
+    # output format and in a batch of 3
+    rng = random.Random(450 + log_n)
+    N, B = 1 << log_n, 3
+    plan = plans(log_n)
+    polys = [rand_scalars(rng, N, kind) for kind in ("full", "u64", "full")]
+    coeffs = [c for p in polys for c in p]
+    evs = [e for p in polys for e in C.fft(p)]
+    inputs = [(pack_scalars(mont(coeffs)), L.FR_MONT, False), (pack_scalars(evs), L.FR_CANONICAL, True),
+              (pack_scalars(mont(evs)), L.FR_MONT, True)]
+    for ofmt in FORMATS:
+        psz = L.POINT_BYTES[ofmt]
+        want = all_coeff(eng, plan, pack_scalars(coeffs), N, B, ofmt).raw
+        for b in range(B):
+            assert all_coeff(eng, plan, pack_scalars(polys[b]), N, 1, ofmt).raw == want[b * N * psz:(b + 1) * N * psz], (ofmt, b)
+        want = split(want, psz, B * N)
+        for blob, sfmt, evals in inputs:
+            got = split(all_coeff(eng, plan, blob, N, B, ofmt, sfmt=sfmt, evals=evals).raw, psz, B * N)
+            for i in range(B * N):
+                assert same_point(got[i], want[i], ofmt), (N, ofmt, sfmt, evals, i)
+
+
 # ---- 5. batch and device buffers ----------------------------------------------------------------------------------------------
 @pytest.mark.limit(600)
 def test_batch_equals_single_calls_and_device_flags(eng, plans):
@@ -259,43 +336,45 @@ def test_every_proof_verifies(eng, params, plans):
 
 
 # ---- 7. known-tau random combination at full size -----------------------------------------------------------------------------
-@pytest.mark.limit(900)
-@pytest.mark.parametrize("log_n", [16, 20])
-def test_known_tau_random_combination(eng, log_n):
+def run_known_tau(eng, log_n):
     rng = random.Random(7 + log_n)
     N = 1 << log_n
     gs = kzg_amd.setup(eng, TAU, N, g2_len=0).gs
-    plan = kzg_amd.FK20Plan(eng, gs, log_n)
     try:
-        coeffs = rand_scalars(rng, N)
-        proofs = all_coeff(eng, plan, pack_scalars(coeffs), N, 1).raw
+        plan = kzg_amd.FK20Plan(eng, gs, log_n)
+        try:
+            coeffs = rand_scalars(rng, N)
+            proofs = all_coeff(eng, plan, pack_scalars(coeffs), N, 1).raw
+        finally:
+            plan.free()
+        # 16 openings through kzg_witness_coeff_many, an MSM route that shares no G1 DFT with FK20
+        idx = [0, 1, N // 2, N - 1]
+        while len(idx) < 16:
+            m = rng.randrange(N)
+            if m not in idx:
+                idx.append(m)
+        ys = evals_at_domain(coeffs, N)
+        w = M.compute_omega(N)[2]
+        prover = kzg_amd.KZGProver(kzg_amd.KZGParams(gs))
+        want, ok = prover.create_witness_many(kzg_amd.Polynomial(coeffs, N - 1), [(pow(w, m, M.R), ys[m]) for m in idx])
+        assert all(ok)
+        for m, wm in zip(idx, want):
+            assert proofs[m * 96:(m + 1) * 96] == wm, (N, m)
     finally:
-        plan.free()
         gs.free()
-    srs = kzg_amd.Srs.upload(eng, proofs, N)
-    try:
-        r = [rng.randrange(M.R) for _ in range(N)]
-        got = eng.msm(srs, r)
-    finally:
-        srs.free()
-    ys = evals_at_domain(coeffs, N)
-    p_tau = C.poly_eval(coeffs, TAU)
-    w = M.compute_omega(N)[2]
-    # sum r_m (p(tau) - p(w^m)) / (tau - w^m), one batched inversion
-    dens, x = [], 1
-    for m in range(N):
-        dens.append((TAU - x) % M.R)
-        x = x * w % M.R
-    pref = [1] * (N + 1)
-    for m in range(N):
-        pref[m + 1] = pref[m] * dens[m] % M.R
-    inv = pow(pref[N], M.R - 2, M.R)
-    total = 0
-    for m in range(N - 1, -1, -1):
-        inv_m = inv * pref[m] % M.R
-        inv = inv * dens[m] % M.R
-        total = (total + r[m] * (p_tau - ys[m]) % M.R * inv_m) % M.R
-    assert got == C.g1_mul(G(), total)
+    known_tau_check(eng, rng, coeffs, N, proofs, ys)
+
+
+@pytest.mark.limit(900)
+@pytest.mark.parametrize("log_n", [16, 20])
+def test_known_tau_random_combination(eng, log_n):
+    run_known_tau(eng, log_n)
+
+
+@pytest.mark.limit(300)  # measured on one MI355X: 22 s, most of it the Python oracle
+def test_known_tau_random_combination_at_the_limit(eng):
+    # log_n = 22 = FK20_MAX_LOG: 2^22 polynomial coefficients, a plan of 2^23 points, G1 DFTs of 2^23 (inverse) and 2^22 points
+    run_known_tau(eng, 22)
 
 
 # ---- 8. validation and sharing ------------------------------------------------------------------------------------------------
@@ -312,6 +391,17 @@ def test_validation(eng, params, plans):
     def ev(d, p=plan):
         return lib.kzg_witness_all_eval(eng.ctx, p.handle, blob, d, 1, L.FR_CANONICAL, 0, out, L.G1_AFFINE_MONT)
 
+    # unknown formats, NULL arguments, a batch whose sizes overflow: rejected, in both forms, before any memory is touched
+    sentinel = b"\xa5" * len(out)
+    ctypes.memmove(out, sentinel, len(sentinel))
+    for fn in (lib.kzg_witness_all_coeff, lib.kzg_witness_all_eval):
+        def call(fn=fn, ctx=eng.ctx, p=plan.handle, src=blob, batch=1, sfmt=L.FR_CANONICAL, o=out, ofmt=L.G1_AFFINE_MONT):
+            return fn(ctx, p, src, N, batch, sfmt, 0, o, ofmt)
+        assert call(sfmt=7) == L.KZG_ERR_SHAPE and call(ofmt=99) == L.KZG_ERR_SHAPE
+        assert call(src=None) == L.KZG_ERR_SHAPE and call(o=None) == L.KZG_ERR_SHAPE
+        assert call(p=None) == L.KZG_ERR_SHAPE and call(ctx=None) == L.KZG_ERR_SHAPE
+        assert call(batch=SIZE_MAX // (N * 144) + 1) == L.KZG_ERR_SHAPE and call(batch=SIZE_MAX) == L.KZG_ERR_SHAPE
+    assert out.raw == sentinel
     assert coeff(0) == L.KZG_ERR_SHAPE
     assert coeff(N + 1) == L.KZG_ERR_SHAPE
     assert coeff(N) == 0 and coeff(1) == 0 and coeff(N, 0) == 0
@@ -382,3 +472,144 @@ def test_plan_shared_by_two_threads_on_two_contexts(eng, plans):
             e.close()
     assert not errors, errors
     assert all(r == want for rs in results for r in rs)
+
+
+# ---- 9. batches of several chunks ---------------------------------------------------------------------------------------------
+# fk20_run works through a batch in chunks of F.chunk_size(N) polynomials, the last one ragged, with n < N so that the input
+# (b0 n) and output (b0 N) offsets differ.  Every batched result equals single calls (one chunk each), and the polynomials at
+# chunk edges also pass an oracle that shares no code with the batched path.
+@pytest.fixture(scope="module")
+def batch14(eng):
+    """130 = 64 + 64 + 2 polynomials of N - 3 coefficients at N = 2^14 (chunk 64) on a local SRS, and their witnesses from one
+    batched coeff-form call"""
+    log_n = 14
+    N = 1 << log_n
+    assert F.chunk_size(N) == 64
+    gs = kzg_amd.setup(eng, TAU, N, g2_len=0).gs
+    plan = kzg_amd.FK20Plan(eng, gs, log_n)
+    rng = random.Random(90)
+    n, B = N - 3, 130
+    polys = [rand_scalars(rng, n, "full" if b % 2 else "u64") for b in range(B)]
+    blob = b"".join(pack_scalars(p) for p in polys)
+    out = all_coeff(eng, plan, blob, n, B).raw
+    yield SimpleNamespace(plan=plan, N=N, n=n, B=B, polys=polys, blob=blob, out=out)
+    plan.free()
+    gs.free()
+
+
+@pytest.mark.limit(600)
+def test_chunked_batch_coeff_form(eng, batch14):
+    t = batch14
+    N, n, B, sz = t.N, t.n, t.B, t.N * 96
+    rng = random.Random(91)
+    for b in range(B):
+        assert all_coeff(eng, t.plan, pack_scalars(t.polys[b]), n, 1).raw == t.out[b * sz:(b + 1) * sz], b
+    for b in (63, 64, 129):  # the last of chunk 0, the first of chunk 1, the last of the ragged chunk 2
+        known_tau_check(eng, rng, t.polys[b], N, t.out[b * sz:(b + 1) * sz])
+    din = eng.alloc_scalars(n * B)
+    din.upload(t.blob)
+    dout = dev_buffer(eng, sz * B)
+    try:
+        assert all_coeff(eng, t.plan, din.ptr, n, B, flags=L.IN_DEVICE).raw == t.out
+        for flags, src in ((L.OUT_DEVICE, t.blob), (L.IN_DEVICE | L.OUT_DEVICE, din.ptr)):
+            assert eng.lib.kzg_dev_upload(eng.ctx, dout, b"\xa5" * (sz * B), sz * B) == 0
+            all_coeff(eng, t.plan, src, n, B, flags=flags, out=dout)
+            assert dev_download(eng, dout, sz * B) == t.out, flags
+    finally:
+        eng.lib.kzg_dev_free(eng.ctx, dout)
+        din.free()
+    mblob = pack_scalars(mont(c for p in t.polys for c in p))
+    assert all_coeff(eng, t.plan, mblob, n, B, sfmt=L.FR_MONT).raw == t.out
+
+
+@pytest.mark.limit(600)
+def test_chunked_batch_eval_form(eng, batch14):
+    t = batch14
+    N, B = t.N, t.B
+    evs = [e for p in t.polys for e in evals_at_domain(p, N)]
+    for sfmt, vals in ((L.FR_CANONICAL, evs), (L.FR_MONT, mont(evs))):
+        blob = pack_scalars(vals)
+        assert all_coeff(eng, t.plan, blob, N, B, sfmt=sfmt, evals=True).raw == t.out, sfmt
+        din = eng.alloc_scalars(N * B, sfmt)
+        try:
+            din.upload(blob)
+            assert all_coeff(eng, t.plan, din.ptr, N, B, sfmt=sfmt, flags=L.IN_DEVICE, evals=True).raw == t.out, sfmt
+        finally:
+            din.free()
+
+
+@pytest.mark.limit(600)
+def test_chunk_cap_branch(eng, params, plans):
+    # N = 64: FK20_CHUNK_POINTS / 2N = 16384, so FK20_MAX_CHUNK sets the chunk; 4099 = 4096 + 3
+    rng = random.Random(92)
+    N, n, B = 64, 61, 4099
+    assert F.chunk_size(N) == 4096 < (1 << 21) // (2 * N)
+    plan = plans(6)
+    polys = [rand_scalars(rng, n, "full" if b % 2 else "u64") for b in range(B)]
+    out = all_coeff(eng, plan, b"".join(pack_scalars(p) for p in polys), n, B).raw
+    sz = N * 96
+    prover = kzg_amd.KZGProver(params)
+    w = M.compute_omega(N)[2]
+    xs = [pow(w, m, M.R) for m in range(N)]
+    for b in (0, 4095, 4096, 4098):
+        got = out[b * sz:(b + 1) * sz]
+        assert all_coeff(eng, plan, pack_scalars(polys[b]), n, 1).raw == got, b
+        want, ok = prover.create_witness_many(kzg_amd.Polynomial(polys[b], n - 1), list(zip(xs, evals_at_domain(polys[b], N))))
+        assert all(ok) and b"".join(want) == got, b
+    eblob = b"".join(pack_scalars(evals_at_domain(p, N)) for p in polys)
+    assert all_coeff(eng, plan, eblob, N, B, evals=True).raw == out
+
+
+@pytest.mark.limit(600)
+def test_chunk_of_one(eng):
+    # N = 2^20: one polynomial per chunk; host output in the 48-byte compressed form, device output affine
+    rng = random.Random(93)
+    log_n = 20
+    N = 1 << log_n
+    n, B = N - 5, 3
+    assert F.chunk_size(N) == 1
+    gs = kzg_amd.setup(eng, TAU, N, g2_len=0).gs
+    try:
+        plan = kzg_amd.FK20Plan(eng, gs, log_n)
+        try:
+            polys = [rand_scalars(rng, n, "u64" if b == 1 else "full") for b in range(B)]
+            blob = b"".join(pack_scalars(p) for p in polys)
+            comp = all_coeff(eng, plan, blob, n, B, ofmt=L.G1_ZCASH_COMPRESSED).raw
+            dout = dev_buffer(eng, N * B * 96)
+            try:
+                all_coeff(eng, plan, blob, n, B, flags=L.OUT_DEVICE, out=dout)
+                aff = dev_download(eng, dout, N * B * 96)
+            finally:
+                eng.lib.kzg_dev_free(eng.ctx, dout)
+            for b in range(B):
+                one = pack_scalars(polys[b])
+                for ofmt, got in ((L.G1_ZCASH_COMPRESSED, comp), (L.G1_AFFINE_MONT, aff)):
+                    psz = L.POINT_BYTES[ofmt]
+                    assert all_coeff(eng, plan, one, n, 1, ofmt).raw == got[b * N * psz:(b + 1) * N * psz], (b, ofmt)
+        finally:
+            plan.free()
+    finally:
+        gs.free()
+    known_tau_check(eng, rng, polys[2], N, aff[2 * N * 96:])
+
+
+def test_domain_of_one(eng, params, plans):
+    # N = 1: every quotient is zero; each element is the identity as kzg_witness_coeff_many writes it
+    rng = random.Random(94)
+    plan = plans(0)
+    B = 5
+    cs = [rng.randrange(M.R) for _ in range(B)]
+    prover = kzg_amd.KZGProver(params)
+    for ofmt in FORMATS:
+        psz = L.POINT_BYTES[ofmt]
+        want, ok = prover.create_witness_many(kzg_amd.Polynomial(cs[:1], 0), [(1, cs[0])], ofmt)
+        assert ok == [True]
+        host = ctypes.create_string_buffer(b"\xa5" * (psz * B), psz * B)
+        all_coeff(eng, plan, pack_scalars(cs), 1, B, ofmt, out=host)
+        assert split(host.raw, psz, B) == want * B, ofmt
+        dout = dev_buffer(eng, psz * B)
+        try:
+            all_coeff(eng, plan, pack_scalars(cs), 1, B, ofmt, flags=L.OUT_DEVICE, out=dout)
+            assert split(dev_download(eng, dout, psz * B), psz, B) == want * B, ofmt
+        finally:
+            eng.lib.kzg_dev_free(eng.ctx, dout)

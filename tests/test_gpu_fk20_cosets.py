@@ -13,15 +13,15 @@ from kzg_amd import _lib as L
 from kzg_amd.api import _raise, pack_scalars, unpack_scalars
 from oracle import c_oracle as C
 from oracle import kzg_model as M
+from tests import fk20_model as F
 from tests.gpu_common import HooksEngine, rand_scalars
-from tests.test_gpu_fk20 import FORMATS, same_point, split
+from tests.test_gpu_fk20 import FORMATS, MONT_R, SIZE_MAX, dev_buffer, dev_download, same_point, split
 
 pytestmark = pytest.mark.gpu
 
 TAU = 0x5EED_C05E7
 SRS_LEN = 1 << 12
 VP, SZ, I32, U32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32
-MONT_R = pow(2, 256, M.R)
 
 
 @pytest.fixture(scope="module")
@@ -250,24 +250,32 @@ def test_every_coset_proof_verifies(eng, params, plans):
 
 
 # ---- 5. known-tau random combination at full size -----------------------------------------------------------------------------
-@pytest.mark.limit(900)
-@pytest.mark.parametrize("log_n,log_l", [(16, 4), (20, 6)])
-def test_known_tau_random_combination(eng, log_n, log_l):
+def run_known_tau(eng, log_n, log_l):
     rng = random.Random(7 + log_n)
     N, l = 1 << log_n, 1 << log_l
     K = N // l
     gs = kzg_amd.setup(eng, TAU, N, g2_len=0).gs
-    plan = kzg_amd.FK20CosetPlan(eng, gs, log_n, log_l)
     try:
-        coeffs = rand_scalars(rng, N)
-        proofs, interp = cosets(eng, plan, pack_scalars(coeffs), N, 1)
-        proofs = proofs.raw
+        plan = kzg_amd.FK20CosetPlan(eng, gs, log_n, log_l)
+        try:
+            coeffs = rand_scalars(rng, N)
+            proofs, interp = cosets(eng, plan, pack_scalars(coeffs), N, 1)
+            proofs, interp = proofs.raw, interp.raw
+        finally:
+            plan.free()
+        # the interpolants, independently: coefficient r of I_i is DFT_K(c^(r))_i
+        cols = [C.fft(coeffs[r::l]) for r in range(l)]
+        # two cosets through kzg_witness_coeff_batched, an MSM route that shares no G1 DFT with the plan (p = I_i on coset i)
+        w = M.compute_omega(N)[2]
+        params = kzg_amd.KZGParams(gs)
+        for i in (K - 1, rng.randrange(K - 1)):
+            xs = [pow(w, i + t * K, M.R) for t in range(l)]
+            ys = [sum(cols[r][i] * pow(x, r, M.R) for r in range(l)) % M.R for x in xs]
+            want_w, want_r = batched(eng, params, coeffs, xs, ys, L.G1_AFFINE_MONT)
+            assert proofs[i * 96:(i + 1) * 96] == want_w and interp[i * l * 32:(i + 1) * l * 32] == want_r, (N, l, i)
     finally:
-        plan.free()
         gs.free()
-    # the interpolants, independently: coefficient r of I_i is DFT_K(c^(r))_i
-    cols = [C.fft(coeffs[r::l]) for r in range(l)]
-    I = unpack_scalars(interp.raw)
+    I = unpack_scalars(interp)
     sample = [0, 1, K - 1] + rng.sample(range(K), 61)
     for i in sample:
         assert I[i * l:(i + 1) * l] == [cols[r][i] for r in range(l)], i
@@ -297,6 +305,20 @@ def test_known_tau_random_combination(eng, log_n, log_l):
         i_tau = sum(cols[r][i] * tpow[r] for r in range(l)) % M.R
         total = (total + rho[i] * (p_tau - i_tau) % M.R * inv_i) % M.R
     assert got == C.g1_mul(G(), total)
+
+
+@pytest.mark.limit(900)
+@pytest.mark.parametrize("log_n,log_l", [(16, 4), (20, 6)])
+def test_known_tau_random_combination(eng, log_n, log_l):
+    run_known_tau(eng, log_n, log_l)
+
+
+@pytest.mark.limit(300)  # measured on one MI355X: 17 s (l = 2), 10 s (l = 64)
+@pytest.mark.parametrize("log_l", [1, 6])
+def test_known_tau_random_combination_at_the_limit(eng, log_l):
+    # log_n = 22 = FK20_MAX_LOG.  l = 2 has the largest K: G1 DFTs of 2^22 (inverse) and 2^21 points and a plan of 8.6 GB;
+    # l = 64 has a 64-term combination per frequency
+    run_known_tau(eng, 22, log_l)
 
 
 # ---- 6. the combination kernel alone ------------------------------------------------------------------------------------------
@@ -396,6 +418,12 @@ def test_validation(eng, params, plans):
     assert coeff(N, sfmt=7) == L.KZG_ERR_SHAPE and coeff(N, ofmt=99) == L.KZG_ERR_SHAPE
     assert coeff(N, src=None) == L.KZG_ERR_SHAPE and coeff(N, w=None) == L.KZG_ERR_SHAPE and coeff(N, p=None) == L.KZG_ERR_SHAPE
     assert lib.kzg_witness_cosets_coeff(None, plan.handle, blob, N, 1, CAN, 0, out, A, rbuf) == L.KZG_ERR_SHAPE
+    # a batch whose sizes overflow, in both forms: rejected before any memory is touched
+    gw, gr = ctypes.create_string_buffer(b"\xa5" * 96, 96), ctypes.create_string_buffer(b"\xa5" * 32, 32)
+    for fn in (lib.kzg_witness_cosets_coeff, lib.kzg_witness_cosets_eval):
+        for batch in (SIZE_MAX // (N * 144) + 1, SIZE_MAX):
+            assert fn(eng.ctx, plan.handle, blob, N, batch, CAN, 0, gw, A, gr) == L.KZG_ERR_SHAPE, batch
+    assert gw.raw == b"\xa5" * 96 and gr.raw == b"\xa5" * 32
     assert ev(N - 1) == L.KZG_ERR_SHAPE and ev(N + 1) == L.KZG_ERR_SHAPE and ev(N) == 0
     assert lib.kzg_fk20_cosets_shape(None, None, None) == L.KZG_ERR_SHAPE
     # a short SRS of 3 points: n - l > len(srs) is the reference's slice panic; n - l == len(srs) is exact; n <= l needs none
@@ -476,3 +504,122 @@ def test_plan_shared_by_two_threads_on_two_contexts(eng, plans):
             e.close()
     assert not errors, errors
     assert all(r == want for rs in results for r in rs)
+
+
+# ---- 9. batches of several chunks ---------------------------------------------------------------------------------------------
+# cosets_run works through a batch in chunks of F.chunk_size(N) polynomials, the last one ragged, and splits each chunk's
+# combination into F.coset_slices residue slices chosen from the FIRST chunk.  n < N, so that the input (b0 n) and output (b0 K,
+# b0 N) offsets differ.  Every batch equals single calls, and the polynomials at chunk edges also equal kzg_witness_coeff_batched.
+@pytest.fixture(scope="module")
+def local_srs(eng):
+    """monomial SRSs of this file's TAU past the 2^12 fixture, one per size"""
+    cache = {}
+
+    def get(log_n):
+        if log_n not in cache:
+            cache[log_n] = kzg_amd.setup(eng, TAU, 1 << log_n, g2_len=0).gs
+        return cache[log_n]
+    yield get
+    for gs in cache.values():
+        gs.free()
+
+
+def check_edges(eng, gs, polys, N, l, bw, br, edges, count, rng):
+    """`count` cosets (0, K - 1, then random ones) of each polynomial b in `edges` against kzg_witness_coeff_batched"""
+    K = N // l
+    params = kzg_amd.KZGParams(gs)
+    w = M.compute_omega(N)[2]
+    for b in edges:
+        ev = C.fft(polys[b] + [0] * (N - len(polys[b])))
+        for i in ([0, K - 1] + rng.sample(range(1, K - 1), max(0, count - 2)))[:count]:
+            xs = [pow(w, i + t * K, M.R) for t in range(l)]
+            want_w, want_r = batched(eng, params, polys[b], xs, [ev[i + t * K] for t in range(l)], L.G1_AFFINE_MONT)
+            assert bw[(b * K + i) * 96:(b * K + i + 1) * 96] == want_w, (N, l, b, i)
+            assert br[(b * N + i * l) * 32:(b * N + (i + 1) * l) * 32] == want_r, (N, l, b, i)
+
+
+@pytest.mark.limit(600)
+@pytest.mark.parametrize("route", [0, 1])
+def test_chunked_batch_with_sliced_combination(eng, local_srs, route):
+    # (14, 6): chunks of 64, 130 = 64 + 64 + 2; the first chunk's S = 4 residue slices are kept for the last chunk of 2
+    rng = random.Random(70 + route)
+    log_n, log_l = 14, 6
+    N, l = 1 << log_n, 1 << log_l
+    K, n, B = N // l, N - 3, 130
+    chunk = F.chunk_size(N)
+    assert (chunk, B % chunk) == (64, 2)
+    assert F.coset_slices(l, 2 * K, chunk) == 4, "the slicing rule changed: (14, 6) no longer splits a chunk's residues"
+    gs = local_srs(log_n)
+    plan = kzg_amd.FK20CosetPlan(eng, gs, log_n, log_l)
+    eng.set_option("fk20_cosets_combine", route)
+    try:
+        polys = [rand_scalars(rng, n, "full" if b % 2 else "u64") for b in range(B)]
+        bw, br = cosets(eng, plan, b"".join(pack_scalars(p) for p in polys), n, B)
+        bw, br = bw.raw, br.raw
+        for b in range(B):
+            w1, r1 = cosets(eng, plan, pack_scalars(polys[b]), n, 1)
+            assert w1.raw == bw[b * K * 96:(b + 1) * K * 96] and r1.raw == br[b * N * 32:(b + 1) * N * 32], (route, b)
+        check_edges(eng, gs, polys, N, l, bw, br, (63, 64, 129), 4, rng)
+    finally:
+        eng.set_option("fk20_cosets_combine", 0)
+        plan.free()
+
+
+@pytest.mark.limit(600)
+def test_chunked_eval_form_on_the_device(eng, local_srs):
+    # (16, 4): chunks of 16, 35 = 16 + 16 + 3.  Montgomery evaluations in device memory, witnesses and interpolants written to
+    # device memory (offsets b0 K psz and b0 N 32), against the host canonical coeff-form batch
+    rng = random.Random(72)
+    log_n, log_l = 16, 4
+    N, l = 1 << log_n, 1 << log_l
+    K, n, B = N // l, N - 3, 35
+    assert (F.chunk_size(N), B % F.chunk_size(N)) == (16, 3)
+    gs = local_srs(log_n)
+    plan = kzg_amd.FK20CosetPlan(eng, gs, log_n, log_l)
+    din = dw = dr = None
+    try:
+        polys = [rand_scalars(rng, n, "full" if b % 2 else "u64") for b in range(B)]
+        want_w, want_r = cosets(eng, plan, b"".join(pack_scalars(p) for p in polys), n, B)
+        want_w, want_r = want_w.raw, want_r.raw
+        din = eng.alloc_scalars(N * B, L.FR_MONT)
+        din.upload(pack_scalars([e * MONT_R % M.R for p in polys for e in C.fft(p + [0] * (N - n))]))
+        dw, dr = dev_buffer(eng, K * B * 96), dev_buffer(eng, N * B * 32)
+        cosets(eng, plan, din.ptr, N, B, sfmt=L.FR_MONT, flags=L.IN_DEVICE | L.OUT_DEVICE, out_w=dw, out_r=dr, evals=True)
+        assert dev_download(eng, dw, K * B * 96) == want_w
+        assert dev_download(eng, dr, N * B * 32) == pack_scalars([v * MONT_R % M.R for v in unpack_scalars(want_r)])
+        check_edges(eng, gs, polys, N, l, want_w, want_r, (15, 16, 34), 2, rng)
+    finally:
+        plan.free()
+        if din is not None:
+            din.free()
+        for p in (dw, dr):
+            if p is not None:
+                eng.lib.kzg_dev_free(eng.ctx, p)
+
+
+@pytest.mark.limit(600)
+def test_chunk_of_one(eng):
+    # (20, 6): one polynomial per chunk, batch 2, with and without interpolants
+    rng = random.Random(73)
+    log_n, log_l = 20, 6
+    N, l = 1 << log_n, 1 << log_l
+    K, n, B = N // l, N - 5, 2
+    assert F.chunk_size(N) == 1
+    gs = kzg_amd.setup(eng, TAU, N, g2_len=0).gs
+    try:
+        plan = kzg_amd.FK20CosetPlan(eng, gs, log_n, log_l)
+        try:
+            polys = [rand_scalars(rng, n, kind) for kind in ("u64", "full")]
+            blob = b"".join(pack_scalars(p) for p in polys)
+            bw, br = cosets(eng, plan, blob, n, B)
+            bw, br = bw.raw, br.raw
+            wn, rn = cosets(eng, plan, blob, n, B, want_r=False)
+            assert rn is None and wn.raw == bw
+            for b in range(B):
+                w1, r1 = cosets(eng, plan, pack_scalars(polys[b]), n, 1)
+                assert w1.raw == bw[b * K * 96:(b + 1) * K * 96] and r1.raw == br[b * N * 32:(b + 1) * N * 32], b
+        finally:
+            plan.free()
+        check_edges(eng, gs, polys, N, l, bw, br, (1,), 2, rng)
+    finally:
+        gs.free()
