@@ -348,25 +348,34 @@ class Srs:
         return Srs(engine, h)
 
 
-class FK20Plan:
-    """kzg_fk20: the per-domain tables of FK20 (every opening of a polynomial over its size-2^log_n domain in one call) for one
-    monomial SRS.  Not a reference type."""
+class _Fk20Handle:
+    """What FK20Plan and FK20CosetPlan share: the opaque handle from the kind's setup entry point and its release."""
+    _setup = _free = None  # names of the two entry points
 
-    def __init__(self, engine, srs, log_n):
+    def __init__(self, engine, srs, *shape):
         self.engine = engine
         h = ctypes.c_void_p()
-        rc = engine.lib.kzg_fk20_setup(engine.ctx, srs.handle, log_n, ctypes.byref(h))
+        rc = getattr(engine.lib, self._setup)(engine.ctx, srs.handle, *shape, ctypes.byref(h))
         if rc:
             _raise(engine, rc)
         self.handle = h
 
-    def domain(self):
-        return self.engine.lib.kzg_fk20_domain(self.handle)
-
     def free(self):
         if self.handle:
-            self.engine.lib.kzg_fk20_free(self.engine.ctx, self.handle)
+            getattr(self.engine.lib, self._free)(self.engine.ctx, self.handle)
             self.handle = None
+
+
+class FK20Plan(_Fk20Handle):
+    """kzg_fk20: the per-domain tables of FK20 (every opening of a polynomial over its size-2^log_n domain in one call) for one
+    monomial SRS.  Not a reference type."""
+    _setup, _free = "kzg_fk20_setup", "kzg_fk20_free"
+
+    def __init__(self, engine, srs, log_n):
+        super().__init__(engine, srs, log_n)
+
+    def domain(self):
+        return self.engine.lib.kzg_fk20_domain(self.handle)
 
 
 def _witness_all(engine, fn, plan, blob, n, batch, ofmt):
@@ -379,18 +388,15 @@ def _witness_all(engine, fn, plan, blob, n, batch, ofmt):
     return [[out.raw[(b * N + m) * psz:(b * N + m + 1) * psz] for m in range(N)] for b in range(batch)]
 
 
-class FK20CosetPlan:
+class FK20CosetPlan(_Fk20Handle):
     """kzg_fk20_cosets: the per-domain tables of multi-point FK20 (every opening of a polynomial at every coset of 2^log_l points
     of its size-2^log_n domain in one call) for one monomial SRS.  Coset i is {w^(i + tK) : t < l}, K = N / l.  Not a reference
     type."""
 
+    _setup, _free = "kzg_fk20_cosets_setup", "kzg_fk20_cosets_free"
+
     def __init__(self, engine, srs, log_n, log_l):
-        self.engine = engine
-        h = ctypes.c_void_p()
-        rc = engine.lib.kzg_fk20_cosets_setup(engine.ctx, srs.handle, log_n, log_l, ctypes.byref(h))
-        if rc:
-            _raise(engine, rc)
-        self.handle = h
+        super().__init__(engine, srs, log_n, log_l)
         self._shape = None
 
     def _dims(self):
@@ -418,11 +424,6 @@ class FK20CosetPlan:
         K = N // l
         w = compute_omega(N)[2]
         return [pow(w, i + t * K, R_MODULUS) for t in range(l)]
-
-    def free(self):
-        if self.handle:
-            self.engine.lib.kzg_fk20_cosets_free(self.engine.ctx, self.handle)
-            self.handle = None
 
 
 def _witness_cosets(engine, fn, plan, blob, n, batch, ofmt):

@@ -1,5 +1,6 @@
-// g1ntt.hip -- FK20 (Feist-Khovratovich, single-point case): every opening of one polynomial over its whole evaluation domain in
-// O(N log N) group operations, and the reusable G1 DFT it is built on.
+// g1ntt.hip -- the G1 DFT and its callers: FK20 (Feist-Khovratovich), every opening of one polynomial over its whole evaluation
+// domain in O(N log N) group operations, at single points (described first) and at cosets (further down), both through one plan
+// representation, one setup and one chunked run function; and compute_lagrange_basis from the monomial SRS (at the end).
 //
 // Domain N = 2^k, w = compute_omega(N).omega, coefficients c_0..c_{N-1} (zero-padded from n <= N), s_i = [tau^i]G.  The witness
 // at w^m is pi_m = [q_m(tau)] with q_m = (p - p(w^m)) / (X - w^m), and pi = DFT_N(H) with H_k = sum_{i <= N-2-k} c_{i+k+1} s_i
@@ -20,6 +21,8 @@
 // thread count so that a wave's reads and writes are coalesced.  The stage with half-size 1 has trivial twiddles only and its own
 // kernel of two additions per butterfly.  The point-wise products (varying scalars) use the same signed digits over 256 bits.
 #include <algorithm>
+#include <optional>
+#include <string>
 
 #include "common.h"
 #include "emit.h"
@@ -103,24 +106,27 @@ __global__ __launch_bounds__(256) void k_glv_twiddles(const Fr *pw, size_t count
     out[i] = glv_recode(k.v);
 }
 
-// x_j = s_{N-2-j} (j <= N-2 and inside the SRS), O otherwise; j < 2N
-__global__ __launch_bounds__(256) void k_fk20_load_x(const G1Affine *srs, size_t srs_n, size_t N, MsmPoint *X) {
-    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= 2 * N) return;
-    const size_t i = N - 2 - j;  // wraps for j >= N - 1
-    X[j] = (j + 2 <= N && i < srs_n) ? g1_from_affine30(g1_affine_to30(srs[i]), false) : MsmPoint::infinity();
+// The two kernels below take the coset size l of the multi-point case (further down); l = 1, K = N is the layout above.
+// X[r][j] = x^(r)_j = s_{r + (K-2-j) l} (j <= K-2 and inside the SRS), O otherwise; r < l, j < 2K
+__global__ __launch_bounds__(256) void k_fk20_load_x(const G1Affine *srs, size_t srs_n, size_t K, size_t l, MsmPoint *X) {
+    const size_t two = 2 * K, u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= l * two) return;
+    const size_t r = u / two, j = u % two;
+    const bool in = j + 2 <= K && r + (K - 2 - j) * l < srs_n;
+    X[u] = in ? g1_from_affine30(g1_affine_to30(srs[r + (K - 2 - j) * l]), false) : MsmPoint::infinity();
 }
 
-// y (2N Montgomery scalars per polynomial) from n coefficients per polynomial (stride n) in sfmt
-__global__ __launch_bounds__(256) void k_fk20_build_y(const Fr *c, size_t n, size_t N, size_t batch, int sfmt, Fr *y) {
+// y[(b l + r) 2K + t] = y^(r)_t of polynomial b, from n coefficients per polynomial (stride n) in sfmt; Montgomery out
+__global__ __launch_bounds__(256) void k_fk20_build_y(const Fr *c, size_t n, size_t K, size_t l, size_t batch, int sfmt, Fr *y) {
     const size_t nt = (size_t)gridDim.x * blockDim.x;
-    const size_t two = 2 * N, work = batch * two;
+    const size_t two = 2 * K, work = batch * l * two;
     for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < work; u += nt) {
-        const size_t b = u / two, t = u % two;
-        const size_t idx = t == 0 ? N - 1 : (t > N ? t - N - 1 : (size_t)-1);
+        const size_t a = u / two, t = u % two, b = a / l, r = a % l;
+        const bool has = t == 0 || t > K;
+        const size_t ci = r + (t == 0 ? K - 1 : t - K - 1) * l;
         Fr v = Fr::zero();
-        if (idx < n) {
-            v = c[b * n + idx];
+        if (has && ci < n) {
+            v = c[b * n + ci];
             if (sfmt == KZG_FR_CANONICAL_LE_32) v = to_mont(v);
         }
         y[u] = v;
@@ -196,201 +202,6 @@ static int g1_dft(kzg_ctx *ctx, hipStream_t st, MsmPoint *P, size_t pstride, uin
     return KZG_OK;
 }
 
-}  // namespace kzg
-
-using namespace kzg;
-
-struct kzg_fk20 {
-    int device = 0;
-    uint32_t log_n = 0;
-    size_t N = 0;
-    size_t srs_n = 0;               // length of the monomial SRS the plan was built from
-    MsmPoint *xhat = nullptr;       // DFT_2N(x), bit-reversed (2N points)
-    GlvTw *tw_fwd = nullptr;        // w_2N^e, e < N
-    GlvTw *tw_inv = nullptr;        // w_2N^-e, e < N
-    Fr inv2n;                       // 1 / 2N, Montgomery
-    Fq30 beta;
-};
-
-static void fk20_release(kzg_fk20 *p) {
-    if (!p) return;
-    if (p->xhat) hipFree(p->xhat);
-    if (p->tw_fwd) hipFree(p->tw_fwd);
-    if (p->tw_inv) hipFree(p->tw_inv);
-    delete p;
-}
-
-extern "C" int kzg_fk20_setup(kzg_ctx *ctx, const kzg_srs *monomial, uint32_t log_n, kzg_fk20 **out) {
-    if (!ctx || !monomial || !out) return KZG_ERR_SHAPE;
-    Guard g(ctx);
-    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (monomial->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "SRS resident on another GPU");
-    if (log_n + 1 >= FR_TWO_ADICITY) return fail(ctx, KZG_ERR_DEGREE_TOO_LARGE, "domain too large");
-    if (log_n > FK20_MAX_LOG) return fail(ctx, KZG_ERR_SHAPE, "kzg_fk20_setup: log_n <= 22 (documented limit)");
-    kzg_fk20 *p = new kzg_fk20();
-    p->device = ctx->device;
-    p->log_n = log_n;
-    p->N = (size_t)1 << log_n;
-    p->srs_n = monomial->n;
-    p->beta = beta30();
-    const size_t N = p->N, two = 2 * N;
-    const Fr w = host_omega(log_n + 1);  // w_2N, w_2N^2 = w_N = compute_omega(N).omega
-    p->inv2n = inv(from_u64<FrParams>((uint64_t)two));
-    hipStream_t st = ctx->lanes[0].stream;
-    int rc = KZG_OK;
-    Fr *pw = nullptr;
-    MsmPoint *scratch = nullptr;
-    const size_t scr = scratch_points(N);
-    if (hipMalloc((void **)&p->xhat, two * sizeof(MsmPoint)) != hipSuccess || hipMalloc((void **)&p->tw_fwd, N * sizeof(GlvTw)) != hipSuccess ||
-        hipMalloc((void **)&p->tw_inv, N * sizeof(GlvTw)) != hipSuccess || hipMalloc((void **)&pw, N * sizeof(Fr)) != hipSuccess ||
-        hipMalloc((void **)&scratch, scr * sizeof(MsmPoint)) != hipSuccess)
-        rc = fail(ctx, KZG_ERR_ALLOC, "hipMalloc(FK20 plan)");
-    if (rc == KZG_OK) rc = glv_table(ctx, st, w, N, pw, p->tw_fwd);
-    if (rc == KZG_OK) rc = glv_table(ctx, st, inv(w), N, pw, p->tw_inv);
-    if (rc == KZG_OK) {
-        KZG_LAUNCH(ctx, st, "k_fk20_load_x", k_fk20_load_x, (unsigned)((two + 255) / 256), 256, 0, monomial->table, monomial->n, N,
-                   p->xhat);
-        rc = g1_dft(ctx, st, p->xhat, two, log_n + 1, 1, p->tw_fwd, 1, true, false, scratch, p->beta);
-    }
-    if (hipStreamSynchronize(st) != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "FK20 plan kernels failed");
-    if (hipGetLastError() != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "FK20 plan kernels failed");
-    if (pw) hipFree(pw);
-    if (scratch) hipFree(scratch);
-    if (ctx->prof) prof_collect(ctx);
-    if (rc != KZG_OK) {
-        fk20_release(p);
-        return rc;
-    }
-    *out = p;
-    return KZG_OK;
-}
-
-extern "C" void kzg_fk20_free(kzg_ctx *ctx, kzg_fk20 *plan) {
-    if (!plan) return;
-    if (ctx) {
-        Guard g(ctx);
-        hipSetDevice(plan->device);
-        hipDeviceSynchronize();
-        fk20_release(plan);
-        return;
-    }
-    hipSetDevice(plan->device);
-    hipDeviceSynchronize();
-    fk20_release(plan);
-}
-
-extern "C" size_t kzg_fk20_domain(const kzg_fk20 *plan) { return plan ? plan->N : 0; }
-
-namespace kzg {
-
-// every witness of `batch` polynomials of n coefficients (eval: N evaluations each), in chunks
-static int fk20_run(kzg_ctx *ctx, const kzg_fk20 *p, const void *in, size_t n, size_t batch, int sfmt, int flags, void *out, int ofmt,
-                    bool eval) {
-    Guard g(ctx);
-    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (sfmt != KZG_FR_MONT_LE_32 && sfmt != KZG_FR_CANONICAL_LE_32) return fail(ctx, KZG_ERR_SHAPE, "unknown scalar format");
-    const size_t psz = point_format_bytes(ofmt);
-    if (!psz) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 output format");
-    if (p->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "FK20 plan resident on another GPU");
-    const size_t N = p->N, two = 2 * N;
-    if (eval && n != N) return fail(ctx, KZG_ERR_SHAPE, "assert!(self.d == evals.d): evaluations must cover the plan's domain");
-    if (n == 0) return fail(ctx, KZG_ERR_SHAPE, "empty polynomial");
-    if (n > N) return fail(ctx, KZG_ERR_SHAPE, "polynomial longer than the plan's domain");
-    if (n - 1 > p->srs_n) return fail(ctx, KZG_ERR_SHAPE, "quotient longer than the SRS (reference: slice index panic)");
-    if (batch == 0) return KZG_OK;
-    if (batch > SIZE_MAX / (N * 144)) return fail(ctx, KZG_ERR_SHAPE, "batch too large");
-    if (!in || !out) return KZG_ERR_SHAPE;
-    const int lane = 0;
-    hipStream_t st = ctx->lanes[lane].stream;
-    const bool out_dev = (flags & KZG_OUT_DEVICE) != 0, in_dev = (flags & KZG_IN_DEVICE) != 0;
-    const uint8_t *src = (const uint8_t *)in;
-    uint8_t *dst = (uint8_t *)out;
-    if (N == 1) {  // every quotient is zero: the identity, as kzg_witness_eval / kzg_witness_coeff_many write it
-        const size_t chunk = std::min(batch, FK20_CHUNK_POINTS);
-        KZG_TRY(lane_reserve(ctx, lane, out_dev ? 4096 : chunk * psz + 4096));
-        for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-            const size_t B = std::min(chunk, batch - b0);
-            uint8_t *d_out = out_dev ? dst + b0 * psz : (uint8_t *)ctx->lanes[lane].arena;
-            KZG_LAUNCH(ctx, st, "k_fk20_emit", k_fk20_emit, (unsigned)std::min<size_t>((B + 63) / 64, 4096), 64, 0, (const MsmPoint *)nullptr,
-                       (size_t)0, 0u, B, d_out, ofmt, psz);
-            if (!out_dev) KZG_HIP_CHECK(ctx, hipMemcpyAsync(dst + b0 * psz, d_out, B * psz, hipMemcpyDeviceToHost, st));
-        }
-        KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        KZG_HIP_CHECK(ctx, hipGetLastError());
-        return KZG_OK;
-    }
-    const uint32_t logn = p->log_n, log2n = logn + 1;
-    const size_t chunk = std::max<size_t>(1, std::min(FK20_MAX_CHUNK, FK20_CHUNK_POINTS / two));
-    const size_t B0 = std::min(chunk, batch);
-    const size_t in_bytes = B0 * n * 32;
-    const size_t scr = scratch_points(B0 * two);
-    size_t need = align_up(B0 * two * sizeof(MsmPoint), 256) + 2 * align_up(B0 * two * 32, 256) + align_up(scr * sizeof(MsmPoint), 256) +
-                  (in_dev ? 0 : align_up(in_bytes, 256)) + (out_dev ? 0 : align_up(B0 * N * psz, 256)) +
-                  ntt_workspace_bytes(log2n) + 65536;
-    KZG_TRY(lane_reserve(ctx, lane, need));
-    MsmPoint *P = (MsmPoint *)lane_alloc(ctx, lane, B0 * two * sizeof(MsmPoint));
-    Fr *y = (Fr *)lane_alloc(ctx, lane, B0 * two * 32);
-    Fr *yh = (Fr *)lane_alloc(ctx, lane, B0 * two * 32);
-    MsmPoint *scratch = (MsmPoint *)lane_alloc(ctx, lane, scr * sizeof(MsmPoint));
-    uint8_t *d_in = in_dev ? nullptr : (uint8_t *)lane_alloc(ctx, lane, in_bytes);
-    uint8_t *d_stage = out_dev ? nullptr : (uint8_t *)lane_alloc(ctx, lane, B0 * N * psz);
-    if (!P || !y || !yh || !scratch || (!in_dev && !d_in) || (!out_dev && !d_stage)) return fail(ctx, KZG_ERR_ALLOC, "workspace");
-    const size_t ntt_mark = ctx->lanes[lane].arena_used;  // every ntt_run below takes its scratch from here (stream-ordered reuse)
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t B = std::min(chunk, batch - b0);
-        const uint8_t *d_src = src + b0 * n * 32;
-        if (!in_dev) {
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_in, d_src, B * n * 32, hipMemcpyHostToDevice, st));
-            d_src = d_in;
-        }
-        const Fr *coeffs = (const Fr *)d_src;
-        int csfmt = sfmt;
-        if (eval) {
-            // iNTT_N of each evaluation vector (Montgomery) into the first N slots of yh, then the coefficients' form is Montgomery
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(yh, d_src, B * N * 32, hipMemcpyDeviceToDevice, st));
-            if (sfmt == KZG_FR_CANONICAL_LE_32) KZG_TRY(fr_convert(ctx, st, yh, B * N, 1));
-            for (size_t b = 0; b < B; b++) {
-                ctx->lanes[lane].arena_used = ntt_mark;
-                KZG_TRY(ntt_run(ctx, lane, yh + b * N, logn, 1));
-            }
-            coeffs = yh;
-            csfmt = KZG_FR_MONT_LE_32;
-        }
-        const unsigned gw = (unsigned)std::min<size_t>((B * two + 255) / 256, 8192);
-        KZG_LAUNCH(ctx, st, "k_fk20_build_y", k_fk20_build_y, gw, 256, 0, coeffs, n, N, B, csfmt, y);
-        for (size_t b = 0; b < B; b++) {
-            ctx->lanes[lane].arena_used = ntt_mark;
-            KZG_TRY(ntt_run(ctx, lane, y + b * two, log2n, 0));
-        }
-        KZG_LAUNCH(ctx, st, "k_fk20_scale_brev", k_fk20_scale_brev, gw, 256, 0, y, log2n, p->inv2n, B, yh);
-        KZG_LAUNCH(ctx, st, "k_fk20_pointwise", k_fk20_pointwise, grid_for(B * two, 256), 256, 0, P, p->xhat, yh, two, B, scratch, p->beta);
-        KZG_TRY(g1_dft(ctx, st, P, two, log2n, B, p->tw_inv, 1, false, true, scratch, p->beta));  // H = iDFT_2N, first half
-        KZG_TRY(g1_dft(ctx, st, P, two, logn, B, p->tw_fwd, 2, true, false, scratch, p->beta));   // pi = DFT_N(H), bit-reversed
-        uint8_t *d_out = out_dev ? dst + b0 * N * psz : d_stage;
-        KZG_LAUNCH(ctx, st, "k_fk20_emit", k_fk20_emit, (unsigned)std::min<size_t>((B * N + 63) / 64, 16384), 64, 0, (const MsmPoint *)P,
-                   two, logn, B, d_out, ofmt, psz);
-        if (!out_dev) KZG_HIP_CHECK(ctx, hipMemcpyAsync(dst + b0 * N * psz, d_stage, B * N * psz, hipMemcpyDeviceToHost, st));
-    }
-    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    KZG_HIP_CHECK(ctx, hipGetLastError());
-    if (ctx->prof) prof_collect(ctx);
-    return KZG_OK;
-}
-
-}  // namespace kzg
-
-extern "C" int kzg_witness_all_coeff(kzg_ctx *ctx, const kzg_fk20 *plan, const void *coeffs, size_t n, size_t batch, int sfmt,
-                                     int flags, void *out, int ofmt) {
-    if (!ctx || !plan) return KZG_ERR_SHAPE;
-    return fk20_run(ctx, plan, coeffs, n, batch, sfmt, flags, out, ofmt, false);
-}
-
-extern "C" int kzg_witness_all_eval(kzg_ctx *ctx, const kzg_fk20 *plan, const void *evals, size_t d, size_t batch, int sfmt,
-                                    int flags, void *out, int ofmt) {
-    if (!ctx || !plan) return KZG_ERR_SHAPE;
-    return fk20_run(ctx, plan, evals, d, batch, sfmt, flags, out, ofmt, true);
-}
-
 // ---- multi-point FK20: every coset opening ------------------------------------------------------------------------------
 // Coset size l = 2^j, K = N / l cosets, C_i = { w^(i + tK) : t < l }, Z_i = X^l - w^(il) (w^l = w_K).  With the residue split
 // c^(r)_t = c_{r + tl}, s^(r)_v = s_{r + vl} (r < l), the witness of coset i is pi_i = DFT_K(h)_i with h = sum_r h^(r) and
@@ -407,18 +218,8 @@ extern "C" int kzg_witness_all_eval(kzg_ctx *ctx, const kzg_fk20 *plan, const vo
 // frequency over the signed 4-bit digits of all its terms (Straus): 256 doublings for the whole sum plus ~60 mixed additions per
 // term.  The per-term route (option "fk20_cosets_combine" = 1) runs mul256 on every term -- 256 doublings, the table build and
 // ~60 additions each -- and is kept for comparison.  Both split the residues into S slices whose partial sums k_coset_reduce adds.
-namespace kzg {
 
 constexpr size_t COSET_TARGET_THREADS = (size_t)1 << 17;  // combination threads per chunk the slicing aims for
-
-// X[r][j] = x^(r)_j = s_{r + (K-2-j) l} (j <= K-2 and inside the SRS), O otherwise; r < l, j < 2K
-__global__ __launch_bounds__(256) void k_coset_load_x(const G1Affine *srs, size_t srs_n, size_t K, size_t l, MsmPoint *X) {
-    const size_t two = 2 * K, u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= l * two) return;
-    const size_t r = u / two, j = u % two;
-    const bool in = j + 2 <= K && r + (K - 2 - j) * l < srs_n;
-    X[u] = in ? g1_from_affine30(g1_affine_to30(srs[r + (K - 2 - j) * l]), false) : MsmPoint::infinity();
-}
 
 // tab[e * count + u] = (e + 1) X[u] in affine 30-bit form, e < 8 (the identity: all limbs zero)
 __global__ __launch_bounds__(256) void k_coset_table(const MsmPoint *X, size_t count, G1Affine30 *tab) {
@@ -432,23 +233,6 @@ __global__ __launch_bounds__(256) void k_coset_table(const MsmPoint *X, size_t c
             else if (e > 1) Q = g1_add30(Q, P);  // (e + 1) P != e P: the group has prime order
             tab[(size_t)e * count + u] = g1_affine_to30(g1_to_affine(g1_xyzz_from30(Q)));
         }
-    }
-}
-
-// y[(b l + r) 2K + t] = y^(r)_t of polynomial b, from n coefficients per polynomial (stride n) in sfmt; Montgomery out
-__global__ __launch_bounds__(256) void k_coset_build_y(const Fr *c, size_t n, size_t K, size_t l, size_t batch, int sfmt, Fr *y) {
-    const size_t nt = (size_t)gridDim.x * blockDim.x;
-    const size_t two = 2 * K, work = batch * l * two;
-    for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < work; u += nt) {
-        const size_t a = u / two, t = u % two, b = a / l, r = a % l;
-        const bool has = t == 0 || t > K;
-        const size_t ci = r + (t == 0 ? K - 1 : t - K - 1) * l;
-        Fr v = Fr::zero();
-        if (has && ci < n) {
-            v = c[b * n + ci];
-            if (sfmt == KZG_FR_CANONICAL_LE_32) v = to_mont(v);
-        }
-        y[u] = v;
     }
 }
 
@@ -578,36 +362,46 @@ static int coset_combine(kzg_ctx *ctx, hipStream_t st, int route, const G1Affine
 
 }  // namespace kzg
 
-struct kzg_fk20_cosets {
+using namespace kzg;
+
+// ---- plans -------------------------------------------------------------------------------------------------------------------
+// One representation for both plan kinds: a single-point plan is the l = 1, K = N case and keeps the DFT output Xh itself
+// (k_fk20_pointwise); a coset plan keeps the affine multiples of Xh (k_coset_straus / k_coset_perterm).  `device` stays the first
+// field.  The two public types are distinct and opaque (include/kzg_mi355x.h).
+struct Fk20Plan {
     int device = 0;
     uint32_t log_n = 0, log_l = 0;
     size_t N = 0, l = 0, K = 0;
     size_t srs_n = 0;               // length of the monomial SRS the plan was built from
-    G1Affine30 *tab = nullptr;      // (e + 1) Xh^(r)_j at tab[(e l + r) 2K + j], e < 8: 8 x 2N rows of 128 B
+    MsmPoint *xhat = nullptr;       // single-point: DFT_2N(x), bit-reversed (2N points)
+    G1Affine30 *tab = nullptr;      // cosets: (e + 1) Xh^(r)_j at tab[(e l + r) 2K + j], e < 8: 8 x 2N rows of 128 B
     GlvTw *tw_fwd = nullptr;        // w_2K^e, e < K
     GlvTw *tw_inv = nullptr;        // w_2K^-e, e < K
     Fr inv2k;                       // 1 / 2K, Montgomery
     Fq30 beta;
+    ~Fk20Plan() {  // on the plan's device, with nothing of the plan in flight
+        if (xhat) hipFree(xhat);
+        if (tab) hipFree(tab);
+        if (tw_fwd) hipFree(tw_fwd);
+        if (tw_inv) hipFree(tw_inv);
+    }
 };
+struct kzg_fk20 : Fk20Plan {};
+struct kzg_fk20_cosets : Fk20Plan {};
 
-static void cosets_release(kzg_fk20_cosets *p) {
-    if (!p) return;
-    if (p->tab) hipFree(p->tab);
-    if (p->tw_fwd) hipFree(p->tw_fwd);
-    if (p->tw_inv) hipFree(p->tw_inv);
-    delete p;
-}
+namespace kzg {
 
-extern "C" int kzg_fk20_cosets_setup(kzg_ctx *ctx, const kzg_srs *monomial, uint32_t log_n, uint32_t log_l, kzg_fk20_cosets **out) {
-    if (!ctx || !monomial || !out) return KZG_ERR_SHAPE;
+// fills *p for `who` (the entry point, named in its error texts); table: a coset plan (log_l >= 1), else log_l = 0
+static int fk20_build(kzg_ctx *ctx, const kzg_srs *monomial, uint32_t log_n, uint32_t log_l, bool table, const std::string &who,
+                      Fk20Plan *p) {
     Guard g(ctx);
     KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if (monomial->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "SRS resident on another GPU");
     if (log_n + 1 >= FR_TWO_ADICITY) return fail(ctx, KZG_ERR_DEGREE_TOO_LARGE, "domain too large");
-    if (log_n > FK20_MAX_LOG) return fail(ctx, KZG_ERR_SHAPE, "kzg_fk20_cosets_setup: log_n <= 22 (documented limit)");
-    if (log_l == 0) return fail(ctx, KZG_ERR_SHAPE, "kzg_fk20_cosets_setup: log_l >= 1 (single points: kzg_fk20_setup)");
-    if (log_l > log_n) return fail(ctx, KZG_ERR_SHAPE, "kzg_fk20_cosets_setup: coset larger than the domain");
-    kzg_fk20_cosets *p = new kzg_fk20_cosets();
+    if (log_n > FK20_MAX_LOG) return fail(ctx, KZG_ERR_SHAPE, who + ": log_n <= 22 (documented limit)");
+    if (table && log_l == 0) return fail(ctx, KZG_ERR_SHAPE, who + ": log_l >= 1 (single points: kzg_fk20_setup)");
+    if (log_l > log_n) return fail(ctx, KZG_ERR_SHAPE, who + ": coset larger than the domain");
+    const std::string what = table ? "FK20 coset plan" : "FK20 plan";
     p->device = ctx->device;
     p->log_n = log_n;
     p->log_l = log_l;
@@ -618,72 +412,80 @@ extern "C" int kzg_fk20_cosets_setup(kzg_ctx *ctx, const kzg_srs *monomial, uint
     p->beta = beta30();
     const size_t K = p->K, two = 2 * K, rows = 2 * p->N;  // l arrays of 2K
     const uint32_t logk = log_n - log_l;
-    const Fr w = host_omega(logk + 1);  // w_2K, w_2K^2 = w_K = w_N^l
+    const Fr w = host_omega(logk + 1);  // w_2K, w_2K^2 = w_K = w_N^l (l = 1: compute_omega(N).omega)
     p->inv2k = inv(from_u64<FrParams>((uint64_t)two));
     hipStream_t st = ctx->lanes[0].stream;
     int rc = KZG_OK;
     Fr *pw = nullptr;
     MsmPoint *X = nullptr, *scratch = nullptr;
     const size_t scr = scratch_points(p->l * K);
-    if (hipMalloc((void **)&p->tab, G1NTT_TAB * rows * sizeof(G1Affine30)) != hipSuccess ||
+    if ((table && hipMalloc((void **)&p->tab, G1NTT_TAB * rows * sizeof(G1Affine30)) != hipSuccess) ||
         hipMalloc((void **)&p->tw_fwd, K * sizeof(GlvTw)) != hipSuccess || hipMalloc((void **)&p->tw_inv, K * sizeof(GlvTw)) != hipSuccess ||
         hipMalloc((void **)&pw, K * sizeof(Fr)) != hipSuccess || hipMalloc((void **)&X, rows * sizeof(MsmPoint)) != hipSuccess ||
         hipMalloc((void **)&scratch, scr * sizeof(MsmPoint)) != hipSuccess)
-        rc = fail(ctx, KZG_ERR_ALLOC, "hipMalloc(FK20 coset plan)");
+        rc = fail(ctx, KZG_ERR_ALLOC, "hipMalloc(" + what + ")");
     if (rc == KZG_OK) rc = glv_table(ctx, st, w, K, pw, p->tw_fwd);
     if (rc == KZG_OK) rc = glv_table(ctx, st, inv(w), K, pw, p->tw_inv);
     if (rc == KZG_OK) {
-        KZG_LAUNCH(ctx, st, "k_coset_load_x", k_coset_load_x, (unsigned)((rows + 255) / 256), 256, 0, monomial->table, monomial->n, K,
-                   p->l, X);
+        KZG_LAUNCH(ctx, st, "k_fk20_load_x", k_fk20_load_x, (unsigned)((rows + 255) / 256), 256, 0, monomial->table, monomial->n, K, p->l, X);
         rc = g1_dft(ctx, st, X, two, logk + 1, p->l, p->tw_fwd, 1, true, false, scratch, p->beta);
     }
-    if (rc == KZG_OK) KZG_LAUNCH(ctx, st, "k_coset_table", k_coset_table, grid_for(rows, 256), 256, 0, (const MsmPoint *)X, rows, p->tab);
-    if (hipStreamSynchronize(st) != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "FK20 coset plan kernels failed");
-    if (hipGetLastError() != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "FK20 coset plan kernels failed");
+    if (rc == KZG_OK && table)
+        KZG_LAUNCH(ctx, st, "k_coset_table", k_coset_table, grid_for(rows, 256), 256, 0, (const MsmPoint *)X, rows, p->tab);
+    if (hipStreamSynchronize(st) != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, what + " kernels failed");
+    if (hipGetLastError() != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, what + " kernels failed");
+    if (!table && rc == KZG_OK) std::swap(p->xhat, X);  // the DFT output is the single-point plan
     if (pw) hipFree(pw);
     if (X) hipFree(X);
     if (scratch) hipFree(scratch);
     if (ctx->prof) prof_collect(ctx);
+    return rc;
+}
+
+template <class Plan>
+static int fk20_setup(kzg_ctx *ctx, const kzg_srs *monomial, uint32_t log_n, uint32_t log_l, bool table, const char *who, Plan **out) {
+    if (!ctx || !monomial || !out) return KZG_ERR_SHAPE;
+    Plan *p = new Plan();
+    const int rc = fk20_build(ctx, monomial, log_n, log_l, table, who, p);
     if (rc != KZG_OK) {
-        cosets_release(p);
+        delete p;
         return rc;
     }
     *out = p;
     return KZG_OK;
 }
 
-extern "C" void kzg_fk20_cosets_free(kzg_ctx *ctx, kzg_fk20_cosets *plan) {
+template <class Plan>
+static void fk20_free(kzg_ctx *ctx, Plan *plan) {
     if (!plan) return;
-    if (ctx) {
-        Guard g(ctx);
-        hipSetDevice(plan->device);
-        hipDeviceSynchronize();
-        cosets_release(plan);
-        return;
-    }
+    std::optional<Guard> g;
+    if (ctx) g.emplace(ctx);
     hipSetDevice(plan->device);
     hipDeviceSynchronize();
-    cosets_release(plan);
+    delete plan;
 }
 
-extern "C" int kzg_fk20_cosets_shape(const kzg_fk20_cosets *plan, size_t *domain, size_t *coset_size) {
-    if (!plan) return KZG_ERR_SHAPE;
-    if (domain) *domain = plan->N;
-    if (coset_size) *coset_size = plan->l;
+// `count` Fr transforms of 2^logd points, transform i at d + i * stride.  Each ntt_run takes its scratch from the arena mark again:
+// the transforms are ordered on the lane's stream, so the next one may reuse what the previous one was given
+static int ntt_each(kzg_ctx *ctx, int lane, size_t mark, Fr *d, size_t stride, size_t count, uint32_t logd, int inverse) {
+    for (size_t i = 0; i < count; i++) {
+        ctx->lanes[lane].arena_used = mark;
+        KZG_TRY(ntt_run(ctx, lane, d + i * stride, logd, inverse));
+    }
     return KZG_OK;
 }
 
-namespace kzg {
-
-// every coset witness (and optionally every interpolant) of `batch` polynomials of n coefficients (eval: N evaluations), in chunks
-static int cosets_run(kzg_ctx *ctx, const kzg_fk20_cosets *p, const void *in, size_t n, size_t batch, int sfmt, int flags, void *out_w,
-                      int ofmt, void *out_r, bool eval) {
+// every witness (and, for a coset plan, optionally every interpolant: out_r) of `batch` polynomials of n coefficients (eval: N
+// evaluations each), in chunks.  Behind kzg_witness_all_* (l = 1, out_r null) and kzg_witness_cosets_*.
+static int fk20_run(kzg_ctx *ctx, const Fk20Plan *p, const void *in, size_t n, size_t batch, int sfmt, int flags, void *out_w, int ofmt,
+                    void *out_r, bool eval) {
+    if (!ctx || !p) return KZG_ERR_SHAPE;
     Guard g(ctx);
     KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if (sfmt != KZG_FR_MONT_LE_32 && sfmt != KZG_FR_CANONICAL_LE_32) return fail(ctx, KZG_ERR_SHAPE, "unknown scalar format");
     const size_t psz = point_format_bytes(ofmt);
     if (!psz) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 output format");
-    if (p->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "FK20 coset plan resident on another GPU");
+    if (p->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, p->tab ? "FK20 coset plan resident on another GPU" : "FK20 plan resident on another GPU");
     const size_t N = p->N, l = p->l, K = p->K, two = 2 * K;
     if (eval && n != N) return fail(ctx, KZG_ERR_SHAPE, "assert!(self.d == evals.d): evaluations must cover the plan's domain");
     if (n == 0) return fail(ctx, KZG_ERR_SHAPE, "empty polynomial");
@@ -696,10 +498,25 @@ static int cosets_run(kzg_ctx *ctx, const kzg_fk20_cosets *p, const void *in, si
     hipStream_t st = ctx->lanes[lane].stream;
     const bool out_dev = (flags & KZG_OUT_DEVICE) != 0, in_dev = (flags & KZG_IN_DEVICE) != 0, want_r = out_r != nullptr;
     const uint8_t *src = (const uint8_t *)in;
+    uint8_t *dst = (uint8_t *)out_w;
+    if (N == 1) {  // every quotient is zero: the identity, as kzg_witness_eval / kzg_witness_coeff_many write it (single-point plans only)
+        const size_t chunk = std::min(batch, FK20_CHUNK_POINTS);
+        KZG_TRY(lane_reserve(ctx, lane, out_dev ? 4096 : chunk * psz + 4096));
+        for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+            const size_t B = std::min(chunk, batch - b0);
+            uint8_t *d_out = out_dev ? dst + b0 * psz : (uint8_t *)ctx->lanes[lane].arena;
+            KZG_LAUNCH(ctx, st, "k_fk20_emit", k_fk20_emit, (unsigned)std::min<size_t>((B + 63) / 64, 4096), 64, 0, (const MsmPoint *)nullptr,
+                       (size_t)0, 0u, B, d_out, ofmt, psz);
+            if (!out_dev) KZG_HIP_CHECK(ctx, hipMemcpyAsync(dst + b0 * psz, d_out, B * psz, hipMemcpyDeviceToHost, st));
+        }
+        KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        KZG_HIP_CHECK(ctx, hipGetLastError());
+        return KZG_OK;
+    }
     const uint32_t logn = p->log_n, logk = logn - p->log_l;
     const size_t chunk = std::max<size_t>(1, std::min(FK20_MAX_CHUNK, FK20_CHUNK_POINTS / (2 * N)));
     const size_t B0 = std::min(chunk, batch);
-    const size_t S = coset_slices(l, two, B0);
+    const size_t S = coset_slices(l, two, B0);  // from the first chunk, kept for the ragged last one
     const int route = ctx->opt_fk20_cosets_combine;
     const size_t in_bytes = B0 * n * 32;
     const size_t scr = scratch_points(B0 * S * two);
@@ -718,7 +535,7 @@ static int cosets_run(kzg_ctx *ctx, const kzg_fk20_cosets *p, const void *in, si
     uint8_t *d_stage_r = (out_dev || !want_r) ? nullptr : (uint8_t *)lane_alloc(ctx, lane, B0 * N * 32);
     if (!P || !y || !yh || !scratch || (want_r && !z) || (!in_dev && !d_in) || (!out_dev && !d_stage) || (!out_dev && want_r && !d_stage_r))
         return fail(ctx, KZG_ERR_ALLOC, "workspace");
-    const size_t ntt_mark = ctx->lanes[lane].arena_used;  // every ntt_run below takes its scratch from here (stream-ordered reuse)
+    const size_t ntt_mark = ctx->lanes[lane].arena_used;  // the scratch of every ntt_each below
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t B = std::min(chunk, batch - b0);
         const uint8_t *d_src = src + b0 * n * 32;
@@ -731,40 +548,34 @@ static int cosets_run(kzg_ctx *ctx, const kzg_fk20_cosets *p, const void *in, si
         if (eval) {  // iNTT_N of each evaluation vector (Montgomery) into yh, which the coefficients' only readers precede
             KZG_HIP_CHECK(ctx, hipMemcpyAsync(yh, d_src, B * N * 32, hipMemcpyDeviceToDevice, st));
             if (sfmt == KZG_FR_CANONICAL_LE_32) KZG_TRY(fr_convert(ctx, st, yh, B * N, 1));
-            for (size_t b = 0; b < B; b++) {
-                ctx->lanes[lane].arena_used = ntt_mark;
-                KZG_TRY(ntt_run(ctx, lane, yh + b * N, logn, 1));
-            }
+            KZG_TRY(ntt_each(ctx, lane, ntt_mark, yh, N, B, logn, 1));
             coeffs = yh;
             csfmt = KZG_FR_MONT_LE_32;
         }
         const unsigned gw = (unsigned)std::min<size_t>((B * 2 * N + 255) / 256, 8192);
         if (want_r) {  // interpolants: DFT_K of every residue class, then transposed into coset-major order
             KZG_LAUNCH(ctx, st, "k_coset_gather_r", k_coset_gather_r, gw, 256, 0, coeffs, n, K, l, B, csfmt, z);
-            if (logk)
-                for (size_t a = 0; a < B * l; a++) {
-                    ctx->lanes[lane].arena_used = ntt_mark;
-                    KZG_TRY(ntt_run(ctx, lane, z + a * K, logk, 0));
-                }
+            if (logk) KZG_TRY(ntt_each(ctx, lane, ntt_mark, z, K, B * l, logk, 0));
             Fr *d_r = out_dev ? (Fr *)((uint8_t *)out_r + b0 * N * 32) : (Fr *)d_stage_r;
             KZG_LAUNCH(ctx, st, "k_coset_emit_r", k_coset_emit_r, gw, 256, 0, (const Fr *)z, K, l, B, sfmt, d_r);
             if (!out_dev)
                 KZG_HIP_CHECK(ctx, hipMemcpyAsync((uint8_t *)out_r + b0 * N * 32, d_stage_r, B * N * 32, hipMemcpyDeviceToHost, st));
         }
-        KZG_LAUNCH(ctx, st, "k_coset_build_y", k_coset_build_y, gw, 256, 0, coeffs, n, K, l, B, csfmt, y);
-        for (size_t a = 0; a < B * l; a++) {
-            ctx->lanes[lane].arena_used = ntt_mark;
-            KZG_TRY(ntt_run(ctx, lane, y + a * two, logk + 1, 0));
-        }
+        KZG_LAUNCH(ctx, st, "k_fk20_build_y", k_fk20_build_y, gw, 256, 0, coeffs, n, K, l, B, csfmt, y);
+        KZG_TRY(ntt_each(ctx, lane, ntt_mark, y, two, B * l, logk + 1, 0));
         KZG_LAUNCH(ctx, st, "k_fk20_scale_brev", k_fk20_scale_brev, gw, 256, 0, y, logk + 1, p->inv2k, B * l, yh);
-        KZG_LAUNCH(ctx, st, "k_coset_recode", k_coset_recode, gw, 256, 0, (const Fr *)yh, B * l, two, (uint32_t *)y);
-        KZG_TRY(coset_combine(ctx, st, route, p->tab, l, two, (const uint32_t *)y, B, S, P, scratch, p->beta));
+        if (p->tab) {  // hh_j = sum_r yh^(r)_j Xh^(r)_j over the plan's table
+            KZG_LAUNCH(ctx, st, "k_coset_recode", k_coset_recode, gw, 256, 0, (const Fr *)yh, B * l, two, (uint32_t *)y);
+            KZG_TRY(coset_combine(ctx, st, route, p->tab, l, two, (const uint32_t *)y, B, S, P, scratch, p->beta));
+        } else {  // Hh_j = yh_j Xh_j
+            KZG_LAUNCH(ctx, st, "k_fk20_pointwise", k_fk20_pointwise, grid_for(B * two, 256), 256, 0, P, p->xhat, yh, two, B, scratch, p->beta);
+        }
         KZG_TRY(g1_dft(ctx, st, P, S * two, logk + 1, B, p->tw_inv, 1, false, true, scratch, p->beta));  // h = iDFT_2K, first half
         KZG_TRY(g1_dft(ctx, st, P, S * two, logk, B, p->tw_fwd, 2, true, false, scratch, p->beta));      // pi = DFT_K(h), bit-reversed
-        uint8_t *d_out = out_dev ? (uint8_t *)out_w + b0 * K * psz : d_stage;
+        uint8_t *d_out = out_dev ? dst + b0 * K * psz : d_stage;
         KZG_LAUNCH(ctx, st, "k_fk20_emit", k_fk20_emit, (unsigned)std::min<size_t>((B * K + 63) / 64, 16384), 64, 0, (const MsmPoint *)P,
                    S * two, logk, B, d_out, ofmt, psz);
-        if (!out_dev) KZG_HIP_CHECK(ctx, hipMemcpyAsync((uint8_t *)out_w + b0 * K * psz, d_stage, B * K * psz, hipMemcpyDeviceToHost, st));
+        if (!out_dev) KZG_HIP_CHECK(ctx, hipMemcpyAsync(dst + b0 * K * psz, d_stage, B * K * psz, hipMemcpyDeviceToHost, st));
     }
     KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
     KZG_HIP_CHECK(ctx, hipGetLastError());
@@ -774,16 +585,121 @@ static int cosets_run(kzg_ctx *ctx, const kzg_fk20_cosets *p, const void *in, si
 
 }  // namespace kzg
 
+extern "C" int kzg_fk20_setup(kzg_ctx *ctx, const kzg_srs *monomial, uint32_t log_n, kzg_fk20 **out) {
+    return fk20_setup(ctx, monomial, log_n, 0, false, "kzg_fk20_setup", out);
+}
+
+extern "C" int kzg_fk20_cosets_setup(kzg_ctx *ctx, const kzg_srs *monomial, uint32_t log_n, uint32_t log_l, kzg_fk20_cosets **out) {
+    return fk20_setup(ctx, monomial, log_n, log_l, true, "kzg_fk20_cosets_setup", out);
+}
+
+extern "C" void kzg_fk20_free(kzg_ctx *ctx, kzg_fk20 *plan) { fk20_free(ctx, plan); }
+
+extern "C" void kzg_fk20_cosets_free(kzg_ctx *ctx, kzg_fk20_cosets *plan) { fk20_free(ctx, plan); }
+
+extern "C" size_t kzg_fk20_domain(const kzg_fk20 *plan) { return plan ? plan->N : 0; }
+
+extern "C" int kzg_fk20_cosets_shape(const kzg_fk20_cosets *plan, size_t *domain, size_t *coset_size) {
+    if (!plan) return KZG_ERR_SHAPE;
+    if (domain) *domain = plan->N;
+    if (coset_size) *coset_size = plan->l;
+    return KZG_OK;
+}
+
+extern "C" int kzg_witness_all_coeff(kzg_ctx *ctx, const kzg_fk20 *plan, const void *coeffs, size_t n, size_t batch, int sfmt,
+                                     int flags, void *out, int ofmt) {
+    return fk20_run(ctx, plan, coeffs, n, batch, sfmt, flags, out, ofmt, nullptr, false);
+}
+
+extern "C" int kzg_witness_all_eval(kzg_ctx *ctx, const kzg_fk20 *plan, const void *evals, size_t d, size_t batch, int sfmt,
+                                    int flags, void *out, int ofmt) {
+    return fk20_run(ctx, plan, evals, d, batch, sfmt, flags, out, ofmt, nullptr, true);
+}
+
 extern "C" int kzg_witness_cosets_coeff(kzg_ctx *ctx, const kzg_fk20_cosets *plan, const void *coeffs, size_t n, size_t batch, int sfmt,
                                         int flags, void *out_w, int ofmt, void *out_r) {
-    if (!ctx || !plan) return KZG_ERR_SHAPE;
-    return cosets_run(ctx, plan, coeffs, n, batch, sfmt, flags, out_w, ofmt, out_r, false);
+    return fk20_run(ctx, plan, coeffs, n, batch, sfmt, flags, out_w, ofmt, out_r, false);
 }
 
 extern "C" int kzg_witness_cosets_eval(kzg_ctx *ctx, const kzg_fk20_cosets *plan, const void *evals, size_t d, size_t batch, int sfmt,
                                        int flags, void *out_w, int ofmt, void *out_r) {
-    if (!ctx || !plan) return KZG_ERR_SHAPE;
-    return cosets_run(ctx, plan, evals, d, batch, sfmt, flags, out_w, ofmt, out_r, true);
+    return fk20_run(ctx, plan, evals, d, batch, sfmt, flags, out_w, ofmt, out_r, true);
+}
+
+// ---- compute_lagrange_basis (src/eval_form.rs:254-280), G1 half, from the monomial SRS alone (no secret) ------------------------
+// lagrange_basis_g[i] = commit(l_i) with l_i(X) = (1/d) sum_j w^(-ij) X^j: L = (1/d) DFT_d(gs) with the inverse twiddles, i.e.
+// g1_dft as a DIF over w^-1 (natural in, bit-reversed out) and the 1/d product in the kernel that reads it out.  The reference
+// builds every l_i by d - 1 polynomial multiplications and commits to it (O(d^3) field work); a ceremony SRS has no tau, so the
+// eval-form path at 2^20 needs this transform.  Untimed input generation.
+namespace kzg {
+
+__global__ __launch_bounds__(256) void k_affine_to_msm_points(const G1Affine *in, MsmPoint *out, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = g1_from_affine30(g1_affine_to30(in[i]), false);
+}
+
+// out[i] = [dinv] P[brev(i)] in the canonical XYZZ form (dinv: canonical 1 / d; d == 1: L_0 = gs[0], no product)
+__global__ __launch_bounds__(256) void k_lagrange_finish(const MsmPoint *P, size_t d, uint32_t bits, Fr dinv, MsmPoint *scratch,
+                                                         Fq30 beta, G1Xyzz *out) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (size_t i = tid; i < d; i += nt) {
+        MsmPoint Q = P[brev(i, bits)];
+        if (d > 1) Q = mul256(Q, dinv, scratch + tid, nt, beta);
+        out[i] = g1_xyzz_from30(Q);
+    }
+}
+
+}  // namespace kzg
+
+extern "C" int kzg_srs_lagrange_from_monomial_g1(kzg_ctx *ctx, const kzg_srs *mono, kzg_srs **out) {
+    if (!ctx || !mono || !out) return KZG_ERR_SHAPE;
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const size_t d = mono->n;
+    if (d == 0 || (d & (d - 1))) return fail(ctx, KZG_ERR_SHAPE, "assert!(d & (d - 1) == 0) (src/eval_form.rs:255-256)");
+    const uint32_t exp = (uint32_t)ilog2_ceil(d);
+    if (exp >= FR_TWO_ADICITY) return fail(ctx, KZG_ERR_DEGREE_TOO_LARGE, "domain too large");
+    if (exp > 24) return fail(ctx, KZG_ERR_SHAPE, "compute_lagrange_basis on the GPU is limited to d <= 2^24 (documented limit)");
+    hipStream_t st = ctx->lanes[0].stream;
+    kzg_srs *s = nullptr;
+    KZG_TRY(srs_alloc(ctx, d, &s));
+    MsmPoint *P = nullptr, *scratch = nullptr;
+    G1Xyzz *rows = nullptr;
+    Fr *pw = nullptr;
+    GlvTw *tw = nullptr;
+    int rc = KZG_OK;
+    const size_t half = d > 1 ? d / 2 : 1;
+    const size_t scr = scratch_points(d);  // the read-out's d threads; the stages have d / 2 butterflies
+    if (hipMalloc((void **)&P, d * sizeof(MsmPoint)) != hipSuccess || hipMalloc((void **)&rows, d * sizeof(G1Xyzz)) != hipSuccess ||
+        hipMalloc((void **)&scratch, scr * sizeof(MsmPoint)) != hipSuccess || hipMalloc((void **)&pw, half * sizeof(Fr)) != hipSuccess ||
+        hipMalloc((void **)&tw, half * sizeof(GlvTw)) != hipSuccess)
+        rc = fail(ctx, KZG_ERR_ALLOC, "hipMalloc(group-FFT workspace)");
+    if (rc == KZG_OK) {
+        const Fq30 beta = beta30();
+        const Fr dinv = from_mont(inv(from_u64<FrParams>((uint64_t)d)));  // canonical
+        KZG_LAUNCH(ctx, st, "k_affine_to_msm_points", k_affine_to_msm_points, (unsigned)((d + 255) / 256), 256, 0, mono->table, P, d);
+        rc = glv_table(ctx, st, inv(host_omega(exp)), half, pw, tw);
+        if (rc == KZG_OK) rc = g1_dft(ctx, st, P, d, exp, 1, tw, 1, true, false, scratch, beta);
+        if (rc == KZG_OK) {
+            KZG_LAUNCH(ctx, st, "k_lagrange_finish", k_lagrange_finish, grid_for(d, 256), 256, 0, (const MsmPoint *)P, d, exp, dinv, scratch,
+                       beta, rows);
+            rc = srs_finish_from_xyzz(ctx, s, rows);
+        }
+    }
+    hipStreamSynchronize(st);
+    if (hipGetLastError() != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "group FFT kernels failed");
+    if (P) hipFree(P);
+    if (rows) hipFree(rows);
+    if (scratch) hipFree(scratch);
+    if (pw) hipFree(pw);
+    if (tw) hipFree(tw);
+    if (rc != KZG_OK) {
+        kzg_srs_free(nullptr, s);
+        return rc;
+    }
+    *out = s;
+    return KZG_OK;
 }
 
 #ifdef KZG_TEST_HOOKS

@@ -57,13 +57,14 @@ def fk20_model(coeffs, N, tau, srs_len=None):
 
 
 def chunk_size(N):
-    """Polynomials per chunk of fk20_run and cosets_run in g1ntt.hip: max(1, min(FK20_MAX_CHUNK, FK20_CHUNK_POINTS / 2N))."""
+    """Polynomials per chunk of fk20_run in g1ntt.hip (single-point and coset calls alike):
+    max(1, min(FK20_MAX_CHUNK, FK20_CHUNK_POINTS / 2N))."""
     return max(1, min(4096, (1 << 21) // (2 * N)))
 
 
 def coset_slices(l, two, batch):
     """Residue slices of a coset combination over `batch` x two frequencies (g1ntt.hip coset_slices, COSET_TARGET_THREADS
-    = 2^17).  cosets_run takes S from its first chunk and keeps it for the ragged last one."""
+    = 2^17).  fk20_run takes S from its first chunk and keeps it for the ragged last one."""
     S = 1
     while S < l and batch * S * two < (1 << 17):
         S *= 2

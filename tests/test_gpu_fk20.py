@@ -14,72 +14,16 @@ from kzg_amd.api import _raise, pack_scalars
 from oracle import c_oracle as C
 from oracle import kzg_model as M
 from tests import fk20_model as F
-from tests.gpu_common import HooksEngine, rand_scalars
+from tests.fk20_common import FORMATS, MONT_R, SIZE_MAX, VP, I32, G, dev_buffer, dev_download, same_point, split
+from tests.fk20_common import eng, hooks, params, plans  # noqa: F401 -- this module's fixtures
+from tests.gpu_common import rand_scalars
 
 pytestmark = pytest.mark.gpu
 
 TAU = 0x5EED_F20
 SRS_LEN = 1 << 12
-VP, SZ, I32, U32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32
-FORMATS = [L.G1_AFFINE_MONT, L.G1_JACOBIAN_MONT, L.G1_ZCASH_UNCOMPRESSED, L.G1_ZCASH_COMPRESSED]
-MONT_R = pow(2, 256, M.R)
-SIZE_MAX = ctypes.c_size_t(-1).value
-
-
-@pytest.fixture(scope="module")
-def eng():
-    e = kzg_amd.Engine(0)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def hooks():
-    h = HooksEngine(0)
-    h.lib.kzg_test_g1_mul_glv.argtypes = [VP, VP, VP, SZ, VP]
-    h.lib.kzg_test_g1_mul_glv.restype = I32
-    h.lib.kzg_test_g1_ntt.argtypes = [VP, VP, U32, I32, VP]
-    h.lib.kzg_test_g1_ntt.restype = I32
-    yield h
-    h.close()
-
-
-@pytest.fixture(scope="module")
-def params(eng):
-    p = kzg_amd.setup(eng, TAU, SRS_LEN, g2_len=2)
-    yield p
-    p.gs.free()
-    if p.hs is not None:
-        p.hs.free()
-
-
-@pytest.fixture(scope="module")
-def plans(eng, params):
-    cache = {}
-
-    def get(log_n):
-        if log_n not in cache:
-            cache[log_n] = kzg_amd.FK20Plan(eng, params.gs, log_n)
-        return cache[log_n]
-    yield get
-    for p in cache.values():
-        p.free()
-
-
-def G():
-    return C.g1_generator()
-
-
-def same_point(a, b, fmt):
-    """byte equality; the Jacobian form is not canonical, so there the projective coordinates are compared"""
-    if fmt != L.G1_JACOBIAN_MONT:
-        return a == b
-    q = M.Q
-    X1, Y1, Z1 = (int.from_bytes(a[i:i + 48], "little") for i in (0, 48, 96))
-    X2, Y2, Z2 = (int.from_bytes(b[i:i + 48], "little") for i in (0, 48, 96))
-    if Z1 % q == 0 or Z2 % q == 0:
-        return Z1 % q == 0 and Z2 % q == 0
-    return (X1 * Z2 * Z2 - X2 * Z1 * Z1) % q == 0 and (Y1 * Z2 ** 3 - Y2 * Z1 ** 3) % q == 0
+G2_LEN = 2
+PLAN = kzg_amd.FK20Plan
 
 
 def all_coeff(eng, plan, blob, n, batch, ofmt=L.G1_AFFINE_MONT, sfmt=L.FR_CANONICAL, flags=0, out=None, evals=False):
@@ -94,30 +38,12 @@ def all_coeff(eng, plan, blob, n, batch, ofmt=L.G1_AFFINE_MONT, sfmt=L.FR_CANONI
     return buf
 
 
-def split(raw, psz, count):
-    return [raw[i * psz:(i + 1) * psz] for i in range(count)]
-
-
 def evals_at_domain(coeffs, N):
     return C.fft(list(coeffs) + [0] * (N - len(coeffs)))
 
 
 def mont(xs):
     return [x * MONT_R % M.R for x in xs]
-
-
-def dev_buffer(eng, nbytes):
-    """a device allocation filled with 0xA5, so that a region no call writes cannot pass for a result"""
-    p = ctypes.c_void_p()
-    assert eng.lib.kzg_dev_alloc(eng.ctx, nbytes, ctypes.byref(p)) == 0
-    assert eng.lib.kzg_dev_upload(eng.ctx, p, b"\xa5" * nbytes, nbytes) == 0
-    return p
-
-
-def dev_download(eng, p, nbytes):
-    back = ctypes.create_string_buffer(nbytes)
-    assert eng.lib.kzg_dev_download(eng.ctx, back, p, nbytes) == 0
-    return back.raw
 
 
 def known_tau_check(eng, rng, coeffs, N, proofs, ys=None):
@@ -431,7 +357,7 @@ def test_plan_of_another_device(eng, hooks, params):
     hooks.lib.kzg_test_srs_set_device.restype = I32
     plan = kzg_amd.FK20Plan(eng, params.gs, 2)
     try:
-        # the plan handle is opaque; its first field is the device (struct kzg_fk20 in g1ntt.hip)
+        # the plan handle is opaque; its first field is the device (struct Fk20Plan in g1ntt.hip)
         ctypes.cast(plan.handle, ctypes.POINTER(ctypes.c_int))[0] = 1
         out = ctypes.create_string_buffer(96 * 4)
         rc = eng.lib.kzg_witness_all_coeff(eng.ctx, plan.handle, pack_scalars([1, 2, 3]), 3, 1, L.FR_CANONICAL, 0, out,

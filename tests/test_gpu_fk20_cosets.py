@@ -14,56 +14,16 @@ from kzg_amd.api import _raise, pack_scalars, unpack_scalars
 from oracle import c_oracle as C
 from oracle import kzg_model as M
 from tests import fk20_model as F
-from tests.gpu_common import HooksEngine, rand_scalars
-from tests.test_gpu_fk20 import FORMATS, MONT_R, SIZE_MAX, dev_buffer, dev_download, same_point, split
+from tests.fk20_common import FORMATS, MONT_R, SIZE_MAX, VP, I32, G, dev_buffer, dev_download, same_point, split
+from tests.fk20_common import eng, hooks, params, plans  # noqa: F401 -- this module's fixtures
+from tests.gpu_common import rand_scalars
 
 pytestmark = pytest.mark.gpu
 
 TAU = 0x5EED_C05E7
 SRS_LEN = 1 << 12
-VP, SZ, I32, U32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32
-
-
-@pytest.fixture(scope="module")
-def eng():
-    e = kzg_amd.Engine(0)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def hooks():
-    h = HooksEngine(0)
-    h.lib.kzg_test_fk20_cosets_combine.argtypes = [VP, VP, VP, SZ, SZ, I32, SZ, VP]
-    h.lib.kzg_test_fk20_cosets_combine.restype = I32
-    yield h
-    h.close()
-
-
-@pytest.fixture(scope="module")
-def params(eng):
-    p = kzg_amd.setup(eng, TAU, SRS_LEN, g2_len=17)
-    yield p
-    p.gs.free()
-    if p.hs is not None:
-        p.hs.free()
-
-
-@pytest.fixture(scope="module")
-def plans(eng, params):
-    cache = {}
-
-    def get(log_n, log_l):
-        if (log_n, log_l) not in cache:
-            cache[(log_n, log_l)] = kzg_amd.FK20CosetPlan(eng, params.gs, log_n, log_l)
-        return cache[(log_n, log_l)]
-    yield get
-    for p in cache.values():
-        p.free()
-
-
-def G():
-    return C.g1_generator()
+G2_LEN = 17
+PLAN = kzg_amd.FK20CosetPlan
 
 
 def cosets(eng, plan, blob, n, batch, ofmt=L.G1_AFFINE_MONT, sfmt=L.FR_CANONICAL, flags=0, out_w=None, out_r=None, want_r=True,
@@ -458,7 +418,7 @@ def test_plan_of_another_device(eng, hooks, params):
     hooks.lib.kzg_test_srs_set_device.restype = I32
     plan = kzg_amd.FK20CosetPlan(eng, params.gs, 2, 1)
     try:
-        # the plan handle is opaque; its first field is the device (struct kzg_fk20_cosets in g1ntt.hip)
+        # the plan handle is opaque; its first field is the device (struct Fk20Plan in g1ntt.hip)
         ctypes.cast(plan.handle, ctypes.POINTER(ctypes.c_int))[0] = 1
         out = ctypes.create_string_buffer(96 * 2)
         rc = eng.lib.kzg_witness_cosets_coeff(eng.ctx, plan.handle, pack_scalars([1, 2, 3]), 3, 1, L.FR_CANONICAL, 0, out,
@@ -507,7 +467,7 @@ def test_plan_shared_by_two_threads_on_two_contexts(eng, plans):
 
 
 # ---- 9. batches of several chunks ---------------------------------------------------------------------------------------------
-# cosets_run works through a batch in chunks of F.chunk_size(N) polynomials, the last one ragged, and splits each chunk's
+# fk20_run works through a batch in chunks of F.chunk_size(N) polynomials, the last one ragged, and splits each chunk's
 # combination into F.coset_slices residue slices chosen from the FIRST chunk.  n < N, so that the input (b0 n) and output (b0 K,
 # b0 N) offsets differ.  Every batch equals single calls, and the polynomials at chunk edges also equal kzg_witness_coeff_batched.
 @pytest.fixture(scope="module")
