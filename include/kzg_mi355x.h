@@ -408,6 +408,27 @@ int kzg_witness_cosets_coeff(kzg_ctx *ctx, const kzg_fk20_cosets *plan, const vo
 /* `batch` evaluation vectors of length d == N (else KZG_ERR_SHAPE), natural domain order: iNTT in Fr, then the above */
 int kzg_witness_cosets_eval(kzg_ctx *ctx, const kzg_fk20_cosets *plan, const void *evals, size_t d, size_t batch, int sfmt,
                             int flags, void *out_w, int ofmt, void *out_r);
+/* ---- recovery from a subset of the cosets (erasure recovery; Fr only, no SRS; not a reference method) ------------------------
+ * The other half of the coset calls above: a polynomial of at most n coefficients from ANY `known` of the K = N / l cosets of
+ * its size-N domain (N = 2^log_n, l = 2^log_l) with known * l >= n.  coset_ids: `known` distinct ids < K in any order (host
+ * memory, always).  cells: batch x known x l scalars in sfmt, cell j of polynomial b at (b known + j) l, holding
+ * p_b(w^(id_j + t K)) for t = 0 .. l-1 (the point order of the coset calls); KZG_IN_DEVICE applies to it.  out_coeffs
+ * (optional): batch x n scalars, stride n -- what kzg_witness_cosets_coeff takes.  out_evals (optional): batch x N scalars in
+ * natural domain order -- what kzg_witness_cosets_eval takes; the known cells come back bit-identical.  At least one output;
+ * KZG_OUT_DEVICE applies to both, both are in sfmt.  status (optional, host, batch ints): 0 = recovered, 1 = the cells of that
+ * polynomial are not the values of a polynomial of fewer than n coefficients (detectable iff known * l > n); the call then
+ * returns KZG_OK and a failed polynomial's outputs are unspecified but stay inside their slots.  Without status any such
+ * polynomial makes the call return KZG_ERR_POINT_NOT_ON_POLY (the convention of kzg_witness_coeff_many).
+ * With M the missing ids, nu = w^l and Zs(Y) = prod_{i in M} (Y - nu^i): the cells times Zs(nu^id) are the values of
+ * p(X) Zs(X^l), of degree < N; one iNTT, a division by Zs(X^l) on the coset 7 H (where it has no root) and the transform
+ * back give p: three size-N transforms per polynomial (four with out_evals).  Zs is built once per call by a product tree in
+ * O(m log^2 m) (leaves of 256 roots), its K values and K inverses by two size-K transforms and one batch inversion.
+ * KZG_ERR_SHAPE, before any memory is touched: log_l > log_n, log_n > 22 (the FK20 plans' limit), n == 0, n > N, known == 0,
+ * known > K, known * l < n, an id >= K, a duplicate id, NULL coset_ids or cells, both outputs NULL, an unknown scalar format.
+ * batch == 0 returns KZG_OK.  Leases one lane like the other blocking calls (concurrent callers run side by side); works in
+ * chunks of at most max(1, 2^21 / 2N) polynomials (the rule of the FK20 calls), so the workspace does not grow with `batch`. */
+int kzg_recover_cosets(kzg_ctx *ctx, uint32_t log_n, uint32_t log_l, size_t n, const size_t *coset_ids, size_t known,
+                       const void *cells, size_t batch, int sfmt, int flags, void *out_coeffs, void *out_evals, int *status);
 /* KZGVerifierEvalForm::verify_poly (:162-171): ifft then monomial MSM, compare. */
 int kzg_verify_poly_eval(kzg_ctx *ctx, const kzg_srs *monomial, const void *commitment, int pfmt,
                          const void *evals, size_t d, int sfmt, int flags, int *ok);

@@ -161,6 +161,19 @@ struct EvaluationDomain {  // src/ft.rs:17-25
     }
 };
 
+// kzg_recover_cosets: the polynomial of at most n coefficients whose values on the cosets `coset_ids` (coset i = { w^(i + tK) },
+// K = N / l, cells[j] = the l values on coset_ids[j]) are `cells`; evals (optional) receives its N evaluations.  Not a reference method.
+inline Polynomial recover_cosets(const Engine &e, uint32_t log_n, uint32_t log_l, size_t n, const std::vector<size_t> &coset_ids,
+                                 const std::vector<Scalar> &cells, std::vector<Scalar> *evals = nullptr) {
+    static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+    if (log_l > log_n || log_n > 22 || cells.size() != (coset_ids.size() << log_l)) throw ReferencePanic("recover_cosets: shape");
+    std::vector<Scalar> c(n ? n : 1);
+    if (evals) evals->resize((size_t)1 << log_n);
+    e.check(kzg_recover_cosets(e.ctx(), log_n, log_l, n, coset_ids.data(), coset_ids.size(), cells.data(), 1, KZG_FR_CANONICAL_LE_32, 0,
+                               c.data(), evals ? evals->data() : nullptr, nullptr));
+    return Polynomial::make(std::move(c));
+}
+
 struct KZGBatchWitness {  // src/coeff_form.rs:12-35
     Polynomial r;
     G1Affine w;

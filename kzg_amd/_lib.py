@@ -121,6 +121,7 @@ def load(path=None):
         "kzg_fk20_cosets_shape": (i32, [vp, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
         "kzg_witness_cosets_coeff": (i32, [vp, vp, vp, sz, sz, i32, i32, vp, i32, vp]),
         "kzg_witness_cosets_eval": (i32, [vp, vp, vp, sz, sz, i32, i32, vp, i32, vp]),
+        "kzg_recover_cosets": (i32, [vp, u32, u32, sz, ctypes.POINTER(sz), sz, vp, sz, i32, i32, vp, vp, ctypes.POINTER(i32)]),
         "kzg_srs_setup_g2": (i32, [vp, vp, i32, sz, c_void_pp]),
         "kzg_srs_setup_lagrange_g2": (i32, [vp, vp, i32, sz, c_void_pp]),
         "kzg_srs_lagrange_from_monomial_g2": (i32, [vp, vp, c_void_pp]),

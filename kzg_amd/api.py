@@ -283,6 +283,43 @@ class Engine:
             _raise(self, rc)
         return unpack_scalars(out.raw)
 
+    def recover_cosets(self, log_n, log_l, n, coset_ids, cells, want_evals=False):
+        """kzg_recover_cosets for one polynomial: the Polynomial of n coefficients whose values on coset coset_ids[j] (the points
+        of FK20CosetPlan.coset_points) are cells[j]; with want_evals also its 2^log_n evaluations in natural domain order.
+        cells: a list of `known` lists of l ints, a canonical blob or a DeviceBuffer.  Raises PointNotOnPolynomial if the cells
+        are not the values of such a polynomial, ReferencePanic on a shape the call rejects."""
+        if not isinstance(cells, (DeviceBuffer, bytes, bytearray, memoryview)):
+            cells = [v for cell in cells for v in cell]
+        res = self.recover_cosets_batch(log_n, log_l, n, coset_ids, cells, 1, want_evals)
+        return (res[0][0], res[1][0]) if want_evals else res[0]
+
+    def recover_cosets_batch(self, log_n, log_l, n, coset_ids, cells, batch=None, want_evals=False):
+        """`batch` polynomials over one id set.  cells: a list of polynomials (each a list of `known` lists of l ints), or a flat
+        list of ints / a canonical blob / a DeviceBuffer of batch x known x l scalars (batch then given).  Returns the list of
+        Polynomials, and with want_evals the pair (polynomials, list of evaluation lists)."""
+        ids = [int(i) for i in coset_ids]
+        known = len(ids)
+        if batch is None:
+            batch = len(cells)
+            cells = [v for poly in cells for cell in poly for v in cell]
+        if n < 0 or batch < 0 or not 0 <= log_l <= log_n <= 22:
+            raise ReferencePanic("recover_cosets: 0 <= log_l <= log_n <= 22, n >= 0 and batch >= 0")
+        ptr, have, sfmt, flags, _keep = self._scalars_arg(cells)
+        if have < (batch * known) << log_l:  # the call would read past the buffer
+            raise ReferencePanic("recover_cosets: %d scalars given, batch * known * l = %d" % (have, (batch * known) << log_l))
+        N = 1 << log_n
+        id_arr = (ctypes.c_size_t * max(known, 1))(*[i % (1 << 64) for i in ids])
+        coeffs = ctypes.create_string_buffer(32 * max(n * batch, 1))
+        evals = ctypes.create_string_buffer(32 * max(N * batch, 1)) if want_evals else None
+        rc = self.lib.kzg_recover_cosets(self.ctx, log_n, log_l, n, id_arr, known, ptr, batch, sfmt, flags, coeffs, evals, None)
+        if rc:
+            _raise(self, rc)
+        conv = (lambda b: [self._scalar_from(b[i:i + 32], sfmt) for i in range(0, len(b), 32)]) if sfmt == L.FR_MONT else unpack_scalars
+        polys = [Polynomial.new_from_coeffs(conv(coeffs.raw[b * n * 32:(b + 1) * n * 32]), n - 1) for b in range(batch)]
+        if not want_evals:
+            return polys
+        return polys, [conv(evals.raw[b * N * 32:(b + 1) * N * 32]) for b in range(batch)]
+
     _MONT_R = (1 << 256) % R_MODULUS
 
     def _host_scalar(self, x, sfmt):

@@ -401,6 +401,9 @@ struct WitnessSink {
 int witness_coeff_batched_run(kzg_ctx *ctx, const WitnessSink &sink, const void *coeffs, size_t n, const void *xs, const void *ys,
                               size_t k, int sfmt, int flags, void *out_w, int ofmt, void *out_r, size_t *out_r_len);
 int vanishing_poly_run(kzg_ctx *ctx, hipStream_t st, const Fr *d_xs_mont, size_t k, Fr *d_z, Fr *d_tmp);  // k+1 coeffs each
+// coset_fft / icoset_fft with shift g (src/ft.rs:142-178): v[i] *= g^i then the transform; the inverse transform then v[i] *= g^-i.
+// nnz (forward only): d[nnz ..) is zero, so only d[0, nnz) is scaled
+int coset_ntt_run(kzg_ctx *ctx, int lane, Fr *d, uint32_t log_n, int inverse, const Fr &g, size_t nnz = (size_t)-1);
 
 // cached per-context tables, released by kzg_ctx_destroy
 void ntt_plans_free(kzg_ctx *ctx);   // ntt.hip

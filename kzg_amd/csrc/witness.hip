@@ -115,7 +115,7 @@ static int distribute_powers(kzg_ctx *ctx, hipStream_t st, Fr *d, size_t n, cons
 
 // coset_fft: distribute_powers(g) then fft; icoset_fft: ifft then distribute_powers(g^-1).
 // nnz (forward only): the caller knows that d[nnz ..) is zero -- a zero-padded short polynomial -- so only d[0, nnz) is scaled
-static int coset_ntt_run(kzg_ctx *ctx, int lane, Fr *d, uint32_t log_n, int inverse, const Fr &g, size_t nnz = (size_t)-1) {
+int coset_ntt_run(kzg_ctx *ctx, int lane, Fr *d, uint32_t log_n, int inverse, const Fr &g, size_t nnz) {
     hipStream_t st = ctx->lanes[lane].stream;
     size_t n = (size_t)1 << log_n;
     const bool unit = g == Fr::one();  // the "coset" 1 * H: the plain transform (create_witness_batched's first choice of a shift)
