@@ -67,6 +67,8 @@ extern "C" {
  *   kzg_srs_lagrange_from_monomial_g1       d <= 2^24;  _g2: d <= 1024
  *   kzg_fk20_setup                          log_n <= 22                      (the plan holds 2N points of 224 B: 1.9 GB there)
  *   kzg_fk20_cosets_setup                   log_n <= 22, 1 <= log_l <= log_n (the plan holds 8 x 2N rows of 128 B: 8.6 GB there)
+ *   kzg_cosets_verifier_setup               log_n <= 22, log_l <= 8           (the plan's window table: 32 x l x 128 affine points of 96 B,
+ *                                                                             393 KiB x l: 25 MB at l = 64, 101 MB at l = 256, the bound)
  *   MSM                                     table rows x points < 2^31       (the sorted entry is a 31-bit table index + sign);
  *                                           window_bits 18, 19 (option), and 20 with option sort_single_pass: windows x points < 2^27
  *   kzg_g1_sum_batch                        count <= 2^20, groups <= 2^24
@@ -145,6 +147,7 @@ int kzg_sync(kzg_ctx *ctx);
  * "naf_window" (0 / 18, applies to SRSs created afterwards: 18 = positional tables, 2^j P for every bit position j = 255 rows of
  * 128 B per point, scalars recoded in width-18 non-adjacent form -- 13.9 instead of 15 bucket additions per scalar for 17x the
  * table: 34 GB at 2^20; measured +3.7 % batched throughput at 2^20, nothing below 2^19, +1.3 ms on a lone commit: opt-in);
+ * "verify_cosets_chunk" (0 = default; n: kzg_verify_cosets works in chunks of at most n cells),
  * "fk20_cosets_combine" (0 = the shared-doubling Straus kernel, default; 1 = one mul256 per term: the same bytes, for comparison),
  * unknown keys -> KZG_ERR_SHAPE */
 int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value);
@@ -471,6 +474,38 @@ int kzg_verify_eval_batched(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *h
 int kzg_verify_eval_all(kzg_ctx *ctx, const kzg_srs *lagrange_g, const kzg_srs_g2 *lagrange_h, const kzg_srs_g2 *hs,
                         const void *ys, size_t ys_len, int sfmt, const void *commitment, const void *witness, int pfmt,
                         int *ok);
+/* ---- bulk verification of coset openings (not a reference method) ---------------------------------------------------------
+ * The check of kzg_verify_eval_batched for the cells of the coset calls above ("all coset openings": N = 2^log_n, l = 2^log_l,
+ * K = N / l, coset i = { w^(i + tK) : t < l } with vanishing polynomial X^l - w^(il)), `count` cells per call, independent checks,
+ * one verdict per cell -- what a caller needs before kzg_recover_cosets, which is only sound on verified cells.  Per cell:
+ *   r_i from the l values in Fr (u = iNTT_l(v) over nu = w^K, r_{i,j} = u_j w^(-ij): the out_r of kzg_witness_cosets_coeff),
+ *   R_i = sum_j r_{i,j} gs[j] gathered from a fixed-base window table of gs[0 .. l) (signed 8-bit digits: 32 l mixed additions, no
+ *   doubling, no bucket method), and e(pi_i, hs[l]) e(-([w^(il)] pi_i + C - R_i), hs[0]) == 1 -- the equation
+ *   e(pi_i, [tau^l]H - [w^(il)]H) == e(C - R_i, H) with both G2 arguments fixed, so one GPU thread runs one check against stored
+ *   Miller lines as kzg_verify_eval does.
+ * A kzg_cosets_verifier holds, for one SRS, one domain and one coset size, the table T[win][j][d] = [d 2^(8 win)] gs[j] (affine,
+ * d = 1 .. 128: 393 KiB x l, at most 101 MB at the limit l = 256), the lines of hs[0] and hs[l] and the powers of w; it is immutable
+ * after creation and may be used from any thread and every kzg_ctx on its device.  Setup (takes the context exclusively):
+ * KZG_ERR_SHAPE if len(gs) < l, len(hs) < l + 1, log_l > log_n, log_n > 22, log_l > 8 or an SRS on another GPU.  log_l == 0 is
+ * kzg_verify_eval at the points w^i. */
+typedef struct kzg_cosets_verifier kzg_cosets_verifier;
+int kzg_cosets_verifier_setup(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, uint32_t log_n, uint32_t log_l,
+                              kzg_cosets_verifier **out);
+void kzg_cosets_verifier_free(kzg_ctx *ctx, kzg_cosets_verifier *plan);
+/* *domain = N, *coset_size = l, *table_bytes = the window table's size in HBM (each may be NULL); KZG_ERR_SHAPE for a NULL plan */
+int kzg_cosets_verifier_shape(const kzg_cosets_verifier *plan, size_t *domain, size_t *coset_size, size_t *table_bytes);
+/* Cell k belongs to commitments[commitment_idx[k]] (n_commitments points in pfmt, host) and coset coset_ids[k]; its l values are at
+ * cells + 32 k l (sfmt; KZG_IN_DEVICE applies to `cells` alone), its proof is proofs[k] (pfmt, host).  Ids and indices are host
+ * memory, always.  ok[k] = 1 or 0.  Duplicate (commitment, coset) pairs are allowed; the identity proof verifies iff C == R (what
+ * FK20 emits for n <= l).  Points are validated as in kzg_verify_eval: a malformed, off-curve or out-of-subgroup commitment or proof
+ * makes the call return KZG_ERR_BAD_POINT and leaves `ok` unwritten.  KZG_ERR_SHAPE, before any memory is touched: an id >= K, an
+ * index >= n_commitments, an unknown format, a Jacobian pfmt, a NULL pointer with count > 0, a plan on another GPU; count == 0
+ * returns KZG_OK.  Leases one lane like the other blocking calls (concurrent callers run side by side); works in chunks of at most
+ * min(16384, 2^20 / l) cells (option "verify_cosets_chunk" lowers it), so the workspace does not grow with `count`; the commitments are decoded once per call, which takes
+ * n_commitments x (point size + 192) bytes of it. */
+int kzg_verify_cosets(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitments, size_t n_commitments,
+                      const uint32_t *commitment_idx, const size_t *coset_ids, const void *cells, const void *proofs, size_t count,
+                      int sfmt, int pfmt, int flags, uint8_t *ok);
 
 /* ---- Fr polynomial helpers on the path (device) ---------------------------------------------- */
 /* Polynomial::eval (src/polynomial.rs:156-165) at one point. */

@@ -268,6 +268,46 @@ class KZGVerifier {  // src/coeff_form.rs:114-183; the pairing checks run on the
     const Engine &e_;
 };
 
+// kzg_cosets_verifier: bulk verification of coset openings (coset i = { w^(i + tK) }, K = N / l, l = 2^log_l <= 256) for one
+// KZGParams, one domain and one coset size.  verify(): cell k belongs to commitments[commitment_idx[k]] and coset coset_ids[k],
+// with its l values at cells[k l ..) and its proof proofs[k]; one verdict per cell.  Not a reference type.
+class CosetVerifier {
+  public:
+    CosetVerifier(const KZGParams &params, uint32_t log_n, uint32_t log_l) : e_(*params.engine), log_l_(log_l) {
+        if (!params.hs) throw ReferencePanic("KZGParams.hs is empty (index out of bounds)");
+        e_.check(kzg_cosets_verifier_setup(e_.ctx(), params.gs, params.hs, log_n, log_l, &plan_));
+    }
+    ~CosetVerifier() { kzg_cosets_verifier_free(e_.ctx(), plan_); }
+    CosetVerifier(const CosetVerifier &) = delete;
+    CosetVerifier &operator=(const CosetVerifier &) = delete;
+    size_t domain() const { return shape(0); }
+    size_t coset_size() const { return shape(1); }
+    size_t table_bytes() const { return shape(2); }  // the window table's size in HBM
+    std::vector<bool> verify(const std::vector<KZGCommitment> &commitments, const std::vector<uint32_t> &commitment_idx,
+                             const std::vector<size_t> &coset_ids, const std::vector<Scalar> &cells,
+                             const std::vector<KZGWitness> &proofs) const {
+        const size_t count = proofs.size();
+        if (commitment_idx.size() != count || coset_ids.size() != count || cells.size() != (count << log_l_))
+            throw ReferencePanic("verify_cosets: shape");
+        std::vector<uint8_t> cb(commitments.size() * 96), pb(count * 96), ok(count ? count : 1);
+        for (size_t i = 0; i < commitments.size(); i++) std::memcpy(cb.data() + 96 * i, commitments[i].bytes.data(), 96);
+        for (size_t i = 0; i < count; i++) std::memcpy(pb.data() + 96 * i, proofs[i].bytes.data(), 96);
+        e_.check(kzg_verify_cosets(e_.ctx(), plan_, cb.data(), commitments.size(), commitment_idx.data(), coset_ids.data(), cells.data(),
+                                   pb.data(), count, KZG_FR_CANONICAL_LE_32, KZG_G1_AFFINE_MONT_96, 0, ok.data()));
+        return std::vector<bool>(ok.begin(), ok.begin() + count);
+    }
+
+  private:
+    size_t shape(int which) const {
+        size_t v[3] = {0, 0, 0};
+        e_.check(kzg_cosets_verifier_shape(plan_, &v[0], &v[1], &v[2]));
+        return v[which];
+    }
+    const Engine &e_;
+    uint32_t log_l_;
+    kzg_cosets_verifier *plan_ = nullptr;
+};
+
 // ---- multi-GPU: KZGParams.gs sharded over a group of GPUs, KZGProver::commit / create_witness over the group ----
 // (the seam is the multi_exp call, src/coeff_form.rs:61,78; partial points are combined over RCCL inside the library)
 // What a ONE-NODE host exports before the first RCCL call of the process (values already exported are kept): RCCL bootstraps every

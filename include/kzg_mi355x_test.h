@@ -76,9 +76,17 @@ enum {
     KZG_ARITH_FR29_QUOTIENT_THREAD = 22, KZG_ARITH_MULSHOUP29X2 = 23, KZG_ARITH_EMIT = 24,
     KZG_ARITH_NUM_OPS = 25
 };
+/* the first two stages of kzg_verify_cosets alone (kzg_amd/csrc/verify_cosets.hip).  stage 0, interpolation: in = count x l cell values
+ * (sfmt) of the cosets coset_ids -> out = count x l interpolant coefficients (sfmt).  stage 1, fixed-base sum: in = count x l scalars
+ * (sfmt; coset_ids unused) -> out = count points sum_j in[k l + j] gs[j], affine Montgomery */
+int kzg_test_verify_cosets_stage(kzg_ctx *ctx, const kzg_cosets_verifier *plan, int stage, const size_t *coset_ids, const void *in,
+                                 size_t count, int sfmt, void *out);
 int kzg_test_arith(kzg_ctx *ctx, int op, const void *in, size_t in_rec, size_t n, void *out, size_t out_rec);
 /* pretend `srs` is resident on GPU `device` (the "SRS of another GPU" error of every MSM entry point, on a one-GPU box) */
 int kzg_test_srs_set_device(struct kzg_srs *srs, int device);
+/* the same for the G2 points and for a kzg_cosets_verifier (kzg_amd/csrc/verify_cosets.hip) */
+int kzg_test_srs_g2_set_device(struct kzg_srs_g2 *srs, int device);
+int kzg_test_cosets_verifier_set_device(kzg_cosets_verifier *plan, int device);
 /* the next sharded call of this group fails locally on local GPU 0 with `code` (status agreement across ranks, mgpu.hip) */
 int kzg_test_mctx_inject_failure(struct kzg_mctx *m, int code);
 /* the next growth of the group's exchange buffers fails on local GPU 0 (a rank-local allocation failure BEFORE the exchange: the

@@ -134,6 +134,10 @@ def load(path=None):
         "kzg_verify_eval": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, i32, sz, vp]),
         "kzg_verify_eval_batched": (i32, [vp, vp, vp, vp, sz, vp, sz, i32, vp, vp, i32, ctypes.POINTER(i32)]),
         "kzg_verify_eval_all": (i32, [vp, vp, vp, vp, vp, sz, i32, vp, vp, i32, ctypes.POINTER(i32)]),
+        "kzg_cosets_verifier_setup": (i32, [vp, vp, vp, u32, u32, c_void_pp]),
+        "kzg_cosets_verifier_free": (None, [vp, vp]),
+        "kzg_cosets_verifier_shape": (i32, [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz)]),
+        "kzg_verify_cosets": (i32, [vp, vp, vp, sz, ctypes.POINTER(u32), ctypes.POINTER(sz), vp, vp, sz, i32, i32, i32, vp]),
         "kzg_poly_eval": (i32, [vp, vp, sz, vp, i32, i32, vp]),
         "kzg_quotient_linear": (i32, [vp, vp, sz, vp, vp, i32, i32, vp]),
         "kzg_quotient_eval": (i32, [vp, vp, sz, sz, i32, i32, vp]),

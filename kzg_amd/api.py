@@ -482,6 +482,61 @@ def _witness_cosets(engine, fn, plan, blob, n, batch, ofmt):
     return res
 
 
+class CosetVerifier:
+    """kzg_cosets_verifier: bulk verification of coset openings for one KZGParams (gs and hs), one domain 2^log_n and one coset
+    size 2^log_l (<= 256): the fixed-base window table of gs[0 .. l), the stored Miller lines of hs[0] and hs[l] and the powers of
+    w.  Coset i is FK20CosetPlan.coset_points(i).  Not a reference type."""
+
+    def __init__(self, engine, params, log_n, log_l):
+        self.engine = engine
+        if params.hs is None:
+            raise ReferencePanic("KZGParams.hs is empty (index out of bounds)")
+        h = ctypes.c_void_p()
+        rc = engine.lib.kzg_cosets_verifier_setup(engine.ctx, params.gs.handle, params.hs.handle, log_n, log_l, ctypes.byref(h))
+        if rc:
+            _raise(engine, rc)
+        self.handle = h
+        N, l, tb = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+        engine.lib.kzg_cosets_verifier_shape(h, ctypes.byref(N), ctypes.byref(l), ctypes.byref(tb))
+        self._shape = (N.value, l.value, tb.value)
+
+    def domain(self):
+        return self._shape[0]
+
+    def coset_size(self):
+        return self._shape[1]
+
+    def table_bytes(self):
+        return self._shape[2]
+
+    def free(self):
+        if self.handle:
+            self.engine.lib.kzg_cosets_verifier_free(self.engine.ctx, self.handle)
+            self.handle = None
+
+    def verify(self, commitments, commitment_idx, coset_ids, cells, proofs, pfmt=L.G1_AFFINE_MONT):
+        """One verdict per cell.  Cell k: commitments[commitment_idx[k]], coset coset_ids[k], proof proofs[k] (bytes in pfmt) and
+        its l values.  cells: a list of cells (each a list of l ints), or a flat list of ints / a canonical blob / a DeviceBuffer
+        of len(proofs) x l scalars.  Raises EngineError on a malformed point, ReferencePanic on a shape the call rejects."""
+        e = self.engine
+        count = len(proofs)
+        if len(commitment_idx) != count or len(coset_ids) != count:
+            raise ReferencePanic("verify_cosets: one commitment index, coset id and proof per cell")
+        if not isinstance(cells, (DeviceBuffer, bytes, bytearray, memoryview)) and len(cells) and isinstance(cells[0], (list, tuple)):
+            cells = [v for cell in cells for v in cell]
+        ptr, have, sfmt, flags, _keep = e._scalars_arg(cells)
+        if have < count * self.coset_size():  # the call would read past the buffer
+            raise ReferencePanic("verify_cosets: %d scalars given, count * l = %d" % (have, count * self.coset_size()))
+        idx = (ctypes.c_uint32 * max(count, 1))(*[int(i) % (1 << 32) for i in commitment_idx])
+        ids = (ctypes.c_size_t * max(count, 1))(*[int(i) % (1 << 64) for i in coset_ids])
+        ok = ctypes.create_string_buffer(max(count, 1))
+        rc = e.lib.kzg_verify_cosets(e.ctx, self.handle, b"".join(commitments), len(commitments), idx, ids, ptr, b"".join(proofs), count,
+                                     sfmt, pfmt, flags, ok)
+        if rc:
+            _raise(e, rc)
+        return [bool(b) for b in ok.raw[:count]]
+
+
 class SrsG2:
     """Resident G2 points (kzg_srs_g2): the `hs` half of KZGParams or a G2 Lagrange basis."""
 
@@ -1073,6 +1128,11 @@ class KZGVerifier:
         if rc:
             _raise(e, rc)
         return bool(ok.value)
+
+    def verify_cosets(self, verifier, commitment, coset_ids, cells, proofs, pfmt=L.G1_AFFINE_MONT):
+        """kzg_verify_cosets for the cells of ONE commitment: cells[k] (l values) and proofs[k] open coset coset_ids[k] of the
+        CosetVerifier's domain -> list of bool.  Not a reference method."""
+        return verifier.verify([commitment], [0] * len(proofs), coset_ids, cells, proofs, pfmt)
 
     def verify_poly(self, commitment, polynomial, pfmt=L.G1_AFFINE_MONT):
         e = self.engine

@@ -6,16 +6,7 @@
 // both pairs and one final exponentiation.  A check is a serial chain of ~25 k Fq multiplies, so ONE THREAD runs
 // ONE check and a batch of openings is one launch (kzg_verify_eval takes `count` tuples); tower.h documents the
 // arithmetic.  Nothing here is on the prover's throughput path.
-#include "common.h"
-#include "tower.h"
-
-struct kzg_srs_g2 {
-    size_t n = 0;
-    kzg::G2Affine *pts = nullptr;  // affine Montgomery (= blst_p2_affine), identity all-zero
-    kzg::Fq2 *lines = nullptr;     // Miller-loop lines of pts[0] and pts[1] (2 x 2*MILLER_LINES Fq2): the verifier's
-                                   // second pairing argument is always one of these two, so a check does no G2 arithmetic
-    int device = 0;
-};
+#include "pairing_shared.h"
 
 namespace kzg {
 
@@ -374,13 +365,15 @@ int g2_from_scalars(kzg_ctx *ctx, hipStream_t st, const Fr *d_scalars_mont, size
     return KZG_OK;
 }
 
-// decode `count` G1 points of format pfmt (host memory) into XYZZ on the device
-int g1_inputs(kzg_ctx *ctx, const void *host, size_t count, int pfmt, G1Xyzz **d_out, int *d_bad) {
+}  // namespace
+
+// decode `count` G1 points of format pfmt (host memory) into XYZZ on the device (pairing_shared.h)
+int kzg::g1_inputs(kzg_ctx *ctx, int lane, const void *host, size_t count, int pfmt, G1Xyzz **d_out, int *d_bad) {
     size_t psz = point_format_bytes(pfmt);
     if (!psz) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 point format");
-    hipStream_t st = ctx->lanes[0].stream;
-    void *raw = lane_alloc(ctx, 0, count * psz);
-    G1Xyzz *pts = (G1Xyzz *)lane_alloc(ctx, 0, count * sizeof(G1Xyzz));
+    hipStream_t st = ctx->lanes[lane].stream;
+    void *raw = lane_alloc(ctx, lane, count * psz);
+    G1Xyzz *pts = (G1Xyzz *)lane_alloc(ctx, lane, count * sizeof(G1Xyzz));
     if (!raw || !pts) return fail(ctx, KZG_ERR_ALLOC, "workspace");
     KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, host, count * psz, hipMemcpyHostToDevice, st));
     KZG_TRY(decode_points(ctx, st, raw, count, pfmt, pts, d_bad, untrusted_level(ctx)));
@@ -388,10 +381,10 @@ int g1_inputs(kzg_ctx *ctx, const void *host, size_t count, int pfmt, G1Xyzz **d
     return KZG_OK;
 }
 
-int fetch_ok(kzg_ctx *ctx, const uint8_t *d_ok, const int *d_bad, size_t count, uint8_t *ok) {
-    hipStream_t st = ctx->lanes[0].stream;
-    KZG_TRY(lane_pinned(ctx, 0, count + 64));
-    char *pin = ctx->lanes[0].pinned;
+int kzg::fetch_ok(kzg_ctx *ctx, int lane, const uint8_t *d_ok, const int *d_bad, size_t count, uint8_t *ok) {
+    hipStream_t st = ctx->lanes[lane].stream;
+    KZG_TRY(lane_pinned(ctx, lane, count + 64));
+    char *pin = ctx->lanes[lane].pinned;
     KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
     KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin + 64, d_ok, count, hipMemcpyDeviceToHost, st));
     KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
@@ -400,7 +393,6 @@ int fetch_ok(kzg_ctx *ctx, const uint8_t *d_ok, const int *d_bad, size_t count, 
     memcpy(ok, pin + 64, count);
     return KZG_OK;
 }
-}  // namespace
 
 // ------------------------------------------------------------------------------------------------
 // C ABI: G2 SRS
@@ -614,11 +606,11 @@ extern "C" int kzg_pairing_check(kzg_ctx *ctx, const void *g1_points, int pfmt1,
     if (!bad || !d_ok || !raw2 || !q) return fail(ctx, KZG_ERR_ALLOC, "workspace");
     KZG_HIP_CHECK(ctx, hipMemsetAsync(bad, 0, sizeof(int), st));
     G1Xyzz *p = nullptr;
-    KZG_TRY(g1_inputs(ctx, g1_points, total, pfmt1, &p, bad));
+    KZG_TRY(g1_inputs(ctx, 0, g1_points, total, pfmt1, &p, bad));
     KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw2, g2_points, total * p2, hipMemcpyHostToDevice, st));
     KZG_LAUNCH(ctx, st, "k_g2_decode", k_g2_decode, (unsigned)((total + 63) / 64), 64, 0, raw2, total, pfmt2, q, bad, untrusted_level(ctx));
     KZG_LAUNCH(ctx, st, "k_pairing_check", k_pairing_check, (unsigned)((checks + 63) / 64), 64, 0, p, q, (int)pairs_per_check, checks, d_ok);
-    return fetch_ok(ctx, d_ok, bad, checks, ok);
+    return fetch_ok(ctx, 0, d_ok, bad, checks, ok);
 }
 
 extern "C" int kzg_verify_eval(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *xs, const void *ys, int sfmt,
@@ -642,11 +634,11 @@ extern "C" int kzg_verify_eval(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2
     KZG_HIP_CHECK(ctx, hipMemcpyAsync(dx, xs, count * 32, hipMemcpyHostToDevice, st));
     KZG_HIP_CHECK(ctx, hipMemcpyAsync(dy, ys, count * 32, hipMemcpyHostToDevice, st));
     G1Xyzz *C = nullptr, *W = nullptr;
-    KZG_TRY(g1_inputs(ctx, commitments, count, pfmt, &C, bad));
-    KZG_TRY(g1_inputs(ctx, witnesses, count, pfmt, &W, bad));
+    KZG_TRY(g1_inputs(ctx, 0, commitments, count, pfmt, &C, bad));
+    KZG_TRY(g1_inputs(ctx, 0, witnesses, count, pfmt, &W, bad));
     KZG_LAUNCH(ctx, st, "k_verify_eval", k_verify_eval, (unsigned)((count + 63) / 64), 64, 0, dx, dy, sfmt == KZG_FR_MONT_LE_32 ? 1 : 0, C, W,
                gs->table, hs->pts, hs->lines, count, d_ok);
-    return fetch_ok(ctx, d_ok, bad, count, ok);
+    return fetch_ok(ctx, 0, d_ok, bad, count, ok);
 }
 
 // shared tail of verify_eval_batched / verify_eval_all: gr = MSM(g1 basis, r), then the pairing check against d_hz
@@ -660,15 +652,15 @@ static int verify_with_hz(kzg_ctx *ctx, const kzg_srs *basis_g, const void *r, s
     if (!bad || !d_ok || !gr || !dr) return fail(ctx, KZG_ERR_ALLOC, "workspace");
     KZG_HIP_CHECK(ctx, hipMemsetAsync(bad, 0, sizeof(int), st));
     G1Xyzz *C = nullptr, *W = nullptr;
-    KZG_TRY(g1_inputs(ctx, commitment, 1, pfmt, &C, bad));
-    KZG_TRY(g1_inputs(ctx, witness, 1, pfmt, &W, bad));
+    KZG_TRY(g1_inputs(ctx, 0, commitment, 1, pfmt, &C, bad));
+    KZG_TRY(g1_inputs(ctx, 0, witness, 1, pfmt, &W, bad));
     if (r_len) KZG_HIP_CHECK(ctx, hipMemcpyAsync(dr, r, r_len * 32, hipMemcpyHostToDevice, st));
     MsmPoint *res = nullptr;
     KZG_TRY(msm_run(ctx, 0, basis_g, 0, dr, r_len, sfmt, &res));
     KZG_TRY(emit_point(ctx, 0, res, gr, KZG_G1_AFFINE_MONT_96));
     KZG_LAUNCH(ctx, st, "k_verify_finish", k_verify_finish, 1, 1, 0, C, gr, W, d_hz, d_h0, d_lines_h0, d_ok);
     uint8_t r8 = 0;
-    KZG_TRY(fetch_ok(ctx, d_ok, bad, 1, &r8));
+    KZG_TRY(fetch_ok(ctx, 0, d_ok, bad, 1, &r8));
     *ok = r8;
     return KZG_OK;
 }

@@ -1,0 +1,20 @@
+// pairing_shared.h -- what the verifier's translation units (pairing.hip, verify_cosets.hip) share besides tower.h: the resident G2
+// points and the two helpers every verifier entry point brings its G1 inputs in and its verdicts out with.
+#pragma once
+#include "common.h"
+#include "tower.h"
+
+struct kzg_srs_g2 {
+    size_t n = 0;
+    kzg::G2Affine *pts = nullptr;  // affine Montgomery (= blst_p2_affine), identity all-zero
+    kzg::Fq2 *lines = nullptr;     // Miller-loop lines of pts[0] and pts[1] (2 x 2*MILLER_LINES Fq2): the verifier's
+                                   // second pairing argument is always one of these two, so a check does no G2 arithmetic
+    int device = 0;
+};
+
+namespace kzg {
+// decode `count` G1 points of format pfmt (host memory) into XYZZ on the device, in the lane's arena and on its stream
+int g1_inputs(kzg_ctx *ctx, int lane, const void *host, size_t count, int pfmt, G1Xyzz **d_out, int *d_bad);
+// the verdicts and the decode flag of one launch: KZG_ERR_BAD_POINT if the flag is set (ok is then not written); synchronises the lane
+int fetch_ok(kzg_ctx *ctx, int lane, const uint8_t *d_ok, const int *d_bad, size_t count, uint8_t *ok);
+}  // namespace kzg
