@@ -360,6 +360,35 @@ int kzg_witness_eval(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals, s
  * Not a reference method: equivalent to calling KZGProverEvalForm::create_witness count times. */
 int kzg_witness_eval_many(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals, size_t d, const size_t *indices,
                           size_t count, int sfmt, int flags, void *out, int ofmt);
+/* ---- openings at ANY point of Fr, in batches, against the Lagrange SRS alone (not a reference method) -------------------------
+ * kzg_witness_eval opens at a point of the domain, by index.  These three open at any z: with f_i = p(w^i), i < d = 2^k,
+ * w = compute_omega(d).omega,
+ *   z off the domain:  y = (z^d - 1)/d  sum_i f_i w^i / (z - w^i),  q_i = (f_i - y) / (w^i - z),  witness = sum_i q_i L_i;
+ *   z = w^m:           y = f_m and q is kzg_quotient_eval(evals, d, m): the witness bytes are kzg_witness_eval(evals, d, m)'s.
+ * Which case a z is in is decided on the host (z^d == 1; m is read one bit per squaring level), so no zero denominator reaches
+ * the batch inversion.  The denominators are formed and inverted once per DISTINCT z of a chunk: a batch that shares one
+ * challenge pays for one inversion of d elements per chunk.  No monomial SRS, no inverse transform.
+ * evals: batch x d scalars in sfmt, stride d; KZG_IN_DEVICE applies to it.  zs: batch host scalars in sfmt, each < r (else
+ * KZG_ERR_SHAPE, the rule for single host scalars); always host memory.  ys_out: batch scalars in sfmt, always host memory.
+ * KZG_ERR_SHAPE, before any memory is touched: d == 0 or not a power of two, an unknown format, a NULL input, a z >= r, and for
+ * kzg_open_eval d != kzg_srs_len(lagrange) (assert!(self.d == evals.d)) or an SRS on another GPU.  batch == 0 returns KZG_OK.
+ * d == 1: y = f_0 and the witness is the identity. */
+/* ys_out[b] = p_b(zs[b]).  Leases one lane like the other blocking calls; works in chunks of at most min(16, 2^22 / d)
+ * polynomials. */
+int kzg_eval_form_eval(kzg_ctx *ctx, const void *evals, size_t d, size_t batch, const void *zs, int sfmt, int flags,
+                       void *ys_out);
+/* The any-point sibling of kzg_quotient_eval, one polynomial: *y_out = p(z) (host, optional) and q_out = the d values of
+ * (p - y)/(X - z) on the domain (host, or device with KZG_OUT_DEVICE) -- the scalars of the witness MSM. */
+int kzg_quotient_eval_at(kzg_ctx *ctx, const void *evals, size_t d, const void *z, int sfmt, int flags, void *y_out,
+                         void *q_out);
+/* The full call: ys_out[b] = p_b(zs[b]) and out_w[b] = its witness in ofmt (host, or device with KZG_OUT_DEVICE).  Either
+ * output may be NULL, not both (out_w == NULL: no MSM runs).  Takes the context exclusively, like kzg_msm_g1_batch whose
+ * pipeline the quotients feed without leaving HBM: chunks of one polynomial per lane (option "streams"), the Fr stage of chunk
+ * c + 1 on a stream of its own beside the MSMs of chunk c.  The workspace does not grow with `batch` (but for its 32 bytes per
+ * value): per chunk 2 x d x 32 bytes of quotients per lane, at most as much again for denominators and inverses (one set per
+ * distinct z), and the lanes' MSM workspaces. */
+int kzg_open_eval(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals, size_t d, size_t batch, const void *zs, int sfmt,
+                  int flags, void *ys_out, void *out_w, int ofmt);
 /* ---- all openings over the domain (FK20, single-point case; not a reference method) ---------------------------------
  * Every witness of a polynomial at every point w^m of its size-N domain (w = compute_omega(N).omega) in O(N log N) group
  * operations instead of N MSMs: two G1 DFTs, 2N variable-base scalar multiplications and one Fr NTT per polynomial, against a

@@ -11,6 +11,7 @@
 #include <stdexcept>
 #include <cstdlib>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "kzg_mi355x.h"
@@ -172,6 +173,16 @@ inline Polynomial recover_cosets(const Engine &e, uint32_t log_n, uint32_t log_l
     e.check(kzg_recover_cosets(e.ctx(), log_n, log_l, n, coset_ids.data(), coset_ids.size(), cells.data(), 1, KZG_FR_CANONICAL_LE_32, 0,
                                c.data(), evals ? evals->data() : nullptr, nullptr));
     return Polynomial::make(std::move(c));
+}
+
+// kzg_eval_form_eval: p_b(zs[b]) for zs.size() polynomials given by their evaluations over the size-d domain (evals: zs.size() x d
+// scalars back to back), at any points of Fr.  Not a reference method.
+inline std::vector<Scalar> eval_form_eval(const Engine &e, const std::vector<Scalar> &evals, size_t d, const std::vector<Scalar> &zs) {
+    static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+    if (evals.size() != zs.size() * d) throw ReferencePanic("eval_form_eval: shape");
+    std::vector<Scalar> ys(zs.size());
+    e.check(kzg_eval_form_eval(e.ctx(), evals.data(), d, zs.size(), zs.data(), KZG_FR_CANONICAL_LE_32, 0, ys.data()));
+    return ys;
 }
 
 struct KZGBatchWitness {  // src/coeff_form.rs:12-35
@@ -446,6 +457,23 @@ class KZGProverEvalForm {  // src/eval_form.rs:39-147
         return out;
     }
     KZGWitness create_witness_all() const { return G1Affine{}; }  // :142-146: the identity
+    // kzg_open_eval: (y, witness) at ANY point z of Fr against the Lagrange SRS alone; at z = omega^i the witness is
+    // create_witness(ev, i).  Not a reference method.
+    std::pair<Scalar, KZGWitness> open_at(const EvaluationDomain &ev, const Scalar &z) const {
+        std::pair<Scalar, KZGWitness> r;
+        e_.check(kzg_open_eval(e_.ctx(), lag_, ev.coeffs.data(), ev.len(), 1, z.le.data(), KZG_FR_CANONICAL_LE_32, 0, r.first.le.data(),
+                               r.second.bytes.data(), KZG_G1_AFFINE_MONT_96));
+        return r;
+    }
+    // one call for zs.size() polynomials: evals holds their evaluations back to back (zs.size() x degree() scalars)
+    std::pair<std::vector<Scalar>, std::vector<KZGWitness>> open_at_batch(const std::vector<Scalar> &evals, const std::vector<Scalar> &zs) const {
+        static_assert(sizeof(Scalar) == 32 && sizeof(G1Affine) == 96, "packed encodings");
+        if (evals.size() != zs.size() * d_) throw ReferencePanic("open_at_batch: one evaluation vector of degree() scalars per point");
+        std::pair<std::vector<Scalar>, std::vector<KZGWitness>> r{std::vector<Scalar>(zs.size()), std::vector<KZGWitness>(zs.size())};
+        e_.check(kzg_open_eval(e_.ctx(), lag_, evals.data(), d_, zs.size(), zs.data(), KZG_FR_CANONICAL_LE_32, 0, r.first.data(),
+                               r.second.data(), KZG_G1_AFFINE_MONT_96));
+        return r;
+    }
 
   private:
     const KZGParams &params_;

@@ -283,6 +283,33 @@ class Engine:
             _raise(self, rc)
         return unpack_scalars(out.raw)
 
+    def eval_form_eval(self, evals, zs, d=None):
+        """kzg_eval_form_eval: the values p_b(zs[b]) of `len(zs)` polynomials given by their evaluations over the size-d domain
+        (any z in Fr, on the domain or off it).  evals: a list of evaluation lists / EvaluationDomains, or a flat list of ints / a
+        canonical blob / a DeviceBuffer of len(zs) x d scalars (d then given)."""
+        ptr, d, sfmt, flags, _keep = self._eval_vectors_arg(evals, len(zs), d)
+        out = ctypes.create_string_buffer(32 * max(len(zs), 1))
+        zb = b"".join(self._host_scalar(int(z), sfmt) for z in zs)
+        rc = self.lib.kzg_eval_form_eval(self.ctx, ptr, d, len(zs), zb, sfmt, flags, out)
+        if rc:
+            _raise(self, rc)
+        return [self._scalar_from(out.raw[32 * b:32 * b + 32], sfmt) for b in range(len(zs))]
+
+    def _eval_vectors_arg(self, evals, batch, d=None):
+        """(pointer, d, sfmt, flags, keep-alive) of `batch` evaluation vectors, stride d"""
+        if not isinstance(evals, (DeviceBuffer, bytes, bytearray, memoryview)) and len(evals) and not isinstance(evals[0], int):
+            vecs = [ev.coeffs if isinstance(ev, EvaluationDomain) else list(ev) for ev in evals]
+            if len(vecs) != batch or any(len(v) != len(vecs[0]) for v in vecs):
+                raise ReferencePanic("one evaluation vector per point, all of one length")
+            d = len(vecs[0])
+            evals = [v for vec in vecs for v in vec]
+        ptr, have, sfmt, flags, keep = self._scalars_arg(evals)
+        if d is None:
+            d = have // max(batch, 1)
+        if have < batch * d:  # the call would read past the buffer
+            raise ReferencePanic("%d scalars given, batch * d = %d" % (have, batch * d))
+        return ptr, d, sfmt, flags, keep
+
     def recover_cosets(self, log_n, log_l, n, coset_ids, cells, want_evals=False):
         """kzg_recover_cosets for one polynomial: the Polynomial of n coefficients whose values on coset coset_ids[j] (the points
         of FK20CosetPlan.coset_points) are cells[j]; with want_evals also its 2^log_n evaluations in natural domain order.
@@ -1179,6 +1206,28 @@ class KZGProverEvalForm:
         if rc:
             _raise(e, rc)
         return out.raw
+
+    def open_at(self, evals, z, ofmt=L.G1_AFFINE_MONT):
+        """(y, witness) at ANY point z of Fr (kzg_open_eval; not a reference method): y = p(z) and the opening proof, against the
+        Lagrange SRS alone.  At z = omega^i the witness is create_witness(evals, i)."""
+        ys, ws = self.open_at_batch([evals], [z], ofmt)
+        return ys[0], ws[0]
+
+    def open_at_batch(self, evals, zs, ofmt=L.G1_AFFINE_MONT):
+        """open_at for len(zs) polynomials in one call -> (list of y, list of witnesses).  evals: a list of EvaluationDomains /
+        evaluation lists, or a canonical blob / a DeviceBuffer of len(zs) x d scalars."""
+        e = self.engine
+        batch = len(zs)
+        ptr, d, sfmt, flags, _keep = e._eval_vectors_arg(evals, batch, len(self.lagrange_basis_g))
+        psz = L.POINT_BYTES[ofmt]
+        ys = ctypes.create_string_buffer(32 * max(batch, 1))
+        out = ctypes.create_string_buffer(psz * max(batch, 1))
+        zb = b"".join(e._host_scalar(int(z), sfmt) for z in zs)
+        rc = e.lib.kzg_open_eval(e.ctx, self.lagrange_basis_g.handle, ptr, d, batch, zb, sfmt, flags, ys, out, ofmt)
+        if rc:
+            _raise(e, rc)
+        return ([e._scalar_from(ys.raw[32 * b:32 * b + 32], sfmt) for b in range(batch)],
+                [out.raw[b * psz:(b + 1) * psz] for b in range(batch)])
 
     def create_witness_many(self, evals, indices, ofmt=L.G1_AFFINE_MONT):
         """Throughput form of create_witness (not a reference method): one witness per index, same evaluation vector."""

@@ -602,6 +602,162 @@ extern "C" int kzg_quotient_eval(kzg_ctx *ctx, const void *evals, size_t d, size
 }
 
 // ---------------------------------------------------------------------------------------------
+// evaluation form at any point of Fr (open_eval.hip): y = p(z), the quotient's values on the domain, the witness
+// ---------------------------------------------------------------------------------------------
+// what the three entry points check alike, before memory is touched: the domain, the scalar format, and every z (host scalars: < r)
+static int open_args(kzg_ctx *ctx, size_t d, size_t batch, const void *zs, int sfmt, uint32_t *log_d, std::vector<OpenPoint> *pts) {
+    KZG_TRY(check_sfmt(ctx, sfmt));
+    if (!is_pow2(d)) return fail(ctx, KZG_ERR_SHAPE, "evaluation domain size must be a power of two");
+    *log_d = (uint32_t)ilog2_ceil(d);
+    if (*log_d >= FR_TWO_ADICITY) return fail(ctx, KZG_ERR_DEGREE_TOO_LARGE, "domain too large");
+    if (batch > SIZE_MAX / (d * 32)) return fail(ctx, KZG_ERR_SHAPE, "batch too large");
+    try {  // (no exception may leave through the C ABI)
+        pts->resize(batch);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, KZG_ERR_ALLOC, "host memory for the opening points");
+    }
+    for (size_t b = 0; b < batch; b++) {
+        Fr zm;
+        KZG_TRY(host_scalar(ctx, (const uint8_t *)zs + 32 * b, sfmt, &zm));
+        if (open_point_classify(*log_d, zm, &(*pts)[b]) != KZG_OK) return fail(ctx, KZG_ERR_INTERNAL, "z^d == 1 but z is no power of omega");
+    }
+    return KZG_OK;
+}
+
+// the Fr stage alone on one lane: ys_out (optional, host) and, for ONE polynomial, its quotient at q_out (optional; host or device)
+static int open_fr_only(kzg_ctx *ctx, int lane, const void *evals, uint32_t log_d, size_t batch, const OpenPoint *pts, int sfmt, int flags,
+                        void *ys_out, void *q_out) {
+    const size_t d = (size_t)1 << log_d;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>({(size_t)OE_MAX_CHUNK, batch, ((size_t)1 << 22) / d}));
+    const bool in_dev = (flags & KZG_IN_DEVICE) != 0, q_dev = q_out && (flags & KZG_OUT_DEVICE);
+    KZG_TRY(lane_reserve(ctx, lane, stage_bytes(chunk * d * 32, flags) + align_up(batch * 32, 256) + ((q_out && !q_dev) ? align_up(d * 32, 256) : 0) +
+                                        open_eval_fr_workspace_bytes(d, chunk) + 65536));
+    hipStream_t st = ctx->lanes[lane].stream;
+    Fr *d_in = in_dev ? nullptr : (Fr *)lane_alloc(ctx, lane, chunk * d * 32);
+    Fr *d_y = (Fr *)lane_alloc(ctx, lane, batch * 32);
+    Fr *d_q = !q_out ? nullptr : (q_dev ? (Fr *)q_out : (Fr *)lane_alloc(ctx, lane, d * 32));
+    if ((!in_dev && !d_in) || !d_y || (q_out && !d_q)) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    int rc = KZG_OK;
+    for (size_t b0 = 0; b0 < batch && rc == KZG_OK; b0 += chunk) {
+        const size_t B = std::min(chunk, batch - b0);
+        const Fr *src = (const Fr *)evals + b0 * d;
+        if (!in_dev) {
+            if (hipMemcpyAsync(d_in, src, B * d * 32, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "stage-in of the evaluations");
+            src = d_in;
+        }
+        if (rc == KZG_OK) rc = open_eval_fr_run(ctx, lane, src, log_d, B, pts + b0, sfmt, d_y + b0, d_q);
+    }
+    if (rc == KZG_OK && ys_out && hipMemcpyAsync(ys_out, d_y, batch * 32, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "copy of the values");
+    if (rc == KZG_OK && q_out && !q_dev && hipMemcpyAsync(q_out, d_q, d * 32, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "copy of the quotient");
+    if (hipStreamSynchronize(st) != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "evaluation-form opening");
+    if (ctx->prof) prof_collect(ctx);
+    return rc;
+}
+
+extern "C" int kzg_eval_form_eval(kzg_ctx *ctx, const void *evals, size_t d, size_t batch, const void *zs, int sfmt, int flags, void *ys_out) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    if (!evals || !zs || !ys_out) return fail(ctx, KZG_ERR_SHAPE, "kzg_eval_form_eval: NULL evals, zs or ys_out");
+    uint32_t log_d = 0;
+    std::vector<OpenPoint> pts;
+    KZG_TRY(open_args(ctx, d, batch, zs, sfmt, &log_d, &pts));
+    if (batch == 0) return KZG_OK;
+    Lease ls;
+    KZG_TRY(lease_lane(ctx, &ls));
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    return open_fr_only(ctx, ls.lane, evals, log_d, batch, pts.data(), sfmt, flags, ys_out, nullptr);
+}
+
+extern "C" int kzg_quotient_eval_at(kzg_ctx *ctx, const void *evals, size_t d, const void *z, int sfmt, int flags, void *y_out, void *q_out) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    if (!evals || !z || !q_out) return fail(ctx, KZG_ERR_SHAPE, "kzg_quotient_eval_at: NULL evals, z or q_out");
+    uint32_t log_d = 0;
+    std::vector<OpenPoint> pts;
+    KZG_TRY(open_args(ctx, d, 1, z, sfmt, &log_d, &pts));
+    Lease ls;
+    KZG_TRY(lease_lane(ctx, &ls));
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    return open_fr_only(ctx, ls.lane, evals, log_d, 1, pts.data(), sfmt, flags, y_out, q_out);
+}
+
+extern "C" int kzg_open_eval(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals, size_t d, size_t batch, const void *zs, int sfmt,
+                             int flags, void *ys_out, void *out_w, int ofmt) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    if (!lagrange || !evals || !zs) return fail(ctx, KZG_ERR_SHAPE, "kzg_open_eval: NULL lagrange, evals or zs");
+    if (!ys_out && !out_w) return fail(ctx, KZG_ERR_SHAPE, "kzg_open_eval: no output");
+    const size_t psz = point_format_bytes(ofmt);
+    if (!psz) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 output format");
+    if (d != lagrange->n) return fail(ctx, KZG_ERR_SHAPE, "assert!(self.d == evals.d) (src/eval_form.rs:115)");
+    if (lagrange->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the Lagrange SRS is resident on another GPU than this context's");
+    uint32_t log_d = 0;
+    std::vector<OpenPoint> pts;
+    KZG_TRY(open_args(ctx, d, batch, zs, sfmt, &log_d, &pts));
+    if (batch == 0) return KZG_OK;
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (!out_w) return open_fr_only(ctx, 0, evals, log_d, batch, pts.data(), sfmt, flags & ~KZG_OUT_DEVICE, ys_out, nullptr);
+    BatchPipe bp;
+    KZG_TRY(batch_begin(ctx, batch, batch * psz, out_w, flags, &bp));
+    // Chunks of one polynomial per lane.  The Fr stage of a chunk runs on the stream of one extra lane (its arena holds what the
+    // chunks share: staged evaluations, the values, two sets of quotients); the MSMs of chunk c read set c & 1 on their lanes while
+    // that stream already works on chunk c + 1, and chunk c + 2 waits for them before it overwrites the set.
+    const size_t chunk = (size_t)bp.nl;
+    const int sl = bp.nl;
+    const bool in_dev = (flags & KZG_IN_DEVICE) != 0;
+    const size_t qset = align_up(chunk * d * 32, 256);
+    int rc = ensure_lanes(ctx, sl + 1);
+    if (rc == KZG_OK) rc = lane_reserve(ctx, sl, stage_bytes(chunk * d * 32, flags) + 2 * qset + align_up(batch * 32, 256) + open_eval_fr_workspace_bytes(d, chunk) + 65536);
+    for (int l = 0; l < bp.nl && rc == KZG_OK; l++) rc = lane_reserve(ctx, l, msm_workspace_bytes(lagrange, d) + 65536);
+    hipStream_t fst = rc == KZG_OK ? ctx->lanes[sl].stream : nullptr;
+    Fr *d_in = nullptr, *d_y = nullptr, *d_q[2] = {nullptr, nullptr};
+    if (rc == KZG_OK) {
+        d_in = in_dev ? nullptr : (Fr *)lane_alloc(ctx, sl, chunk * d * 32);
+        d_y = (Fr *)lane_alloc(ctx, sl, batch * 32);
+        d_q[0] = (Fr *)lane_alloc(ctx, sl, qset);
+        d_q[1] = (Fr *)lane_alloc(ctx, sl, qset);
+        if ((!in_dev && !d_in) || !d_y || !d_q[0] || !d_q[1]) rc = fail(ctx, KZG_ERR_ALLOC, "workspace");
+    }
+    // events: the Fr stage of a chunk is done (per set); lane l is done with its MSM of a chunk (per set and lane)
+    std::vector<hipEvent_t> evs;
+    try {
+        evs.assign(2 + 2 * chunk, nullptr);
+    } catch (const std::bad_alloc &) {
+        if (rc == KZG_OK) rc = fail(ctx, KZG_ERR_ALLOC, "host memory");
+    }
+    for (size_t i = 0; i < evs.size() && rc == KZG_OK; i++)
+        if (hipEventCreateWithFlags(&evs[i], hipEventDisableTiming) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "hipEventCreate");
+    for (size_t b0 = 0, c = 0; b0 < batch && rc == KZG_OK; b0 += chunk, c++) {
+        const size_t B = std::min(chunk, batch - b0), p = c & 1;
+        hipEvent_t fr_done = evs[p], *lane_done = &evs[2 + p * chunk];
+        if (c >= 2)  // (every chunk but the last is full: all lanes recorded in chunk c - 2)
+            for (size_t l = 0; l < chunk && rc == KZG_OK; l++)
+                if (hipStreamWaitEvent(fst, lane_done[l], 0) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "hipStreamWaitEvent");
+        const Fr *src = (const Fr *)evals + b0 * d;
+        if (!in_dev && rc == KZG_OK) {
+            if (hipMemcpyAsync(d_in, src, B * d * 32, hipMemcpyHostToDevice, fst) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "stage-in of the evaluations");
+            src = d_in;
+        }
+        if (rc == KZG_OK) rc = open_eval_fr_run(ctx, sl, src, log_d, B, pts.data() + b0, sfmt, d_y + b0, d_q[p]);
+        if (rc == KZG_OK && hipEventRecord(fr_done, fst) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "hipEventRecord");
+        for (size_t b = 0; b < B && rc == KZG_OK; b++) {
+            const int l = (int)b;
+            hipStream_t st = ctx->lanes[l].stream;
+            ctx->lanes[l].arena_used = 0;  // stream order makes re-use of the lane arena safe
+            if (hipStreamWaitEvent(st, fr_done, 0) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "hipStreamWaitEvent");
+            MsmPoint *res = nullptr;
+            if (rc == KZG_OK) rc = batch_msm(ctx, bp, b0 + b, l, lagrange, 0, d_q[p] + b * d, d, sfmt, &res);
+            if (rc == KZG_OK) rc = emit_point(ctx, l, res, bp.d_out + (b0 + b) * psz, ofmt);
+            if (rc == KZG_OK && hipEventRecord(lane_done[l], st) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "hipEventRecord");
+        }
+    }
+    if (fst && hipStreamSynchronize(fst) != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "evaluation-form opening");
+    rc = batch_end(ctx, bp, rc, out_w, batch * psz);
+    for (hipEvent_t e : evs)
+        if (e) (void)hipEventDestroy(e);
+    if (rc == KZG_OK && ys_out) KZG_HIP_CHECK(ctx, hipMemcpy(ys_out, d_y, batch * 32, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
 // witnesses
 // ---------------------------------------------------------------------------------------------
 extern "C" int kzg_witness_coeff(kzg_ctx *ctx, const kzg_srs *srs, const void *coeffs, size_t n, const void *x,

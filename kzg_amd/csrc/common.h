@@ -436,4 +436,17 @@ int quotient_linear_run(kzg_ctx *ctx, int lane, const Fr *d_coeffs, size_t n, co
                         Fr *d_px_out);
 int quotient_eval_run(kzg_ctx *ctx, int lane, const Fr *d_evals, uint32_t log_d, size_t m, int sfmt, Fr *d_q_out);
 
+// open_eval.hip: evaluation-form polynomials at any point of Fr
+constexpr int OE_MAX_CHUNK = 16;  // polynomials per chunk (the most lanes option "streams" allows)
+struct OpenPoint {                // an opening point, classified on the host
+    Fr z;                         // Montgomery
+    Fr c;                         // (z^d - 1) / d; zero on the domain
+    bool on_domain;               // z = w^m
+    size_t m;
+};
+int open_point_classify(uint32_t log_d, const Fr &z_mont, OpenPoint *pt);  // KZG_ERR_INTERNAL: the walk over the bits of m broke down
+size_t open_eval_fr_workspace_bytes(size_t d, size_t B);                   // arena bytes one open_eval_fr_run of B polynomials takes
+// y (d_y + b) and, unless d_q is null, the quotient (d_q + b d) of B <= OE_MAX_CHUNK polynomials (d_evals + b d) at pts[b], on the lane's stream
+int open_eval_fr_run(kzg_ctx *ctx, int lane, const Fr *d_evals, uint32_t log_d, size_t B, const OpenPoint *pts, int sfmt, Fr *d_y, Fr *d_q);
+
 }  // namespace kzg
