@@ -69,6 +69,8 @@ extern "C" {
  *   kzg_fk20_cosets_setup                   log_n <= 22, 1 <= log_l <= log_n (the plan holds 8 x 2N rows of 128 B: 8.6 GB there)
  *   kzg_cosets_verifier_setup               log_n <= 22, log_l <= 8           (the plan's window table: 32 x l x 128 affine points of 96 B,
  *                                                                             393 KiB x l: 25 MB at l = 64, 101 MB at l = 256, the bound)
+ *   kzg_verify_cosets_batch                 the plan's limits; any count: the workspace is 3 x 8 x 32 x 128 buckets of 192 B (18.9 MB)
+ *                                                                             beside one chunk's buffers and 32 B per commitment
  *   MSM                                     table rows x points < 2^31       (the sorted entry is a 31-bit table index + sign);
  *                                           window_bits 18, 19 (option), and 20 with option sort_single_pass: windows x points < 2^27
  *   kzg_g1_sum_batch                        count <= 2^20, groups <= 2^24
@@ -148,6 +150,8 @@ int kzg_sync(kzg_ctx *ctx);
  * 128 B per point, scalars recoded in width-18 non-adjacent form -- 13.9 instead of 15 bucket additions per scalar for 17x the
  * table: 34 GB at 2^20; measured +3.7 % batched throughput at 2^20, nothing below 2^19, +1.3 ms on a lone commit: opt-in);
  * "verify_cosets_chunk" (0 = default; n: kzg_verify_cosets works in chunks of at most n cells),
+ * "host_pairing" (1 / 0: the one pairing check that ends kzg_verify_cosets_batch runs on the calling thread -- the same tower code
+ *  compiled for the host -- instead of in a one-thread kernel; the same verdict, default 1),
  * "fk20_cosets_combine" (0 = the shared-doubling Straus kernel, default; 1 = one mul256 per term: the same bytes, for comparison),
  * unknown keys -> KZG_ERR_SHAPE */
 int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value);
@@ -535,6 +539,26 @@ int kzg_cosets_verifier_shape(const kzg_cosets_verifier *plan, size_t *domain, s
 int kzg_verify_cosets(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitments, size_t n_commitments,
                       const uint32_t *commitment_idx, const size_t *coset_ids, const void *cells, const void *proofs, size_t count,
                       int sfmt, int pfmt, int flags, uint8_t *ok);
+/* "Are all of these cells good?": ONE verdict for the whole call from one pairing check (the verify_cell_kzg_proof_batch shape of the
+ * data-availability-sampling specifications).  Every argument means what it means in kzg_verify_cosets and the plan is the same.  With
+ * the challenge r (one host scalar in sfmt) the per-cell equations are weighted by rho_k = r^k, k = 0 .. count - 1, and summed:
+ *   a_j = sum_k rho_k r_{k,j},  Ragg = sum_j a_j gs[j];   c_m = sum_{k: m_k = m} rho_k,  Cagg = sum_m c_m C_m;
+ *   P1 = sum_k rho_k pi_k,  P2 = sum_k (rho_k w^(i_k l)) pi_k;   *ok = [ e(P1, hs[l]) e(-(P2 + Cagg - Ragg), hs[0]) == 1 ].
+ * Per cell that is an interpolation in Fr and 2 x 32 bucket additions of a variable-base multi-scalar sum (signed 8-bit digits);
+ * the fixed-base sum and the pairing check happen once per call.
+ * WHAT THE CALLER OWES.  The verdict is sound only if r is unpredictable to whoever produced the cells: draw it at random AFTER the
+ * cells, proofs and commitments have been received, or derive it as a hash of ALL inputs of the call, as the consensus specifications
+ * do (the library has no hash, and the domain separation is the protocol's business).  With a predictable r a forger can make errors
+ * cancel: with r = 1, pi_a + D and pi_b - D in one coset pass.  Honest cells pass for every r.  *ok == 0 says nothing about WHICH
+ * cell is bad: follow it with kzg_verify_cosets.
+ * r == 0 (only cell 0 would be checked) or r >= modulus: KZG_ERR_SHAPE.  count == 0: *ok = 1 (if ok is non-NULL), KZG_OK.  Every other
+ * shape error and KZG_ERR_BAD_POINT follow the rules of kzg_verify_cosets exactly and leave *ok unwritten; duplicate (commitment,
+ * coset) pairs and identity proofs are allowed.  Leases one lane, works in the chunks of kzg_verify_cosets (option
+ * "verify_cosets_chunk"), so the workspace does not grow with `count` (Limits).  Option "host_pairing" chooses where the one pairing
+ * check runs. */
+int kzg_verify_cosets_batch(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitments, size_t n_commitments,
+                            const uint32_t *commitment_idx, const size_t *coset_ids, const void *cells, const void *proofs,
+                            size_t count, const void *r, int sfmt, int pfmt, int flags, int *ok);
 
 /* ---- Fr polynomial helpers on the path (device) ---------------------------------------------- */
 /* Polynomial::eval (src/polynomial.rs:156-165) at one point. */

@@ -307,6 +307,23 @@ class CosetVerifier {
                                    pb.data(), count, KZG_FR_CANONICAL_LE_32, KZG_G1_AFFINE_MONT_96, 0, ok.data()));
         return std::vector<bool>(ok.begin(), ok.begin() + count);
     }
+    // kzg_verify_cosets_batch: true iff ALL the cells verify, from one pairing check of their combination with the weights r^k.
+    // r must be unpredictable to whoever produced the cells (drawn after they arrived, or the hash of all inputs): see the header.
+    // false says nothing about which cell is bad: verify() does.
+    bool verify_batch(const std::vector<KZGCommitment> &commitments, const std::vector<uint32_t> &commitment_idx,
+                      const std::vector<size_t> &coset_ids, const std::vector<Scalar> &cells, const std::vector<KZGWitness> &proofs,
+                      const Scalar &r) const {
+        const size_t count = proofs.size();
+        if (commitment_idx.size() != count || coset_ids.size() != count || cells.size() != (count << log_l_))
+            throw ReferencePanic("verify_cosets_batch: shape");
+        std::vector<uint8_t> cb(commitments.size() * 96), pb(count * 96);
+        for (size_t i = 0; i < commitments.size(); i++) std::memcpy(cb.data() + 96 * i, commitments[i].bytes.data(), 96);
+        for (size_t i = 0; i < count; i++) std::memcpy(pb.data() + 96 * i, proofs[i].bytes.data(), 96);
+        int ok = 0;
+        e_.check(kzg_verify_cosets_batch(e_.ctx(), plan_, cb.data(), commitments.size(), commitment_idx.data(), coset_ids.data(), cells.data(),
+                                         pb.data(), count, r.le.data(), KZG_FR_CANONICAL_LE_32, KZG_G1_AFFINE_MONT_96, 0, &ok));
+        return ok != 0;
+    }
 
   private:
     size_t shape(int which) const {

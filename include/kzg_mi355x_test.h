@@ -81,6 +81,15 @@ enum {
  * (sfmt; coset_ids unused) -> out = count points sum_j in[k l + j] gs[j], affine Montgomery */
 int kzg_test_verify_cosets_stage(kzg_ctx *ctx, const kzg_cosets_verifier *plan, int stage, const size_t *coset_ids, const void *in,
                                  size_t count, int sfmt, void *out);
+/* the variable-base multi-scalar sum of kzg_verify_cosets_batch alone (kzg_amd/csrc/verify_cosets_batch.hip) over row 0 of a resident
+ * SRS: out = sum_{i < n} scalars[i] srs[offset + i], affine Montgomery 96 B -- what kzg_msm_g1 gives for the same arguments */
+int kzg_test_vb_msm(kzg_ctx *ctx, const struct kzg_srs *srs, size_t offset, const void *scalars, size_t n, int sfmt, void *out_affine_mont_96);
+/* kzg_verify_cosets_batch with its intermediate results: out_a = the l scalars a_j, out_cw = the n_commitments scalars c_m (both
+ * canonical), out_points = P1, P2, Cagg, Ragg (4 x affine Montgomery 96 B).  count > 0 */
+int kzg_test_verify_cosets_batch_parts(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitments, size_t n_commitments,
+                                       const uint32_t *commitment_idx, const size_t *coset_ids, const void *cells, const void *proofs,
+                                       size_t count, const void *r, int sfmt, int pfmt, int flags, int *ok, void *out_a, void *out_cw,
+                                       void *out_points);
 int kzg_test_arith(kzg_ctx *ctx, int op, const void *in, size_t in_rec, size_t n, void *out, size_t out_rec);
 /* pretend `srs` is resident on GPU `device` (the "SRS of another GPU" error of every MSM entry point, on a one-GPU box) */
 int kzg_test_srs_set_device(struct kzg_srs *srs, int device);

@@ -138,6 +138,8 @@ def load(path=None):
         "kzg_cosets_verifier_free": (None, [vp, vp]),
         "kzg_cosets_verifier_shape": (i32, [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz)]),
         "kzg_verify_cosets": (i32, [vp, vp, vp, sz, ctypes.POINTER(u32), ctypes.POINTER(sz), vp, vp, sz, i32, i32, i32, vp]),
+        "kzg_verify_cosets_batch": (i32, [vp, vp, vp, sz, ctypes.POINTER(u32), ctypes.POINTER(sz), vp, vp, sz, vp, i32, i32, i32,
+                                          ctypes.POINTER(i32)]),
         "kzg_poly_eval": (i32, [vp, vp, sz, vp, i32, i32, vp]),
         "kzg_quotient_linear": (i32, [vp, vp, sz, vp, vp, i32, i32, vp]),
         "kzg_quotient_eval": (i32, [vp, vp, sz, sz, i32, i32, vp]),

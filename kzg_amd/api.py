@@ -12,6 +12,7 @@ happens on the GPU in libkzg_mi355x.so; nothing here computes field or curve ope
 """
 import ctypes
 import os
+import secrets
 
 from . import _lib as L
 
@@ -562,6 +563,42 @@ class CosetVerifier:
         if rc:
             _raise(e, rc)
         return [bool(b) for b in ok.raw[:count]]
+
+    def verify_batch(self, commitments, commitment_idx, coset_ids, cells, proofs, r=None, pfmt=L.G1_AFFINE_MONT):
+        """kzg_verify_cosets_batch: True iff ALL the cells verify, from one pairing check of their combination with the weights
+        r^k.  The arguments of verify(); r: the challenge, an int in [1, R).  r=None draws it here with `secrets` -- sound because it
+        is drawn after the cells were handed over; a protocol that needs a reproducible verdict passes the hash of all inputs.
+        False says nothing about which cell is bad: verify() does (verify_with_fallback)."""
+        e = self.engine
+        count = len(proofs)
+        if len(commitment_idx) != count or len(coset_ids) != count:
+            raise ReferencePanic("verify_cosets_batch: one commitment index, coset id and proof per cell")
+        if not isinstance(cells, (DeviceBuffer, bytes, bytearray, memoryview)) and len(cells) and isinstance(cells[0], (list, tuple)):
+            cells = [v for cell in cells for v in cell]
+        ptr, have, sfmt, flags, _keep = e._scalars_arg(cells)
+        if have < count * self.coset_size():  # the call would read past the buffer
+            raise ReferencePanic("verify_cosets_batch: %d scalars given, count * l = %d" % (have, count * self.coset_size()))
+        if r is None:
+            r = secrets.randbelow(R_MODULUS - 1) + 1
+        if not 0 <= int(r) < (1 << 256):
+            raise ReferencePanic("verify_cosets_batch: the challenge r must be in [1, R)")
+        r = int(r)
+        if sfmt == L.FR_MONT and r < R_MODULUS:  # the challenge travels in the scalar format of the cells (0 and r >= R: the call's error)
+            r = r * (1 << 256) % R_MODULUS
+        idx = (ctypes.c_uint32 * max(count, 1))(*[int(i) % (1 << 32) for i in commitment_idx])
+        ids = (ctypes.c_size_t * max(count, 1))(*[int(i) % (1 << 64) for i in coset_ids])
+        ok = ctypes.c_int(-1)
+        rc = e.lib.kzg_verify_cosets_batch(e.ctx, self.handle, b"".join(commitments), len(commitments), idx, ids, ptr, b"".join(proofs),
+                                           count, r.to_bytes(32, "little"), sfmt, pfmt, flags, ctypes.byref(ok))
+        if rc:
+            _raise(e, rc)
+        return bool(ok.value)
+
+    def verify_with_fallback(self, commitments, commitment_idx, coset_ids, cells, proofs, r=None, pfmt=L.G1_AFFINE_MONT):
+        """One verdict per cell, as verify(): the batch check first, and the per-cell checks only when it says no."""
+        if self.verify_batch(commitments, commitment_idx, coset_ids, cells, proofs, r, pfmt):
+            return [True] * len(proofs)
+        return self.verify(commitments, commitment_idx, coset_ids, cells, proofs, pfmt)
 
 
 class SrsG2:
@@ -1160,6 +1197,10 @@ class KZGVerifier:
         """kzg_verify_cosets for the cells of ONE commitment: cells[k] (l values) and proofs[k] open coset coset_ids[k] of the
         CosetVerifier's domain -> list of bool.  Not a reference method."""
         return verifier.verify([commitment], [0] * len(proofs), coset_ids, cells, proofs, pfmt)
+
+    def verify_cosets_batch(self, verifier, commitment, coset_ids, cells, proofs, r=None, pfmt=L.G1_AFFINE_MONT):
+        """kzg_verify_cosets_batch for the cells of ONE commitment -> bool (CosetVerifier.verify_batch).  Not a reference method."""
+        return verifier.verify_batch([commitment], [0] * len(proofs), coset_ids, cells, proofs, r, pfmt)
 
     def verify_poly(self, commitment, polynomial, pfmt=L.G1_AFFINE_MONT):
         e = self.engine

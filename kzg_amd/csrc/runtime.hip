@@ -372,6 +372,8 @@ extern "C" int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value) 
         ctx->opt_small_entries = value;
     } else if (k == "host_affine") {
         ctx->opt_host_affine = value != 0;
+    } else if (k == "host_pairing") {
+        ctx->opt_host_pairing = value != 0;
     } else if (k == "heavy_bins") {
         if (value < 0 || value > 2) return fail(ctx, KZG_ERR_SHAPE, "heavy_bins: 0 (adaptive), 1 (always slice oversized sort bins), 2 (never)");
         ctx->opt_heavy_bins = (int)value;

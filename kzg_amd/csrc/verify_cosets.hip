@@ -15,16 +15,9 @@
 #include <new>
 #include <vector>
 
-#include "pairing_shared.h"
+#include "verify_cosets_shared.h"
 
 namespace kzg {
-
-constexpr uint32_t VC_MAX_LOG_L = 8;    // cosets of up to 256 points (include/kzg_mi355x.h, Limits)
-constexpr uint32_t VC_MAX_LOG_N = 22;   // the FK20 plans' limit: what can be proved can be verified
-constexpr int VC_C = 8;                 // window bits: 32 windows x 128 entries per base (DESIGN.md 3.5e for the choice)
-constexpr int VC_W = (256 + VC_C - 1) / VC_C;
-constexpr uint32_t VC_D = 1u << (VC_C - 1);
-constexpr size_t VC_CHUNK_CELLS = 16384, VC_CHUNK_SCALARS = (size_t)1 << 20;  // cells per chunk: min(16384, 2^20 / l)
 
 // ---- plan construction -------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_vc_base(const G1Affine *gs, uint32_t l, G1Xyzz *base) {
@@ -91,23 +84,6 @@ __global__ __launch_bounds__(256) void k_vc_interp(const Fr *cells, const uint32
 }
 
 // ---- 2. fixed-base sum -------------------------------------------------------------------------------------------------------
-// Signed digit `win` of a canonical scalar (Booth recoding: every digit from its own c + 1 bits, no carry chain, so any lane can
-// take any window): d = bits[c win, c win + c) + bit[c win - 1] - 2^c bit[c win + c - 1], |d| <= 2^(c-1); c W >= 256 > the top bit
-__device__ __forceinline__ int vc_digit(const uint32_t *k, int win) {
-    const int lo = VC_C * win - 1;
-    uint32_t x;
-    if (lo < 0) {
-        x = (k[0] << 1) & ((2u << VC_C) - 1u);
-    } else {
-        const int w = lo >> 5, sh = lo & 31;
-        x = k[w] >> sh;
-        if (sh && w + 1 < 8) x |= k[w + 1] << (32 - sh);
-        x &= (2u << VC_C) - 1u;
-    }
-    const int d = (int)(x >> 1) + (int)(x & 1u);
-    return (x >> VC_C) ? d - (1 << VC_C) : d;
-}
-
 // One wave per cell: lane e takes the (base, window) pairs e, e + 64, ... of the cell's l W, adds its table entries into one XYZZ
 // accumulator (mixed additions) and the 64 partial sums fold in LDS in six rounds.  out[cell] = R.
 __global__ __launch_bounds__(64) void k_vc_sum(const Fr *r, uint32_t log_l, int is_mont, const G1Affine *table, G1Xyzz *out) {
@@ -171,18 +147,6 @@ __global__ __launch_bounds__(64) void k_vc_check(const uint32_t *ids, const uint
 
 using namespace kzg;
 
-struct kzg_cosets_verifier {
-    uint32_t log_n = 0, log_l = 0;
-    int device = 0;
-    size_t table_bytes = 0;
-    G1Affine *table = nullptr;  // [VC_W][l][VC_D]
-    G2Affine *hq = nullptr;     // hs[0], hs[l]
-    Fq2 *lines = nullptr;       // their stored Miller lines, 2 x 2 MILLER_LINES
-    // powers of w = compute_omega(N), Montgomery: ninv_lo[e] = w^-e / l and pos_lo[e] = w^e for e < 1024, ninv_hi[h] = w^(-1024 h) and
-    // pos_hi[h] = w^(1024 h) for h < max(1, N / 1024); nu_inv[e] = nu^-e for e < max(1, l / 2).  One allocation (ninv_lo).
-    Fr *ninv_lo = nullptr, *ninv_hi = nullptr, *pos_lo = nullptr, *pos_hi = nullptr, *nu_inv = nullptr;
-};
-
 namespace {
 static inline unsigned vc_grid(size_t n, unsigned b = 256) { return (unsigned)((n + b - 1) / b); }
 
@@ -195,24 +159,25 @@ void vc_release(kzg_cosets_verifier *p) {
     delete p;
 }
 
+}  // namespace
+
 // stages 1 and 2 of a chunk of B cells on stream st: d_cells (sfmt) -> d_r (sfmt) -> d_R
-int vc_interp(kzg_ctx *ctx, hipStream_t st, const kzg_cosets_verifier *p, const Fr *d_cells, const uint32_t *d_ids, size_t B, Fr *d_r) {
+int kzg::vc_interp(kzg_ctx *ctx, hipStream_t st, const kzg_cosets_verifier *p, const Fr *d_cells, const uint32_t *d_ids, size_t B, Fr *d_r) {
     KZG_LAUNCH(ctx, st, "k_vc_interp", k_vc_interp, vc_grid(B, 256u >> p->log_l), 256, 0, d_cells, d_ids, B, p->log_n, p->log_l,
                (const Fr *)p->nu_inv, (const Fr *)p->ninv_lo, (const Fr *)p->ninv_hi, d_r);
     return KZG_OK;
 }
-int vc_sum(kzg_ctx *ctx, hipStream_t st, const kzg_cosets_verifier *p, const Fr *d_r, size_t B, int sfmt, G1Xyzz *d_R) {
+int kzg::vc_sum(kzg_ctx *ctx, hipStream_t st, const kzg_cosets_verifier *p, const Fr *d_r, size_t B, int sfmt, G1Xyzz *d_R) {
     KZG_LAUNCH(ctx, st, "k_vc_sum", k_vc_sum, (unsigned)B, 64, 0, d_r, p->log_l, sfmt == KZG_FR_MONT_LE_32 ? 1 : 0, (const G1Affine *)p->table,
                d_R);
     return KZG_OK;
 }
 
-size_t vc_chunk(const kzg_ctx *ctx, const kzg_cosets_verifier *p) {
+size_t kzg::vc_chunk(const kzg_ctx *ctx, const kzg_cosets_verifier *p) {
     size_t chunk = std::max<size_t>(1, std::min(VC_CHUNK_CELLS, VC_CHUNK_SCALARS >> p->log_l));
     if (ctx->opt_verify_cosets_chunk > 0) chunk = std::min(chunk, (size_t)ctx->opt_verify_cosets_chunk);
     return chunk;
 }
-}  // namespace
 
 extern "C" int kzg_cosets_verifier_setup(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, uint32_t log_n, uint32_t log_l,
                                          kzg_cosets_verifier **out) {
@@ -266,6 +231,9 @@ extern "C" int kzg_cosets_verifier_setup(kzg_ctx *ctx, const kzg_srs *gs, const 
     if (rc == KZG_OK) rc = build();
     if (hipStreamSynchronize(st) != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "kzg_cosets_verifier_setup: a kernel failed");
     if (rc == KZG_OK && hipGetLastError() != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "kzg_cosets_verifier_setup: a launch failed");
+    if (rc == KZG_OK && (hipMemcpy(p->h_hq, p->hq, sizeof(p->h_hq), hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(p->h_lines, p->lines, sizeof(p->h_lines), hipMemcpyDeviceToHost) != hipSuccess))
+        rc = fail(ctx, KZG_ERR_HIP, "kzg_cosets_verifier_setup: the host copy of the Miller lines");
     if (base) hipFree(base);
     if (row) hipFree(row);
     if (ctx->prof) prof_collect(ctx);

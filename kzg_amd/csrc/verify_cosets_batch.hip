@@ -1,0 +1,433 @@
+// verify_cosets_batch.hip -- kzg_verify_cosets_batch: ONE verdict for any number of coset openings, by a random linear combination
+// of the per-cell equations of verify_cosets.hip.  Not a reference method.  Notation as there: N = 2^log_n, l = 2^log_l, K = N / l.
+//
+// Cell k: commitment index m_k, coset i_k, interpolant r_k, proof pi_k, h_k = w^(i_k l); weights rho_k = r^k over the whole call.
+//   a_j = sum_k rho_k r_{k,j}        Ragg = sum_j a_j gs[j]        c_m = sum_{k: m_k = m} rho_k        Cagg = sum_m c_m C_m
+//   P1 = sum_k rho_k pi_k            P2 = sum_k (rho_k h_k) pi_k
+//   ok = [ e(P1, hs[l]) e(-(P2 + Cagg - Ragg), hs[0]) == 1 ]
+// Per chunk of B cells: the proofs are decoded, rho = r^(k0 + k) (k_powers), the interpolants (k_vc_interp), then
+//   k_vcb_scalars   rho_k and rho_k h_k as canonical scalars
+//   k_vcb_fold / k_vcb_fold2   a_j += sum_k rho_k r_{k,j}: partial sums per 64 cells, then one thread per j adds them in order
+//   k_vcb_cweights  c_m += sum rho_k over the chunk's cells of commitment m (lists from a counting sort on the host)
+//   k_vcb_bucket    the variable-base sum: bucket (slice-slot, window, |digit|) += +-pi_k for both scalar sets
+// and after the last chunk the same bucket kernel over the commitments with the scalars c, then k_vcb_reduce (slots folded, each
+// window's 128 buckets to sum_b b B_b), the fixed-base sum of `a` (k_vc_sum) and the finish of vcb_finish.h on the calling thread or
+// in the one-thread kernel k_vcb_finish.  The buckets live in the lane arena for the whole call and every bucket has one owner
+// thread, so chunk after chunk adds into them without atomics.  DESIGN.md section 3.5f.
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+#include "vcb_finish.h"
+#include "verify_cosets_shared.h"
+
+namespace kzg {
+
+constexpr uint32_t VCB_S = 2048;                     // points per slice: one workgroup sorts them by digit in LDS (16-bit indices)
+constexpr uint32_t VCB_G = VC_CHUNK_CELLS / VCB_S;   // slice slots of a chunk
+constexpr size_t VCB_SET = (size_t)VC_W * VC_D;      // buckets of one slot: 32 windows x 128
+constexpr uint32_t VCB_FOLD_CELLS = 64;              // cells per k_vcb_fold workgroup
+static_assert(VC_W == VCB_W, "vcb_finish.h and verify_cosets_shared.h disagree on the windows");
+static_assert(VCB_S <= 32768, "the sorted entries keep the sign in bit 15");
+
+// any scalar of sfmt -> canonical and reduced
+__global__ __launch_bounds__(256) void k_vcb_canon(const Fr *in, size_t n, int is_mont, Fr *out) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = is_mont ? from_mont(in[i]) : mul(in[i], Fr::one());
+}
+
+// s1[k] = rho_k, s2[k] = rho_k h_k, canonical; h_k = w^(i_k l) = pos_hi[e >> 10] pos_lo[e & 1023], e = i_k l < N (as k_vc_check forms it)
+__global__ __launch_bounds__(256) void k_vcb_scalars(const Fr *rho, const uint32_t *ids, size_t count, uint32_t log_l, const Fr *wlo,
+                                                     const Fr *whi, Fr *s1, Fr *s2) {
+    size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const uint32_t e = ids[k] << log_l;
+    const Fr p = rho[k];
+    s1[k] = from_mont(p);
+    s2[k] = from_mont(mul(p, mul(whi[e >> 10], wlo[e & 1023])));
+}
+
+// part[blk l + j] = sum over the workgroup's 64 cells of rho_k r_{k,j}.  256 / l cells side by side, thread (row, j); the rows fold in
+// LDS in a fixed order.  r is in the caller's scalar format and rho Montgomery, so the products keep the format of r.
+__global__ __launch_bounds__(256) void k_vcb_fold(const Fr *r, const Fr *rho, size_t count, uint32_t log_l, Fr *part) {
+    __shared__ Fr sh[256];
+    const uint32_t l = 1u << log_l, j = threadIdx.x & (l - 1), row = threadIdx.x >> log_l, rows = 256u >> log_l;
+    const size_t k0 = (size_t)blockIdx.x * VCB_FOLD_CELLS;
+    Fr acc = Fr::zero();
+    for (uint32_t c = row; c < VCB_FOLD_CELLS && k0 + c < count; c += rows) acc = add(acc, mul(r[((k0 + c) << log_l) + j], rho[k0 + c]));
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    if (row == 0) {
+        for (uint32_t q = 1; q < rows; q++) acc = add(acc, sh[(q << log_l) + j]);
+        part[((size_t)blockIdx.x << log_l) + j] = acc;
+    }
+}
+__global__ __launch_bounds__(256) void k_vcb_fold2(const Fr *part, uint32_t blocks, uint32_t l, Fr *a) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= l) return;
+    Fr acc = a[j];
+    for (uint32_t b = 0; b < blocks; b++) acc = add(acc, part[(size_t)b * l + j]);
+    a[j] = acc;
+}
+
+// one workgroup per non-empty list: c[m] += sum of rho over order[start[g] .. start[g + 1]) (Montgomery)
+__global__ __launch_bounds__(64) void k_vcb_cweights(const Fr *rho, const uint32_t *which, const uint32_t *start, const uint32_t *order, Fr *c) {
+    __shared__ Fr sh[64];
+    const uint32_t g = blockIdx.x, t = threadIdx.x, e0 = start[g], e1 = start[g + 1];
+    Fr acc = Fr::zero();
+    for (uint32_t e = e0 + t; e < e1; e += 64) acc = add(acc, rho[order[e]]);
+    sh[t] = acc;
+    __syncthreads();
+    for (uint32_t s = 32; s >= 1; s >>= 1) {
+        if (t < s) sh[t] = add(sh[t], sh[t + s]);
+        __syncthreads();
+    }
+    if (t == 0) c[which[g]] = add(c[which[g]], sh[0]);
+}
+
+// ---- the variable-base sum ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ G1Affine vcb_point(const G1Affine *pts, size_t i) { return pts[i]; }
+__device__ __forceinline__ G1Affine vcb_point(const G1Xyzz *pts, size_t i) {  // decode_points leaves zz = zzz = 1, or the identity
+    G1Affine a;
+    if (pts[i].zz.is_zero()) return G1Affine::inf();
+    a.x = pts[i].x;
+    a.y = pts[i].y;
+    return a;
+}
+
+// Workgroup (slice, window, set): the window's digit of the slice's <= S canonical scalars, a counting sort of the point indices by
+// |digit| in LDS (128 counters, a scan, a scatter), then thread b walks the contiguous list of bucket b + 1 with mixed additions into
+// the bucket it owns.  The order inside a list is whatever the scatter left; the sum of a list does not depend on it, and g1_madd
+// handles P + P, P + (-P) and the identity.  Set z takes the scalars sc[z] into the buckets bk[z]; the points are shared.
+template <class PT>
+__global__ __launch_bounds__(128) void k_vcb_bucket(const PT *pts, const Fr *sc0, const Fr *sc1, size_t n, G1Xyzz *bk0, G1Xyzz *bk1) {
+    __shared__ uint32_t cnt[VC_D], cur[VC_D];
+    __shared__ uint16_t dig[VCB_S], ent[VCB_S];
+    const uint32_t t = threadIdx.x, slot = blockIdx.x, win = blockIdx.y;
+    const Fr *sc = blockIdx.z ? sc1 : sc0;
+    G1Xyzz *bk = (blockIdx.z ? bk1 : bk0) + ((size_t)slot * VC_W + win) * VC_D;
+    const size_t p0 = (size_t)slot * VCB_S;
+    const uint32_t m = (uint32_t)(n - p0 < VCB_S ? n - p0 : VCB_S);  // the grid has ceil(n / S) slices: p0 < n
+    cnt[t] = 0;
+    __syncthreads();
+    for (uint32_t p = t; p < m; p += 128) {
+        const int d = vc_digit(sc[p0 + p].v, (int)win);
+        const uint32_t mag = (uint32_t)(d < 0 ? -d : d);  // <= 128
+        dig[p] = (uint16_t)(mag | (d < 0 ? 0x8000u : 0u));
+        if (mag) atomicAdd(&cnt[mag - 1], 1u);
+    }
+    __syncthreads();
+    uint32_t first = 0;
+    for (uint32_t b = 0; b < t; b++) first += cnt[b];
+    cur[t] = first;
+    __syncthreads();
+    for (uint32_t p = t; p < m; p += 128) {
+        const uint32_t d = dig[p], mag = d & 0x7fffu;
+        if (mag) ent[atomicAdd(&cur[mag - 1], 1u)] = (uint16_t)(p | (d & 0x8000u));  // a slot below the slice's count of non-zero digits
+    }
+    __syncthreads();
+    const uint32_t len = cnt[t];
+    if (!len) return;
+    G1Xyzz acc = bk[t];
+    for (uint32_t e = first; e < first + len; e++) {
+        const uint32_t x = ent[e];
+        G1Affine p = vcb_point(pts, p0 + (x & 0x7fffu));
+        if (x & 0x8000u) p = g1_neg(p);
+        acc = g1_madd(acc, p);
+    }
+    bk[t] = acc;
+}
+
+// Workgroup (window, set): thread b folds the `slots` slice slots of bucket b + 1, then the 128 buckets become sum_b (b + 1) B_b by a
+// suffix scan (7 rounds) and a tree sum of the suffixes (7 rounds) in LDS.  out[set][window].
+__global__ __launch_bounds__(128) void k_vcb_reduce(const G1Xyzz *bk, uint32_t slots, G1Xyzz *out) {
+    __shared__ G1Xyzz sh[VC_D];
+    const uint32_t t = threadIdx.x, win = blockIdx.x, set = blockIdx.y;
+    const G1Xyzz *b = bk + (size_t)set * VCB_G * VCB_SET + (size_t)win * VC_D + t;
+    G1Xyzz acc = b[0];
+    for (uint32_t g = 1; g < slots; g++) acc = g1_add(acc, b[(size_t)g * VCB_SET]);
+    sh[t] = acc;
+    __syncthreads();
+    for (uint32_t s = 1; s < VC_D; s <<= 1) {  // suffix sums: sh[t] = sum_{u >= t} B_u
+        const bool on = t + s < VC_D;
+        G1Xyzz o;
+        if (on) o = sh[t + s];
+        __syncthreads();
+        if (on) {
+            acc = g1_add(acc, o);
+            sh[t] = acc;
+        }
+        __syncthreads();
+    }
+    for (uint32_t s = VC_D / 2; s >= 1; s >>= 1) {
+        if (t < s) sh[t] = g1_add(sh[t], sh[t + s]);
+        __syncthreads();
+    }
+    if (t == 0) out[(size_t)set * VC_W + win] = sh[0];
+}
+
+// the finish on the GPU (option host_pairing = 0): the three Horner chains side by side on lanes 0 .. 2 of the one wave (lockstep: the
+// time of one chain), then one thread for the pairing check, as k_vc_check
+__global__ __launch_bounds__(64) void k_vcb_finish(const VcbSums *sums, const G2Affine *hq, const Fq2 *lines, uint8_t *ok, G1Affine *parts) {
+    __shared__ G1Xyzz tot[3];
+    if (blockIdx.x) return;
+    if (threadIdx.x < 3) vcb_horner(tot[threadIdx.x], sums->win[threadIdx.x]);
+    __syncthreads();
+    if (threadIdx.x == 0) ok[0] = vcb_check(tot, sums->ragg, hq, lines, parts) ? 1 : 0;
+}
+
+namespace {
+inline unsigned vcb_grid(size_t n, unsigned b = 256) { return (unsigned)((n + b - 1) / b); }
+
+// buckets of `sets` scalar sets += the digits' multiples of n points (n <= VCB_G x VCB_S)
+template <class PT>
+int vb_accumulate(kzg_ctx *ctx, hipStream_t st, const PT *d_pts, const Fr *sc0, const Fr *sc1, size_t n, G1Xyzz *bk0, G1Xyzz *bk1, int sets) {
+    if (!n) return KZG_OK;
+    KZG_LAUNCH(ctx, st, "k_vcb_bucket", k_vcb_bucket<PT>, dim3(vcb_grid(n, VCB_S), VC_W, sets), 128, 0, d_pts, sc0, sc1, n, bk0, bk1);
+    return KZG_OK;
+}
+
+struct BatchParts {  // the extra outputs of kzg_test_verify_cosets_batch_parts (host)
+    void *a = nullptr, *cw = nullptr, *points = nullptr;
+};
+
+int load_challenge(kzg_ctx *ctx, const void *r, int sfmt, Fr *mont) {
+    Fr x;
+    memcpy(x.v, r, 32);
+    if (!is_canonical(x) || x.is_zero()) return fail(ctx, KZG_ERR_SHAPE, "kzg_verify_cosets_batch: the challenge r must be in [1, modulus)");
+    *mont = sfmt == KZG_FR_MONT_LE_32 ? x : to_mont(x);
+    return KZG_OK;
+}
+
+int vcb_run(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitments, size_t n_commitments, const uint32_t *commitment_idx,
+            const size_t *coset_ids, const void *cells, const void *proofs, size_t count, const void *r, int sfmt, int pfmt, int flags, int *ok,
+            const BatchParts *parts) {
+    const char *who = "kzg_verify_cosets_batch";
+    // ---- shape: everything is decided before memory is touched or a kernel launched (the rules of kzg_verify_cosets) ----
+    if (!ctx) return KZG_ERR_SHAPE;
+    if (!plan) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL plan");
+    if (sfmt != KZG_FR_MONT_LE_32 && sfmt != KZG_FR_CANONICAL_LE_32) return fail(ctx, KZG_ERR_SHAPE, "unknown scalar format");
+    const size_t psz = point_format_bytes(pfmt);
+    if (!psz || pfmt == KZG_G1_JACOBIAN_MONT_144) return fail(ctx, KZG_ERR_SHAPE, "commitments / proofs are affine (G1Affine)");
+    if (plan->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the plan is resident on another GPU than this context's");
+    if (!count) {
+        if (ok) *ok = 1;
+        return KZG_OK;
+    }
+    if (!commitments || !commitment_idx || !coset_ids || !cells || !proofs || !r || !ok) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL argument");
+    Fr rm;
+    KZG_TRY(load_challenge(ctx, r, sfmt, &rm));
+    const uint32_t log_l = plan->log_l;
+    const size_t l = (size_t)1 << log_l, K = (size_t)1 << (plan->log_n - log_l);
+    if (count > (SIZE_MAX >> 6) / l || n_commitments > (SIZE_MAX >> 9)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": count too large");
+    const size_t chunk = vc_chunk(ctx, plan), B0 = std::min(chunk, count), BP = std::min(chunk, std::max(count, n_commitments));
+    std::vector<uint32_t> meta, cnt, which, start, order;  // ids, then commitment indices, as the kernels read them; the counting sort
+    try {  // (no exception may leave through the C ABI)
+        meta.resize(2 * count);
+        cnt.assign(n_commitments, 0);
+        which.resize(B0);
+        start.resize(B0 + 1);
+        order.resize(B0);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, KZG_ERR_ALLOC, std::string(who) + ": host memory for the ids");
+    }
+    for (size_t k = 0; k < count; k++) {
+        if (coset_ids[k] >= K) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": coset id >= K");
+        if (commitment_idx[k] >= n_commitments) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": commitment index >= n_commitments");
+        meta[k] = (uint32_t)coset_ids[k];
+        meta[count + k] = commitment_idx[k];
+    }
+
+    kzg::Lease ls;
+    KZG_TRY(lease_lane(ctx, &ls));
+    const int lane = ls.lane;
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->lanes[lane].stream;
+    const bool in_dev = (flags & KZG_IN_DEVICE) != 0;
+    const size_t fold_blocks = (B0 + VCB_FOLD_CELLS - 1) / VCB_FOLD_CELLS, bucket_bytes = 3 * (size_t)VCB_G * VCB_SET * sizeof(G1Xyzz);
+    KZG_TRY(lane_reserve(ctx, lane, bucket_bytes + sizeof(VcbSums) + n_commitments * 32 + BP * (psz + sizeof(G1Xyzz)) +
+                                        B0 * (4 * 4 + 3 * 32 + (in_dev ? 1 : 2) * l * 32) + (fold_blocks + 1) * l * 32 + 65536));
+    struct Drain {  // nothing of the call is in flight once its host-side buffers go out of scope
+        hipStream_t st;
+        ~Drain() { hipStreamSynchronize(st); }
+    } drain{st};
+    int *bad = (int *)lane_alloc(ctx, lane, 256);
+    uint8_t *d_ok = (uint8_t *)lane_alloc(ctx, lane, 256);
+    G1Affine *d_parts = (G1Affine *)lane_alloc(ctx, lane, 4 * sizeof(G1Affine));
+    G1Xyzz *bk = (G1Xyzz *)lane_alloc(ctx, lane, bucket_bytes);
+    VcbSums *sums = (VcbSums *)lane_alloc(ctx, lane, sizeof(VcbSums));
+    Fr *d_a = (Fr *)lane_alloc(ctx, lane, l * 32), *d_part = (Fr *)lane_alloc(ctx, lane, fold_blocks * l * 32);
+    Fr *d_c = (Fr *)lane_alloc(ctx, lane, std::max<size_t>(n_commitments, 1) * 32);
+    uint32_t *d_ids = (uint32_t *)lane_alloc(ctx, lane, B0 * 4), *d_which = (uint32_t *)lane_alloc(ctx, lane, B0 * 4);
+    uint32_t *d_start = (uint32_t *)lane_alloc(ctx, lane, (B0 + 1) * 4), *d_order = (uint32_t *)lane_alloc(ctx, lane, B0 * 4);
+    Fr *d_rho = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_s1 = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_s2 = (Fr *)lane_alloc(ctx, lane, B0 * 32);
+    Fr *d_cells = in_dev ? nullptr : (Fr *)lane_alloc(ctx, lane, B0 * l * 32), *d_r = (Fr *)lane_alloc(ctx, lane, B0 * l * 32);
+    uint8_t *raw = (uint8_t *)lane_alloc(ctx, lane, BP * psz);
+    G1Xyzz *W = (G1Xyzz *)lane_alloc(ctx, lane, BP * sizeof(G1Xyzz));
+    if (!bad || !d_ok || !d_parts || !bk || !sums || !d_a || !d_part || !d_c || !d_ids || !d_which || !d_start || !d_order || !d_rho || !d_s1 ||
+        !d_s2 || (!in_dev && !d_cells) || !d_r || !raw || !W)
+        return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    G1Xyzz *bk1 = bk, *bk2 = bk + (size_t)VCB_G * VCB_SET, *bk3 = bk + 2 * (size_t)VCB_G * VCB_SET;
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(bad, 0, sizeof(int), st));
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(bk, 0, bucket_bytes, st));  // zz = 0: the identity
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(d_a, 0, l * 32, st));
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(d_c, 0, std::max<size_t>(n_commitments, 1) * 32, st));
+    size_t slots = 0;  // slice slots any chunk has used
+    for (size_t k0 = 0; k0 < count; k0 += chunk) {
+        const size_t B = std::min(chunk, count - k0);
+        // the chunk's cells listed per commitment, commitments in the order of their first cell
+        size_t lists = 0;
+        const uint32_t *cm = meta.data() + count + k0;
+        for (size_t k = 0; k < B; k++)
+            if (!cnt[cm[k]]++) which[lists++] = cm[k];
+        uint32_t at = 0;
+        for (size_t g = 0; g < lists; g++) {
+            start[g] = at;
+            at += cnt[which[g]];
+            cnt[which[g]] = start[g];
+        }
+        start[lists] = at;
+        for (size_t k = 0; k < B; k++) order[cnt[cm[k]]++] = (uint32_t)k;
+        for (size_t g = 0; g < lists; g++) cnt[which[g]] = 0;
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_ids, meta.data() + k0, B * 4, hipMemcpyHostToDevice, st));
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_which, which.data(), lists * 4, hipMemcpyHostToDevice, st));
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_start, start.data(), (lists + 1) * 4, hipMemcpyHostToDevice, st));
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_order, order.data(), B * 4, hipMemcpyHostToDevice, st));
+        const Fr *src = (const Fr *)((const uint8_t *)cells + k0 * l * 32);
+        if (!in_dev) {
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_cells, src, B * l * 32, hipMemcpyHostToDevice, st));
+            src = d_cells;
+        }
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)proofs + k0 * psz, B * psz, hipMemcpyHostToDevice, st));
+        KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
+        KZG_TRY(powers_run(ctx, st, rm, k0, B, d_rho));
+        KZG_TRY(vc_interp(ctx, st, plan, src, d_ids, B, d_r));
+        KZG_LAUNCH(ctx, st, "k_vcb_scalars", k_vcb_scalars, vcb_grid(B), 256, 0, (const Fr *)d_rho, (const uint32_t *)d_ids, B, log_l,
+                   (const Fr *)plan->pos_lo, (const Fr *)plan->pos_hi, d_s1, d_s2);
+        const uint32_t fb = vcb_grid(B, VCB_FOLD_CELLS);
+        KZG_LAUNCH(ctx, st, "k_vcb_fold", k_vcb_fold, fb, 256, 0, (const Fr *)d_r, (const Fr *)d_rho, B, log_l, d_part);
+        KZG_LAUNCH(ctx, st, "k_vcb_fold2", k_vcb_fold2, vcb_grid(l), 256, 0, (const Fr *)d_part, fb, (uint32_t)l, d_a);
+        KZG_LAUNCH(ctx, st, "k_vcb_cweights", k_vcb_cweights, (unsigned)lists, 64, 0, (const Fr *)d_rho, (const uint32_t *)d_which,
+                   (const uint32_t *)d_start, (const uint32_t *)d_order, d_c);
+        KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_s1, d_s2, B, bk1, bk2, 2));
+        slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
+        // the host lists and the chunk's device buffers are free again
+        KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    }
+    // Cagg: the commitments against the canonical c, in chunks like the cells (d_s1 holds a chunk's scalars)
+    for (size_t m0 = 0; m0 < n_commitments; m0 += BP) {
+        const size_t B = std::min(BP, n_commitments - m0);
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)commitments + m0 * psz, B * psz, hipMemcpyHostToDevice, st));
+        KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
+        KZG_LAUNCH(ctx, st, "k_vcb_canon", k_vcb_canon, vcb_grid(B), 256, 0, (const Fr *)(d_c + m0), B, 1, d_c + m0);
+        KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_c + m0, d_c + m0, B, bk3, bk3, 1));
+        slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
+    }
+    KZG_LAUNCH(ctx, st, "k_vcb_reduce", k_vcb_reduce, dim3(VC_W, 3), 128, 0, (const G1Xyzz *)bk, (uint32_t)slots, &sums->win[0][0]);
+    KZG_TRY(vc_sum(ctx, st, plan, d_a, 1, sfmt, &sums->ragg));
+
+    const bool on_host = ctx->opt_host_pairing != 0;
+    KZG_TRY(lane_pinned(ctx, lane, 1024 + sizeof(VcbSums)));
+    char *pin = ctx->lanes[lane].pinned;
+    if (!on_host) {
+        KZG_LAUNCH(ctx, st, "k_vcb_finish", k_vcb_finish, 1, 64, 0, (const VcbSums *)sums, (const G2Affine *)plan->hq, (const Fq2 *)plan->lines, d_ok,
+                   parts ? d_parts : (G1Affine *)nullptr);
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin + 64, d_ok, 1, hipMemcpyDeviceToHost, st));
+        if (parts) KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin + 128, d_parts, 4 * sizeof(G1Affine), hipMemcpyDeviceToHost, st));
+    } else {
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin + 1024, sums, sizeof(VcbSums), hipMemcpyDeviceToHost, st));
+    }
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin, bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (parts) {
+        if (sfmt == KZG_FR_MONT_LE_32) KZG_LAUNCH(ctx, st, "k_vcb_canon", k_vcb_canon, vcb_grid(l), 256, 0, (const Fr *)d_a, l, 1, d_a);
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(parts->a, d_a, l * 32, hipMemcpyDeviceToHost, st));
+        if (n_commitments) KZG_HIP_CHECK(ctx, hipMemcpyAsync(parts->cw, d_c, n_commitments * 32, hipMemcpyDeviceToHost, st));
+    }
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    KZG_HIP_CHECK(ctx, hipGetLastError());
+    if (ctx->prof) prof_collect(ctx);
+    // the decode flag before the verdict, as fetch_ok
+    if (*(int *)pin) return fail(ctx, KZG_ERR_BAD_POINT, "an input point failed to decode, is not on the curve or not in the r-torsion subgroup");
+    int verdict;
+    if (on_host) {
+        const auto t0 = std::chrono::steady_clock::now();
+        verdict = vcb_finish(*(const VcbSums *)(pin + 1024), plan->h_hq, plan->h_lines, parts ? (G1Affine *)(pin + 128) : nullptr) ? 1 : 0;
+        if (ctx->prof) {  // the calling thread's share of the call, beside the kernels of kzg_prof_get
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            std::lock_guard<std::mutex> lk(ctx->prof_mu);
+            ProfEntry &e = ctx->prof_map["vcb_host_finish"];
+            e.launches++;
+            e.total_ms += ms;
+        }
+    } else {
+        verdict = pin[64] ? 1 : 0;
+    }
+    if (parts) memcpy(parts->points, pin + 128, 4 * sizeof(G1Affine));
+    *ok = verdict;
+    return KZG_OK;
+}
+}  // namespace
+
+}  // namespace kzg
+
+using namespace kzg;
+
+extern "C" int kzg_verify_cosets_batch(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitments, size_t n_commitments,
+                                       const uint32_t *commitment_idx, const size_t *coset_ids, const void *cells, const void *proofs,
+                                       size_t count, const void *r, int sfmt, int pfmt, int flags, int *ok) {
+    return vcb_run(ctx, plan, commitments, n_commitments, commitment_idx, coset_ids, cells, proofs, count, r, sfmt, pfmt, flags, ok, nullptr);
+}
+
+#ifdef KZG_TEST_HOOKS
+#include "../../include/kzg_mi355x_test.h"
+extern "C" int kzg_test_verify_cosets_batch_parts(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitments, size_t n_commitments,
+                                                  const uint32_t *commitment_idx, const size_t *coset_ids, const void *cells, const void *proofs,
+                                                  size_t count, const void *r, int sfmt, int pfmt, int flags, int *ok, void *out_a, void *out_cw,
+                                                  void *out_points) {
+    if (!out_a || !out_cw || !out_points || !count) return KZG_ERR_SHAPE;
+    BatchParts parts;
+    parts.a = out_a;
+    parts.cw = out_cw;
+    parts.points = out_points;
+    return vcb_run(ctx, plan, commitments, n_commitments, commitment_idx, coset_ids, cells, proofs, count, r, sfmt, pfmt, flags, ok, &parts);
+}
+
+// the variable-base routine alone over row 0 of a resident SRS: out = sum_i scalars[i] srs[offset + i], affine Montgomery
+extern "C" int kzg_test_vb_msm(kzg_ctx *ctx, const kzg_srs *srs, size_t offset, const void *scalars, size_t n, int sfmt, void *out) {
+    if (!ctx || !srs || !scalars || !out || !n) return KZG_ERR_SHAPE;
+    if (sfmt != KZG_FR_MONT_LE_32 && sfmt != KZG_FR_CANONICAL_LE_32) return KZG_ERR_SHAPE;
+    if (offset > srs->n || n > srs->n - offset || srs->device != ctx->device) return KZG_ERR_SHAPE;
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->lanes[0].stream;
+    const size_t CH = (size_t)VCB_G * VCB_S, B0 = std::min(CH, n), set_bytes = (size_t)VCB_G * VCB_SET * sizeof(G1Xyzz);
+    KZG_TRY(lane_reserve(ctx, 0, 3 * set_bytes + sizeof(VcbSums) + B0 * 64 + 65536));
+    G1Xyzz *bk = (G1Xyzz *)lane_alloc(ctx, 0, 3 * set_bytes);  // k_vcb_reduce walks three sets: two stay empty
+    VcbSums *sums = (VcbSums *)lane_alloc(ctx, 0, sizeof(VcbSums));
+    Fr *d_in = (Fr *)lane_alloc(ctx, 0, B0 * 32), *d_sc = (Fr *)lane_alloc(ctx, 0, B0 * 32);
+    G1Affine *d_out = (G1Affine *)lane_alloc(ctx, 0, 4 * sizeof(G1Affine));
+    uint8_t *d_ok = (uint8_t *)lane_alloc(ctx, 0, 256);
+    if (!bk || !sums || !d_in || !d_sc || !d_out || !d_ok) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(bk, 0, 3 * set_bytes, st));
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(sums, 0, sizeof(VcbSums), st));
+    size_t slots = 0;
+    for (size_t i0 = 0; i0 < n; i0 += CH) {
+        const size_t B = std::min(CH, n - i0);
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_in, (const uint8_t *)scalars + i0 * 32, B * 32, hipMemcpyHostToDevice, st));
+        KZG_LAUNCH(ctx, st, "k_vcb_canon", k_vcb_canon, vcb_grid(B), 256, 0, (const Fr *)d_in, B, sfmt == KZG_FR_MONT_LE_32 ? 1 : 0, d_sc);
+        KZG_TRY(vb_accumulate(ctx, st, (const G1Affine *)srs->table + offset + i0, d_sc, d_sc, B, bk, bk, 1));
+        slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
+        KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    }
+    KZG_LAUNCH(ctx, st, "k_vcb_reduce", k_vcb_reduce, dim3(VC_W, 3), 128, 0, (const G1Xyzz *)bk, (uint32_t)slots, &sums->win[0][0]);
+    VcbSums h;
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(&h, sums, sizeof(VcbSums), hipMemcpyDeviceToHost, st));
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    KZG_HIP_CHECK(ctx, hipGetLastError());
+    G1Xyzz sum;
+    vcb_horner(sum, h.win[0]);
+    const G1Affine a = g1_to_affine(sum);
+    memcpy(out, &a, sizeof(G1Affine));
+    return KZG_OK;
+}
+#endif
