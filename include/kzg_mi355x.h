@@ -71,6 +71,8 @@ extern "C" {
  *                                                                             393 KiB x l: 25 MB at l = 64, 101 MB at l = 256, the bound)
  *   kzg_verify_cosets_batch                 the plan's limits; any count: the workspace is 3 x 8 x 32 x 128 buckets of 192 B (18.9 MB)
  *                                                                             beside one chunk's buffers and 32 B per commitment
+ *   kzg_verify_eval_batch                   any count: the same three bucket sets beside one chunk's buffers (16,384 openings), and
+ *                                                                             32 B per commitment when indices are given
  *   MSM                                     table rows x points < 2^31       (the sorted entry is a 31-bit table index + sign);
  *                                           window_bits 18, 19 (option), and 20 with option sort_single_pass: windows x points < 2^27
  *   kzg_g1_sum_batch                        count <= 2^20, groups <= 2^24
@@ -150,7 +152,8 @@ int kzg_sync(kzg_ctx *ctx);
  * 128 B per point, scalars recoded in width-18 non-adjacent form -- 13.9 instead of 15 bucket additions per scalar for 17x the
  * table: 34 GB at 2^20; measured +3.7 % batched throughput at 2^20, nothing below 2^19, +1.3 ms on a lone commit: opt-in);
  * "verify_cosets_chunk" (0 = default; n: kzg_verify_cosets works in chunks of at most n cells),
- * "host_pairing" (1 / 0: the one pairing check that ends kzg_verify_cosets_batch runs on the calling thread -- the same tower code
+ * "verify_eval_batch_chunk" (0 = default, 16384; n <= 16384: kzg_verify_eval_batch works in chunks of at most n openings),
+ * "host_pairing" (1 / 0: the one pairing check that ends kzg_verify_cosets_batch / kzg_verify_eval_batch runs on the calling thread -- the same tower code
  *  compiled for the host -- instead of in a one-thread kernel; the same verdict, default 1),
  * "fk20_cosets_combine" (0 = the shared-doubling Straus kernel, default; 1 = one mul256 per term: the same bytes, for comparison),
  * unknown keys -> KZG_ERR_SHAPE */
@@ -559,6 +562,36 @@ int kzg_verify_cosets(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void 
 int kzg_verify_cosets_batch(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitments, size_t n_commitments,
                             const uint32_t *commitment_idx, const size_t *coset_ids, const void *cells, const void *proofs,
                             size_t count, const void *r, int sfmt, int pfmt, int flags, int *ok);
+/* "Are all of these openings good?" for single-point openings: ONE verdict for the whole call from one pairing check (the
+ * verify_kzg_proof_batch / verify_blob_kzg_proof_batch shape of the data-availability specifications; not a reference method).
+ * Opening k claims p_{m_k}(x_k) = y_k with the witness witnesses[k], where m_k = commitment_idx[k] names one of the n_commitments
+ * points of `commitments`; commitment_idx == NULL means m_k = k and requires n_commitments == count (one commitment per opening).
+ * With the challenge r (one host scalar in sfmt) the equations of kzg_verify_eval are weighted by rho_k = r^k, k = 0 .. count - 1,
+ * and summed:
+ *   P1 = sum_k rho_k pi_k,  P2 = sum_k (rho_k x_k) pi_k;   c_m = sum_{k: m_k = m} rho_k,  Cagg = sum_m c_m C_m;
+ *   yagg = sum_k rho_k y_k;   *ok = [ e(P1, hs[1]) e(-(P2 + Cagg - [yagg] gs[0]), hs[0]) == 1 ].
+ * Per opening that is 2 x 32 (3 x 32 without indices) bucket additions of a variable-base multi-scalar sum; the pairing check happens
+ * once per call.  xs, ys, the points, the indices and r are host memory.  xs and ys (count scalars each, sfmt) are taken as
+ * kzg_verify_eval takes them: they are not range-checked, and a value >= the modulus counts as its residue.  pfmt: any affine format.
+ * Duplicate openings, the identity witness (a constant polynomial), the identity commitment and commitments that no opening names
+ * (c_m = 0; they are validated all the same) are allowed.
+ * WHAT THE CALLER OWES.  The verdict is sound only if r is unpredictable to whoever produced the openings: draw it at random AFTER the
+ * points, values, witnesses and commitments have been received, or derive it as a hash of ALL inputs of the call, as the consensus
+ * specifications do (the library has no hash, and the domain separation is the protocol's business).  With a predictable r a forger
+ * can make errors cancel: with r = 1, pi_a + D and pi_b - D at one common x pass while both openings fail alone.  Honest openings
+ * pass for every r.  *ok == 0 says nothing about WHICH opening is bad: follow it with kzg_verify_eval.
+ * KZG_ERR_SHAPE, before any memory is touched and with *ok unwritten: r == 0 (only opening 0 would be checked) or r >= modulus, gs
+ * without a point or hs with fewer than two, an index >= n_commitments, NULL indices with n_commitments != count, an unknown format,
+ * a Jacobian pfmt, a NULL pointer with count > 0, an SRS on another GPU.  count == 0: *ok = 1 (if ok is non-NULL), KZG_OK -- of
+ * the errors above only the formats and the SRS (NULL, too short, another GPU) are looked at then, not r, the pointers or n_commitments,
+ * as in kzg_verify_cosets_batch.  Points are
+ * validated as in kzg_verify_eval (option "trusted_points"): a malformed, off-curve or out-of-subgroup commitment or witness makes
+ * the call return KZG_ERR_BAD_POINT and leaves *ok unwritten.  Leases one lane like the other blocking calls (concurrent callers run
+ * side by side); works in chunks of at most 16384 openings (option "verify_eval_batch_chunk" lowers it), so the workspace does not
+ * grow with `count` (Limits).  Option "host_pairing" chooses where the one pairing check runs. */
+int kzg_verify_eval_batch(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *xs, const void *ys, int sfmt,
+                          const void *commitments, size_t n_commitments, const uint32_t *commitment_idx, const void *witnesses, int pfmt,
+                          size_t count, const void *r, int *ok);
 
 /* ---- Fr polynomial helpers on the path (device) ---------------------------------------------- */
 /* Polynomial::eval (src/polynomial.rs:156-165) at one point. */

@@ -265,6 +265,25 @@ class KZGVerifier {  // src/coeff_form.rs:114-183; the pairing checks run on the
                                  c.bytes.data(), w.bytes.data(), KZG_G1_AFFINE_MONT_96, 1, &ok));
         return ok != 0;
     }
+    // kzg_verify_eval_batch: true iff ALL the openings verify, from one pairing check of their combination with the weights r^k.
+    // Opening k claims p(xs[k]) = ys[k] for commitments[commitment_idx[k]]; an empty commitment_idx means one commitment per opening.
+    // r must be unpredictable to whoever produced the openings (drawn after they arrived, or the hash of all inputs): see the header.
+    // false says nothing about which opening is bad: verify_eval() does.
+    bool verify_eval_batch(const std::vector<Scalar> &xs, const std::vector<Scalar> &ys, const std::vector<KZGCommitment> &commitments,
+                           const std::vector<uint32_t> &commitment_idx, const std::vector<KZGWitness> &witnesses, const Scalar &r) const {
+        if (!params_.hs) throw ReferencePanic("KZGParams.hs is empty (index out of bounds)");
+        const size_t count = xs.size();
+        if (ys.size() != count || witnesses.size() != count || (!commitment_idx.empty() && commitment_idx.size() != count))
+            throw ReferencePanic("verify_eval_batch: shape");
+        std::vector<uint8_t> cb(commitments.size() * 96), wb(count * 96);
+        for (size_t i = 0; i < commitments.size(); i++) std::memcpy(cb.data() + 96 * i, commitments[i].bytes.data(), 96);
+        for (size_t i = 0; i < count; i++) std::memcpy(wb.data() + 96 * i, witnesses[i].bytes.data(), 96);
+        int ok = 0;
+        e_.check(kzg_verify_eval_batch(e_.ctx(), params_.gs, params_.hs, xs.data(), ys.data(), KZG_FR_CANONICAL_LE_32, cb.data(),
+                                       commitments.size(), commitment_idx.empty() ? nullptr : commitment_idx.data(), wb.data(),
+                                       KZG_G1_AFFINE_MONT_96, count, r.le.data(), &ok));
+        return ok != 0;
+    }
     bool verify_eval_batched(const std::vector<Scalar> &xs, const KZGCommitment &c, const KZGBatchWitness &w) const {  // :144-182
         if (!params_.hs) throw ReferencePanic("KZGParams.hs is empty (index out of bounds)");
         int ok = 0;

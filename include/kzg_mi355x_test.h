@@ -90,6 +90,13 @@ int kzg_test_verify_cosets_batch_parts(kzg_ctx *ctx, const kzg_cosets_verifier *
                                        const uint32_t *commitment_idx, const size_t *coset_ids, const void *cells, const void *proofs,
                                        size_t count, const void *r, int sfmt, int pfmt, int flags, int *ok, void *out_a, void *out_cw,
                                        void *out_points);
+/* kzg_verify_eval_batch with its intermediate results: out_yagg = the scalar sum_k rho_k y_k, out_cw = the n_commitments scalars c_m
+ * (both canonical), out_points = the four points the finish consumes (4 x affine Montgomery 96 B): P1, P2, the total of the third
+ * bucket set = Cagg - [yagg] gs[0], and the Ragg slot, which this call leaves the identity.  count > 0 */
+int kzg_test_verify_eval_batch_parts(kzg_ctx *ctx, const struct kzg_srs *gs, const struct kzg_srs_g2 *hs, const void *xs, const void *ys,
+                                     int sfmt, const void *commitments, size_t n_commitments, const uint32_t *commitment_idx,
+                                     const void *witnesses, int pfmt, size_t count, const void *r, int *ok, void *out_yagg, void *out_cw,
+                                     void *out_points);
 int kzg_test_arith(kzg_ctx *ctx, int op, const void *in, size_t in_rec, size_t n, void *out, size_t out_rec);
 /* pretend `srs` is resident on GPU `device` (the "SRS of another GPU" error of every MSM entry point, on a one-GPU box) */
 int kzg_test_srs_set_device(struct kzg_srs *srs, int device);

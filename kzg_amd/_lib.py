@@ -140,6 +140,7 @@ def load(path=None):
         "kzg_verify_cosets": (i32, [vp, vp, vp, sz, ctypes.POINTER(u32), ctypes.POINTER(sz), vp, vp, sz, i32, i32, i32, vp]),
         "kzg_verify_cosets_batch": (i32, [vp, vp, vp, sz, ctypes.POINTER(u32), ctypes.POINTER(sz), vp, vp, sz, vp, i32, i32, i32,
                                           ctypes.POINTER(i32)]),
+        "kzg_verify_eval_batch": (i32, [vp, vp, vp, vp, vp, i32, vp, sz, ctypes.POINTER(u32), vp, i32, sz, vp, ctypes.POINTER(i32)]),
         "kzg_poly_eval": (i32, [vp, vp, sz, vp, i32, i32, vp]),
         "kzg_quotient_linear": (i32, [vp, vp, sz, vp, vp, i32, i32, vp]),
         "kzg_quotient_eval": (i32, [vp, vp, sz, sz, i32, i32, vp]),

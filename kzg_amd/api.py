@@ -1182,6 +1182,39 @@ class KZGVerifier:
             _raise(e, rc)
         return [bool(b) for b in ok.raw[:n]]
 
+    def verify_eval_batch(self, points, commitments, witnesses, r=None, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
+        """kzg_verify_eval_batch (not a reference method): True iff ALL the openings verify, from one pairing check of their
+        combination with the weights r^k.  points[k] = (x_k, y_k) and witnesses[k] open commitments[commitment_idx[k]];
+        commitment_idx=None: one commitment per opening.  r: the challenge, an int in [1, R).  r=None draws it here with `secrets`
+        -- sound because it is drawn after the openings were handed over; a protocol that needs a reproducible verdict passes the
+        hash of all inputs.  False says nothing about which opening is bad: verify_eval_many() does (verify_eval_with_fallback)."""
+        e = self.engine
+        count = len(points)
+        if len(witnesses) != count or (commitment_idx is not None and len(commitment_idx) != count):
+            raise ReferencePanic("verify_eval_batch: one point, witness and commitment index per opening")
+        if r is None:
+            r = secrets.randbelow(R_MODULUS - 1) + 1
+        if not 1 <= int(r) < R_MODULUS:
+            raise ReferencePanic("verify_eval_batch: the challenge r must be in [1, R)")
+        idx = None
+        if commitment_idx is not None:
+            idx = (ctypes.c_uint32 * max(count, 1))(*[int(i) % (1 << 32) for i in commitment_idx])
+        ok = ctypes.c_int(-1)
+        rc = e.lib.kzg_verify_eval_batch(e.ctx, self.parameters.gs.handle, self._hs().handle, pack_scalars([p[0] for p in points]),
+                                         pack_scalars([p[1] for p in points]), L.FR_CANONICAL, b"".join(commitments), len(commitments),
+                                         idx, b"".join(witnesses), pfmt, count, int(r).to_bytes(32, "little"), ctypes.byref(ok))
+        if rc:
+            _raise(e, rc)
+        return bool(ok.value)
+
+    def verify_eval_with_fallback(self, points, commitments, witnesses, r=None, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
+        """One verdict per opening, as verify_eval_many(): the batch check first, and the per-opening checks only when it says no."""
+        if self.verify_eval_batch(points, commitments, witnesses, r, commitment_idx, pfmt):
+            return [True] * len(points)
+        if commitment_idx is not None:
+            commitments = [commitments[i] for i in commitment_idx]
+        return self.verify_eval_many(points, commitments, witnesses, pfmt)
+
     def verify_eval_batched(self, xs, commitment, witness, pfmt=L.G1_AFFINE_MONT):  # :144-182
         e = self.engine
         r = witness.r
@@ -1319,6 +1352,25 @@ class KZGVerifierEvalForm:
     def verify_eval(self, point, commitment, witness, pfmt=L.G1_AFFINE_MONT):  # :173-190
         i, y = point
         return KZGVerifier(self.parameters).verify_eval((pow(self.omega, i, R_MODULUS), y), commitment, witness, pfmt)
+
+    def _at_omega(self, points):
+        return [(pow(self.omega, i, R_MODULUS), y) for i, y in points]
+
+    def verify_eval_batch(self, points, commitments, witnesses, r=None, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
+        """KZGVerifier.verify_eval_batch with points[k] = (i_k, y_k) as verify_eval takes them: opening k is at omega^i_k."""
+        return KZGVerifier(self.parameters).verify_eval_batch(self._at_omega(points), commitments, witnesses, r, commitment_idx, pfmt)
+
+    def verify_eval_with_fallback(self, points, commitments, witnesses, r=None, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
+        """One verdict per opening (points[k] = (i_k, y_k)): the batch check first, the per-opening checks only when it says no."""
+        return KZGVerifier(self.parameters).verify_eval_with_fallback(self._at_omega(points), commitments, witnesses, r, commitment_idx, pfmt)
+
+    def verify_open_at_batch(self, evals, zs, commitments, witnesses, r=None, pfmt=L.G1_AFFINE_MONT):
+        """The blob-level check: witnesses[b] opens the polynomial with the evaluations evals[b] and the commitment commitments[b]
+        at zs[b] (any point of Fr; what KZGProverEvalForm.open_at_batch produced).  The claimed values p_b(zs[b]) are computed from
+        the evaluations (Engine.eval_form_eval; 32 bytes each come back to the host), then one verify_eval_batch.  evals as
+        eval_form_eval takes them; r as verify_eval_batch."""
+        ys = self.engine.eval_form_eval(evals, zs, self.d)
+        return KZGVerifier(self.parameters).verify_eval_batch(list(zip(zs, ys)), commitments, witnesses, r, None, pfmt)
 
     def verify_eval_all(self, ys, commitment, witness, pfmt=L.G1_AFFINE_MONT):  # :192-217
         e = self.engine

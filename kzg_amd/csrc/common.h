@@ -141,7 +141,8 @@ struct kzg_ctx {
     int opt_trusted_points = 0;        // 1: caller vouches for its points (skip the subgroup check of uploads / verifier inputs)
     int opt_ntt_vec_log = 2;           // NTT passes: 2^v adjacent columns / rows per LDS tile
     int opt_verify_cosets_chunk = 0;   // kzg_verify_cosets: at most this many cells per chunk (0 = the rule min(16384, 2^20 / l) alone)
-    int opt_host_pairing = 1;          // kzg_verify_cosets_batch: its one pairing check runs on the calling thread (vcb_finish.h); 0 = in a one-thread kernel
+    int opt_verify_eval_batch_chunk = 0;  // kzg_verify_eval_batch: at most this many openings per chunk (0 = 16384 alone)
+    int opt_host_pairing = 1;          // kzg_verify_cosets_batch, kzg_verify_eval_batch: the one pairing check runs on the calling thread (vcb_finish.h); 0 = in a one-thread kernel
     int opt_fk20_cosets_combine = 0;   // the coset combination of kzg_witness_cosets_*: 0 = Straus (shared doublings), 1 = mul256 per term
     int opt_ntt_kernel = KZG_NTT_KERNEL_DEFAULT;  // 0: three-phase passes (k_ntt_pass1/2); 1: load/store fused into the first/last stage pair (k_ntt_tile); 2: 1 + two butterflies per thread
     int opt_ntt_three_from = 23;       // NTT sizes from 2^this on take three passes of <= 2^8 points (ntt_run3); 0 = never

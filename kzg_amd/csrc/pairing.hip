@@ -342,6 +342,9 @@ int g2_make_lines(kzg_ctx *ctx, hipStream_t st, kzg_srs_g2 *s) {
     if (hipMalloc((void **)&s->lines, 2 * 2 * MILLER_LINES * sizeof(Fq2)) != hipSuccess) return fail(ctx, KZG_ERR_ALLOC, "hipMalloc(G2 lines)");
     if (hipMemsetAsync(s->lines, 0, 2 * 2 * MILLER_LINES * sizeof(Fq2), st) != hipSuccess) return fail(ctx, KZG_ERR_HIP, "memset");
     if (cnt) KZG_LAUNCH(ctx, st, "k_g2_lines", k_g2_lines, 1, 64, 0, s->pts, cnt, s->lines);
+    // the host copies (pairing_shared.h); every caller synchronises the stream before it publishes `s`
+    if (cnt && hipMemcpyAsync(s->h_pts, s->pts, cnt * sizeof(G2Affine), hipMemcpyDeviceToHost, st) != hipSuccess) return fail(ctx, KZG_ERR_HIP, "memcpy");
+    if (hipMemcpyAsync(s->h_lines, s->lines, sizeof(s->h_lines), hipMemcpyDeviceToHost, st) != hipSuccess) return fail(ctx, KZG_ERR_HIP, "memcpy");
     return KZG_OK;
 }
 

@@ -10,6 +10,10 @@ struct kzg_srs_g2 {
     kzg::Fq2 *lines = nullptr;     // Miller-loop lines of pts[0] and pts[1] (2 x 2*MILLER_LINES Fq2): the verifier's
                                    // second pairing argument is always one of these two, so a check does no G2 arithmetic
     int device = 0;
+    // host copies of pts[0], pts[1] and lines, made when the points are created (they never change afterwards): kzg_verify_eval_batch
+    // finishes its one pairing check on the calling thread (option host_pairing)
+    kzg::G2Affine h_pts[2] = {};
+    kzg::Fq2 h_lines[2 * 2 * kzg::MILLER_LINES] = {};
 };
 
 namespace kzg {

@@ -18,17 +18,9 @@
 #include <chrono>
 #include <vector>
 
-#include "vcb_finish.h"
-#include "verify_cosets_shared.h"
+#include "vcb_shared.h"
 
 namespace kzg {
-
-constexpr uint32_t VCB_S = 2048;                     // points per slice: one workgroup sorts them by digit in LDS (16-bit indices)
-constexpr uint32_t VCB_G = VC_CHUNK_CELLS / VCB_S;   // slice slots of a chunk
-constexpr size_t VCB_SET = (size_t)VC_W * VC_D;      // buckets of one slot: 32 windows x 128
-constexpr uint32_t VCB_FOLD_CELLS = 64;              // cells per k_vcb_fold workgroup
-static_assert(VC_W == VCB_W, "vcb_finish.h and verify_cosets_shared.h disagree on the windows");
-static_assert(VCB_S <= 32768, "the sorted entries keep the sign in bit 15");
 
 // any scalar of sfmt -> canonical and reduced
 __global__ __launch_bounds__(256) void k_vcb_canon(const Fr *in, size_t n, int is_mont, Fr *out) {
@@ -177,27 +169,96 @@ __global__ __launch_bounds__(64) void k_vcb_finish(const VcbSums *sums, const G2
 }
 
 namespace {
-inline unsigned vcb_grid(size_t n, unsigned b = 256) { return (unsigned)((n + b - 1) / b); }
-
-// buckets of `sets` scalar sets += the digits' multiples of n points (n <= VCB_G x VCB_S)
 template <class PT>
-int vb_accumulate(kzg_ctx *ctx, hipStream_t st, const PT *d_pts, const Fr *sc0, const Fr *sc1, size_t n, G1Xyzz *bk0, G1Xyzz *bk1, int sets) {
+int vb_accumulate_any(kzg_ctx *ctx, hipStream_t st, const PT *d_pts, const Fr *sc0, const Fr *sc1, size_t n, G1Xyzz *bk0, G1Xyzz *bk1, int sets) {
     if (!n) return KZG_OK;
     KZG_LAUNCH(ctx, st, "k_vcb_bucket", k_vcb_bucket<PT>, dim3(vcb_grid(n, VCB_S), VC_W, sets), 128, 0, d_pts, sc0, sc1, n, bk0, bk1);
     return KZG_OK;
 }
+}  // namespace
 
-struct BatchParts {  // the extra outputs of kzg_test_verify_cosets_batch_parts (host)
-    void *a = nullptr, *cw = nullptr, *points = nullptr;
-};
+// ---- the stages behind vcb_shared.h --------------------------------------------------------------------------------------------
+int vb_accumulate(kzg_ctx *ctx, hipStream_t st, const G1Xyzz *d_pts, const Fr *sc0, const Fr *sc1, size_t n, G1Xyzz *bk0, G1Xyzz *bk1, int sets) {
+    return vb_accumulate_any(ctx, st, d_pts, sc0, sc1, n, bk0, bk1, sets);
+}
+int vb_accumulate(kzg_ctx *ctx, hipStream_t st, const G1Affine *d_pts, const Fr *sc0, const Fr *sc1, size_t n, G1Xyzz *bk0, G1Xyzz *bk1, int sets) {
+    return vb_accumulate_any(ctx, st, d_pts, sc0, sc1, n, bk0, bk1, sets);
+}
 
-int load_challenge(kzg_ctx *ctx, const void *r, int sfmt, Fr *mont) {
+int vb_reduce(kzg_ctx *ctx, hipStream_t st, const G1Xyzz *d_bk, uint32_t slots, VcbSums *d_sums) {
+    KZG_LAUNCH(ctx, st, "k_vcb_reduce", k_vcb_reduce, dim3(VC_W, 3), 128, 0, d_bk, slots, &d_sums->win[0][0]);
+    return KZG_OK;
+}
+
+int vcb_canon(kzg_ctx *ctx, hipStream_t st, const Fr *d_in, size_t n, int is_mont, Fr *d_out) {
+    if (!n) return KZG_OK;
+    KZG_LAUNCH(ctx, st, "k_vcb_canon", k_vcb_canon, vcb_grid(n), 256, 0, d_in, n, is_mont, d_out);
+    return KZG_OK;
+}
+
+int vcb_fold(kzg_ctx *ctx, hipStream_t st, const Fr *d_r, const Fr *d_rho, size_t B, uint32_t log_l, Fr *d_part, Fr *d_a) {
+    const uint32_t fb = vcb_grid(B, VCB_FOLD_CELLS), l = 1u << log_l;
+    KZG_LAUNCH(ctx, st, "k_vcb_fold", k_vcb_fold, fb, 256, 0, d_r, d_rho, B, log_l, d_part);
+    KZG_LAUNCH(ctx, st, "k_vcb_fold2", k_vcb_fold2, vcb_grid(l), 256, 0, (const Fr *)d_part, fb, l, d_a);
+    return KZG_OK;
+}
+
+int vcb_cweights(kzg_ctx *ctx, hipStream_t st, const Fr *d_rho, const uint32_t *d_which, const uint32_t *d_start, const uint32_t *d_order,
+                 size_t lists, Fr *d_c) {
+    KZG_LAUNCH(ctx, st, "k_vcb_cweights", k_vcb_cweights, (unsigned)lists, 64, 0, d_rho, d_which, d_start, d_order, d_c);
+    return KZG_OK;
+}
+
+int load_challenge(kzg_ctx *ctx, const char *who, const void *r, int sfmt, Fr *mont) {
     Fr x;
     memcpy(x.v, r, 32);
-    if (!is_canonical(x) || x.is_zero()) return fail(ctx, KZG_ERR_SHAPE, "kzg_verify_cosets_batch: the challenge r must be in [1, modulus)");
+    if (!is_canonical(x) || x.is_zero()) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": the challenge r must be in [1, modulus)");
     *mont = sfmt == KZG_FR_MONT_LE_32 ? x : to_mont(x);
     return KZG_OK;
 }
+
+int vcb_conclude(kzg_ctx *ctx, int lane, const VcbSums *d_sums, const G2Affine *d_hq, const Fq2 *d_lines, const G2Affine *h_hq,
+                 const Fq2 *h_lines, const int *d_bad, uint8_t *d_ok, G1Affine *d_parts, void *points, int *ok) {
+    hipStream_t st = ctx->lanes[lane].stream;
+    const bool on_host = ctx->opt_host_pairing != 0;
+    KZG_TRY(lane_pinned(ctx, lane, 1024 + sizeof(VcbSums)));
+    char *pin = ctx->lanes[lane].pinned;
+    if (!on_host) {
+        KZG_LAUNCH(ctx, st, "k_vcb_finish", k_vcb_finish, 1, 64, 0, d_sums, d_hq, d_lines, d_ok, points ? d_parts : (G1Affine *)nullptr);
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin + 64, d_ok, 1, hipMemcpyDeviceToHost, st));
+        if (points) KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin + 128, d_parts, 4 * sizeof(G1Affine), hipMemcpyDeviceToHost, st));
+    } else {
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin + 1024, d_sums, sizeof(VcbSums), hipMemcpyDeviceToHost, st));
+    }
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    KZG_HIP_CHECK(ctx, hipGetLastError());
+    if (ctx->prof) prof_collect(ctx);
+    // the decode flag before the verdict, as fetch_ok
+    if (*(int *)pin) return fail(ctx, KZG_ERR_BAD_POINT, "an input point failed to decode, is not on the curve or not in the r-torsion subgroup");
+    int verdict;
+    if (on_host) {
+        const auto t0 = std::chrono::steady_clock::now();
+        verdict = vcb_finish(*(const VcbSums *)(pin + 1024), h_hq, h_lines, points ? (G1Affine *)(pin + 128) : nullptr) ? 1 : 0;
+        if (ctx->prof) {  // the calling thread's share of the call, beside the kernels of kzg_prof_get
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            std::lock_guard<std::mutex> lk(ctx->prof_mu);
+            ProfEntry &e = ctx->prof_map["vcb_host_finish"];
+            e.launches++;
+            e.total_ms += ms;
+        }
+    } else {
+        verdict = pin[64] ? 1 : 0;
+    }
+    if (points) memcpy(points, pin + 128, 4 * sizeof(G1Affine));
+    *ok = verdict;
+    return KZG_OK;
+}
+
+namespace {
+struct BatchParts {  // the extra outputs of kzg_test_verify_cosets_batch_parts (host)
+    void *a = nullptr, *cw = nullptr, *points = nullptr;
+};
 
 int vcb_run(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitments, size_t n_commitments, const uint32_t *commitment_idx,
             const size_t *coset_ids, const void *cells, const void *proofs, size_t count, const void *r, int sfmt, int pfmt, int flags, int *ok,
@@ -216,7 +277,7 @@ int vcb_run(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitmen
     }
     if (!commitments || !commitment_idx || !coset_ids || !cells || !proofs || !r || !ok) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL argument");
     Fr rm;
-    KZG_TRY(load_challenge(ctx, r, sfmt, &rm));
+    KZG_TRY(load_challenge(ctx, who, r, sfmt, &rm));
     const uint32_t log_l = plan->log_l;
     const size_t l = (size_t)1 << log_l, K = (size_t)1 << (plan->log_n - log_l);
     if (count > (SIZE_MAX >> 6) / l || n_commitments > (SIZE_MAX >> 9)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": count too large");
@@ -304,11 +365,8 @@ int vcb_run(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitmen
         KZG_TRY(vc_interp(ctx, st, plan, src, d_ids, B, d_r));
         KZG_LAUNCH(ctx, st, "k_vcb_scalars", k_vcb_scalars, vcb_grid(B), 256, 0, (const Fr *)d_rho, (const uint32_t *)d_ids, B, log_l,
                    (const Fr *)plan->pos_lo, (const Fr *)plan->pos_hi, d_s1, d_s2);
-        const uint32_t fb = vcb_grid(B, VCB_FOLD_CELLS);
-        KZG_LAUNCH(ctx, st, "k_vcb_fold", k_vcb_fold, fb, 256, 0, (const Fr *)d_r, (const Fr *)d_rho, B, log_l, d_part);
-        KZG_LAUNCH(ctx, st, "k_vcb_fold2", k_vcb_fold2, vcb_grid(l), 256, 0, (const Fr *)d_part, fb, (uint32_t)l, d_a);
-        KZG_LAUNCH(ctx, st, "k_vcb_cweights", k_vcb_cweights, (unsigned)lists, 64, 0, (const Fr *)d_rho, (const uint32_t *)d_which,
-                   (const uint32_t *)d_start, (const uint32_t *)d_order, d_c);
+        KZG_TRY(vcb_fold(ctx, st, d_r, d_rho, B, log_l, d_part, d_a));
+        KZG_TRY(vcb_cweights(ctx, st, d_rho, d_which, d_start, d_order, lists, d_c));
         KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_s1, d_s2, B, bk1, bk2, 2));
         slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
         // the host lists and the chunk's device buffers are free again
@@ -319,52 +377,18 @@ int vcb_run(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitmen
         const size_t B = std::min(BP, n_commitments - m0);
         KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)commitments + m0 * psz, B * psz, hipMemcpyHostToDevice, st));
         KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
-        KZG_LAUNCH(ctx, st, "k_vcb_canon", k_vcb_canon, vcb_grid(B), 256, 0, (const Fr *)(d_c + m0), B, 1, d_c + m0);
+        KZG_TRY(vcb_canon(ctx, st, d_c + m0, B, 1, d_c + m0));
         KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_c + m0, d_c + m0, B, bk3, bk3, 1));
         slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
     }
-    KZG_LAUNCH(ctx, st, "k_vcb_reduce", k_vcb_reduce, dim3(VC_W, 3), 128, 0, (const G1Xyzz *)bk, (uint32_t)slots, &sums->win[0][0]);
+    KZG_TRY(vb_reduce(ctx, st, bk, (uint32_t)slots, sums));
     KZG_TRY(vc_sum(ctx, st, plan, d_a, 1, sfmt, &sums->ragg));
-
-    const bool on_host = ctx->opt_host_pairing != 0;
-    KZG_TRY(lane_pinned(ctx, lane, 1024 + sizeof(VcbSums)));
-    char *pin = ctx->lanes[lane].pinned;
-    if (!on_host) {
-        KZG_LAUNCH(ctx, st, "k_vcb_finish", k_vcb_finish, 1, 64, 0, (const VcbSums *)sums, (const G2Affine *)plan->hq, (const Fq2 *)plan->lines, d_ok,
-                   parts ? d_parts : (G1Affine *)nullptr);
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin + 64, d_ok, 1, hipMemcpyDeviceToHost, st));
-        if (parts) KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin + 128, d_parts, 4 * sizeof(G1Affine), hipMemcpyDeviceToHost, st));
-    } else {
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin + 1024, sums, sizeof(VcbSums), hipMemcpyDeviceToHost, st));
-    }
-    KZG_HIP_CHECK(ctx, hipMemcpyAsync(pin, bad, sizeof(int), hipMemcpyDeviceToHost, st));
     if (parts) {
-        if (sfmt == KZG_FR_MONT_LE_32) KZG_LAUNCH(ctx, st, "k_vcb_canon", k_vcb_canon, vcb_grid(l), 256, 0, (const Fr *)d_a, l, 1, d_a);
+        if (sfmt == KZG_FR_MONT_LE_32) KZG_TRY(vcb_canon(ctx, st, d_a, l, 1, d_a));
         KZG_HIP_CHECK(ctx, hipMemcpyAsync(parts->a, d_a, l * 32, hipMemcpyDeviceToHost, st));
         if (n_commitments) KZG_HIP_CHECK(ctx, hipMemcpyAsync(parts->cw, d_c, n_commitments * 32, hipMemcpyDeviceToHost, st));
     }
-    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    KZG_HIP_CHECK(ctx, hipGetLastError());
-    if (ctx->prof) prof_collect(ctx);
-    // the decode flag before the verdict, as fetch_ok
-    if (*(int *)pin) return fail(ctx, KZG_ERR_BAD_POINT, "an input point failed to decode, is not on the curve or not in the r-torsion subgroup");
-    int verdict;
-    if (on_host) {
-        const auto t0 = std::chrono::steady_clock::now();
-        verdict = vcb_finish(*(const VcbSums *)(pin + 1024), plan->h_hq, plan->h_lines, parts ? (G1Affine *)(pin + 128) : nullptr) ? 1 : 0;
-        if (ctx->prof) {  // the calling thread's share of the call, beside the kernels of kzg_prof_get
-            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            std::lock_guard<std::mutex> lk(ctx->prof_mu);
-            ProfEntry &e = ctx->prof_map["vcb_host_finish"];
-            e.launches++;
-            e.total_ms += ms;
-        }
-    } else {
-        verdict = pin[64] ? 1 : 0;
-    }
-    if (parts) memcpy(parts->points, pin + 128, 4 * sizeof(G1Affine));
-    *ok = verdict;
-    return KZG_OK;
+    return vcb_conclude(ctx, lane, sums, plan->hq, plan->lines, plan->h_hq, plan->h_lines, bad, d_ok, d_parts, parts ? parts->points : nullptr, ok);
 }
 }  // namespace
 
@@ -414,12 +438,12 @@ extern "C" int kzg_test_vb_msm(kzg_ctx *ctx, const kzg_srs *srs, size_t offset, 
     for (size_t i0 = 0; i0 < n; i0 += CH) {
         const size_t B = std::min(CH, n - i0);
         KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_in, (const uint8_t *)scalars + i0 * 32, B * 32, hipMemcpyHostToDevice, st));
-        KZG_LAUNCH(ctx, st, "k_vcb_canon", k_vcb_canon, vcb_grid(B), 256, 0, (const Fr *)d_in, B, sfmt == KZG_FR_MONT_LE_32 ? 1 : 0, d_sc);
+        KZG_TRY(vcb_canon(ctx, st, d_in, B, sfmt == KZG_FR_MONT_LE_32 ? 1 : 0, d_sc));
         KZG_TRY(vb_accumulate(ctx, st, (const G1Affine *)srs->table + offset + i0, d_sc, d_sc, B, bk, bk, 1));
         slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
         KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
     }
-    KZG_LAUNCH(ctx, st, "k_vcb_reduce", k_vcb_reduce, dim3(VC_W, 3), 128, 0, (const G1Xyzz *)bk, (uint32_t)slots, &sums->win[0][0]);
+    KZG_TRY(vb_reduce(ctx, st, bk, (uint32_t)slots, sums));
     VcbSums h;
     KZG_HIP_CHECK(ctx, hipMemcpyAsync(&h, sums, sizeof(VcbSums), hipMemcpyDeviceToHost, st));
     KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
