@@ -45,6 +45,20 @@
  *   KZG_G2_JACOBIAN_MONT_288 X,Y,Z in Fq2; identity has Z = 0 (= blst_p2 = G2Projective)
  *   KZG_G2_ZCASH_UNCOMPRESSED_192 / KZG_G2_ZCASH_COMPRESSED_96  x.c1 || x.c0 [|| y.c1 || y.c0] big-endian
  *                            with the same flag bits (= G2Affine::to_uncompressed / to_compressed)
+ *
+ * Decoding (what "validated" above means format by format; ONE byte string per group element, so a caller may hash the bytes it
+ * hands in -- the challenge r of kzg_verify_cosets_batch / kzg_verify_eval_batch).  Anything else is KZG_ERR_BAD_POINT:
+ *   ZCASH compressed     bit 7 set.  Bit 6 set: bit 5 clear and EVERY other bit of the encoding zero -> the identity.  Otherwise x
+ *                        (G2: c1 || c0) is the remaining 381 bits, every component < q; x^3 + b must be a square; y is the
+ *                        lexicographically larger root exactly when bit 5 is set (G1: y > (q-1)/2; G2: (c1, c0) against the
+ *                        negation's, c0 deciding when c1 = 0).
+ *   ZCASH uncompressed   bit 7 clear.  Bit 6 set: every other bit, bit 5 included, zero -> the identity.  Otherwise bit 5 clear,
+ *                        every coordinate < q, (x, y) on the curve.  All-zero bytes are (0, 0), which is not.
+ *   affine Montgomery    every limb vector < q; all-zero is the identity; anything else, (0, y) and (x, 0) included, must satisfy
+ *                        the curve equation.
+ *   Jacobian Montgomery  X, Y, Z < q (also when Z = 0); Z = 0 is the identity; otherwise Y^2 = X^3 + b Z^6.
+ *   then [r]P == O unless option "trusted_points" = 1.  The encoders write exactly these forms, so re-encoding a decoded wire
+ *   point gives back its bytes (oracle/decode.py is the reference decoder; tests/test_gpu_decode.py).
  */
 #ifndef KZG_MI355X_H
 #define KZG_MI355X_H

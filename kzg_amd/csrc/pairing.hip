@@ -7,21 +7,13 @@
 // ONE check and a batch of openings is one launch (kzg_verify_eval takes `count` tuples); tower.h documents the
 // arithmetic.  Nothing here is on the prover's throughput path.
 #include "pairing_shared.h"
+#include "wire.h"
 
 namespace kzg {
 
 // ------------------------------------------------------------------------------------------------
 // encodings (zcash: x.c1 || x.c0 [|| y.c1 || y.c0], big-endian, flag bits in the first byte)
 // ------------------------------------------------------------------------------------------------
-static __device__ Fq rd_be48(const uint8_t *src, bool mask_flags) {
-    Fq r = Fq::zero();
-    for (int i = 0; i < 48; i++) {
-        uint32_t byte = src[47 - i];
-        if (mask_flags && i == 47) byte &= 0x1f;
-        r.v[i >> 2] |= byte << (8 * (i & 3));
-    }
-    return r;
-}
 static __device__ void wr_be48(uint8_t *dst, const Fq &canon) {
     for (int i = 0; i < 48; i++) dst[47 - i] = (uint8_t)(canon.v[i >> 2] >> (8 * (i & 3)));
 }
@@ -98,38 +90,37 @@ __global__ __launch_bounds__(64) void k_g2_decode(const uint8_t *src, size_t n, 
         G2Jacobian j = *reinterpret_cast<const G2Jacobian *>(src + i * 288);
         if (level >= POINTS_ON_CURVE) ok = f2_canonical(j.x) && f2_canonical(j.y) && f2_canonical(j.z);
         g2_to_affine(a, j);
-        if (level >= POINTS_ON_CURVE) ok = ok && g2_on_curve(a);
-    } else if (fmt == KZG_G2_ZCASH_UNCOMPRESSED_192) {
-        const uint8_t *p = src + i * 192;
-        if (p[0] & 0x80) ok = false;
-        if (p[0] & 0x40) {
-            a.x = Fq2::zero();
-            a.y = Fq2::zero();
-        } else {
-            Fq x1 = rd_be48(p, true), x0 = rd_be48(p + 48, false), y1 = rd_be48(p + 96, false), y0 = rd_be48(p + 144, false);
-            ok = ok && is_canonical(x0) && is_canonical(x1) && is_canonical(y0) && is_canonical(y1);
-            a.x = Fq2{to_mont(x0), to_mont(x1)};
-            a.y = Fq2{to_mont(y0), to_mont(y1)};
-            ok = ok && g2_on_curve(a);
-        }
+        // Z != 0 with X = Y = 0 becomes the affine (0, 0), which is NOT the identity here: 0 != 0 + b Z^6
+        if (level >= POINTS_ON_CURVE) ok = ok && (j.is_inf() || (!a.is_inf() && g2_on_curve(a)));
     } else {
-        const uint8_t *p = src + i * 96;
-        if (!(p[0] & 0x80)) ok = false;
-        if (p[0] & 0x40) {
-            a.x = Fq2::zero();
-            a.y = Fq2::zero();
-        } else {
-            Fq x1 = rd_be48(p, true), x0 = rd_be48(p + 48, false);
-            ok = ok && is_canonical(x0) && is_canonical(x1);
+        // the wire formats (wire.h for the flag rules): a malformed first byte is bad whatever the coordinates are
+        const bool compressed = fmt != KZG_G2_ZCASH_UNCOMPRESSED_192;
+        const int len = compressed ? 96 : 192;
+        const uint8_t *p = src + i * (size_t)len;
+        bool infinity, sign;
+        a.x = Fq2::zero();
+        a.y = Fq2::zero();
+        ok = wire_header(p, len, compressed, &infinity, &sign);
+        if (ok && !infinity) {
+            Fq x1 = wire_read_be48(p, true), x0 = wire_read_be48(p + 48, false);
+            ok = is_canonical(x0) && is_canonical(x1);
             a.x = Fq2{to_mont(x0), to_mont(x1)};
-            Fq2 rhs, b;
-            f2_sqr(rhs, a.x);
-            f2_mul(rhs, rhs, a.x);
-            b.c0 = from_u64<FqParams>(4);
-            b.c1 = b.c0;
-            f2_add(rhs, rhs, b);
-            ok = f2_sqrt(a.y, rhs) && ok;
-            if (f2_lex_largest(a.y) != ((p[0] & 0x20) != 0)) f2_neg(a.y, a.y);
+            if (!compressed) {
+                Fq y1 = wire_read_be48(p + 96, false), y0 = wire_read_be48(p + 144, false);
+                ok = ok && is_canonical(y0) && is_canonical(y1);
+                a.y = Fq2{to_mont(y0), to_mont(y1)};
+                // (0, 0) without the infinity flag is a pair of coordinates like any other, and 0 != 0 + 4(1+u)
+                ok = ok && !a.is_inf() && g2_on_curve(a);
+            } else {
+                Fq2 rhs, b;
+                f2_sqr(rhs, a.x);
+                f2_mul(rhs, rhs, a.x);
+                b.c0 = from_u64<FqParams>(4);
+                b.c1 = b.c0;
+                f2_add(rhs, rhs, b);
+                ok = f2_sqrt(a.y, rhs) && ok;
+                if (f2_lex_largest(a.y) != sign) f2_neg(a.y, a.y);
+            }
         }
     }
     if (ok && level >= POINTS_SUBGROUP) ok = g2_in_subgroup(a);

@@ -4,6 +4,7 @@
 // generators: setup() (src/lib.rs:38-47, G1 half) and the Lagrange basis for a known secret.
 #include "common.h"
 #include "curve30.h"
+#include "wire.h"
 
 namespace kzg {
 
@@ -181,16 +182,6 @@ int srs_finish_from_xyzz(kzg_ctx *ctx, kzg_srs *srs, G1Xyzz *d_row0_xyzz) {
 // ---------------------------------------------------------------------------------------------
 // decoding of the four input point formats into row 0
 // ---------------------------------------------------------------------------------------------
-__device__ Fq read_be48(const uint8_t *src, bool mask_flags) {
-    Fq r = Fq::zero();
-    for (int i = 0; i < 48; i++) {
-        uint32_t byte = src[47 - i];
-        if (mask_flags && i == 47) byte &= 0x1f;
-        r.v[i >> 2] |= byte << (8 * (i & 3));
-    }
-    return r;
-}
-
 // y = sqrt(a) = a^((q+1)/4) (q = 3 mod 4); caller checks y^2 == a
 __device__ Fq fq_sqrt_candidate(const Fq &a) {
     // (q + 1) / 4
@@ -265,34 +256,31 @@ __global__ __launch_bounds__(256) void k_decode_points(const uint8_t *src, size_
         out[i] = p;
         return;
     }
-    G1Affine a;
-    bool ok = true;
+    // the wire formats (wire.h for the flag rules): a malformed first byte is bad whatever the coordinates are
+    G1Affine a = G1Affine::inf();
+    bool ok, infinity, sign;
     if (fmt == KZG_G1_ZCASH_UNCOMPRESSED_96) {
         const uint8_t *p = src + i * 96;
-        if (p[0] & 0x80) ok = false;
-        if (p[0] & 0x40) {
-            a = G1Affine::inf();
-        } else {
-            Fq x = read_be48(p, true), y = read_be48(p + 48, false);
-            ok = ok && is_canonical(x) && is_canonical(y);
+        ok = wire_header(p, 96, false, &infinity, &sign);
+        if (ok && !infinity) {
+            Fq x = wire_read_be48(p, true), y = wire_read_be48(p + 48, false);
+            ok = is_canonical(x) && is_canonical(y);
             a.x = to_mont(x);
             a.y = to_mont(y);
-            ok = ok && g1_on_curve(a);
+            // (0, 0) without the infinity flag is a pair of coordinates like any other, and 0 != 0 + 4
+            ok = ok && !a.is_inf() && g1_on_curve(a);
         }
     } else {
         const uint8_t *p = src + i * 48;
-        if (!(p[0] & 0x80)) ok = false;
-        if (p[0] & 0x40) {
-            a = G1Affine::inf();
-        } else {
-            Fq x = read_be48(p, true);
-            ok = ok && is_canonical(x);
+        ok = wire_header(p, 48, true, &infinity, &sign);
+        if (ok && !infinity) {
+            Fq x = wire_read_be48(p, true);
+            ok = is_canonical(x);
             a.x = to_mont(x);
             Fq rhs = add(mul(sqr(a.x), a.x), from_u64<FqParams>(4));
             Fq y = fq_sqrt_candidate(rhs);
             ok = ok && (sqr(y) == rhs);
-            bool want_big = (p[0] & 0x20) != 0;
-            if (fq_gt_half(from_mont(y)) != want_big) y = neg(y);
+            if (fq_gt_half(from_mont(y)) != sign) y = neg(y);
             a.y = y;
         }
     }
