@@ -410,6 +410,38 @@ int kzg_quotient_eval_at(kzg_ctx *ctx, const void *evals, size_t d, const void *
  * distinct z), and the lanes' MSM workspaces. */
 int kzg_open_eval(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals, size_t d, size_t batch, const void *zs, int sfmt,
                   int flags, void *ys_out, void *out_w, int ofmt);
+/* ---- many polynomials opened at ONE point with a single folded witness (not a reference method) -------------------------------
+ * The shape of PLONK-style provers and aggregate blob proofs: t polynomials p_0 .. p_{t-1} opened at a common z are answered by their
+ * t values and ONE group element.  With a challenge gamma,
+ *   F = sum_i gamma^i p_i,   y_F = sum_i gamma^i y_i,   witness = [(F - y_F)/(X - z)]_1:
+ * one MSM per group of t polynomials instead of t, after one streaming pass over the inputs (the fold).  `groups` such groups per call,
+ * group g with its own point zs[g] and challenge gammas[g] (host scalars in sfmt; a z >= r, a gamma == 0 or >= r: KZG_ERR_SHAPE).
+ * kzg_verify_fold (below) checks the result; what the caller owes for gamma is said there.
+ * The fold alone: out[g d + j] = sum_{i < t} gammas[g]^i vecs[(g t + i) d + j] for `groups` groups of t vectors of d >= 1 scalars (any d,
+ * not only a power of two).  vecs and out are host memory, or device memory with KZG_IN_DEVICE / KZG_OUT_DEVICE; out has the form of
+ * the inputs (canonical in, canonical out; Montgomery in, Montgomery out).  Canonical inputs may hold any 256-bit value: they count as
+ * their residue.  Host inputs are staged in pieces of at most 64 MiB with the running sum on the device, host outputs come back per
+ * chunk of groups: the workspace does not grow with t x groups.  Leases one lane.  KZG_ERR_SHAPE, before memory is touched: d == 0,
+ * t == 0, a NULL pointer with groups > 0, an unknown format, a gamma == 0 or >= r, groups x t x d x 32 beyond size_t.  groups == 0:
+ * KZG_OK. */
+int kzg_fr_fold(kzg_ctx *ctx, const void *vecs, size_t d, size_t t, size_t groups, const void *gammas, int sfmt, int flags, void *out);
+/* Evaluation form: evals holds groups x t vectors of d values (stride d; KZG_IN_DEVICE applies), group g opened at zs[g], any point
+ * of Fr.  ys_out[g t + i] = p_{g,i}(zs[g]) (host, optional; the values of kzg_eval_form_eval) and out_w[g] = the folded witness in ofmt
+ * (host, or device with KZG_OUT_DEVICE; optional; not both NULL).  At z = w^m the witness bytes are kzg_witness_eval's of the folded
+ * vector at m; everywhere they are kzg_open_eval's of the folded vector.  Takes the context exclusively like kzg_open_eval, whose
+ * pipeline it feeds: per chunk of one group per lane the t vectors of a group are evaluated (only when ys_out is given) and folded
+ * in pieces of at most 16 vectors, the folded vectors go through the evaluation stage once more for their quotients, and the MSMs
+ * of the chunk run beside the Fr stage of the next.  Workspace: one piece of staged input (host input only), per lane one folded vector
+ * and two quotients of d scalars, the denominators and inverses of one chunk, the lanes' MSM workspaces, 32 bytes per value.
+ * KZG_ERR_SHAPE as for kzg_open_eval, and t == 0, a gamma == 0 or >= r; groups == 0: KZG_OK. */
+int kzg_open_fold_eval(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals, size_t d, size_t t, size_t groups, const void *zs,
+                       const void *gammas, int sfmt, int flags, void *ys_out, void *out_w, int ofmt);
+/* Coefficient form: coeffs holds groups x t polynomials of n >= 1 coefficients each (the caller pads to the common length; stride n;
+ * KZG_IN_DEVICE applies), n - 1 <= kzg_srs_len(srs).  ys_out[g t + i] = p_{g,i}(zs[g]) (kzg_poly_eval's values) and out_w[g] =
+ * kzg_witness_coeff of the folded polynomial at (zs[g], F(zs[g])).  Group g runs on lane g mod lanes: values, fold, the linear quotient
+ * of the folded coefficients, one MSM.  Outputs, errors and groups == 0 as above (n == 0 and n - 1 > kzg_srs_len(srs): KZG_ERR_SHAPE). */
+int kzg_open_fold_coeff(kzg_ctx *ctx, const kzg_srs *srs, const void *coeffs, size_t n, size_t t, size_t groups, const void *zs,
+                        const void *gammas, int sfmt, int flags, void *ys_out, void *out_w, int ofmt);
 /* ---- all openings over the domain (FK20, single-point case; not a reference method) ---------------------------------
  * Every witness of a polynomial at every point w^m of its size-N domain (w = compute_omega(N).omega) in O(N log N) group
  * operations instead of N MSMs: two G1 DFTs, 2N variable-base scalar multiplications and one Fr NTT per polynomial, against a
@@ -606,6 +638,28 @@ int kzg_verify_cosets_batch(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const
 int kzg_verify_eval_batch(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *xs, const void *ys, int sfmt,
                           const void *commitments, size_t n_commitments, const uint32_t *commitment_idx, const void *witnesses, int pfmt,
                           size_t count, const void *r, int *ok);
+/* The verifier of kzg_open_fold_eval / kzg_open_fold_coeff: ONE verdict from one pairing check for `groups` folded openings.  Group g
+ * claims p_{m(g,i)}(zs[g]) = ys[g t + i] for i < t with the ONE witness witnesses[g], folded with gammas[g]; m(g,i) =
+ * commitment_idx[g t + i] names one of the n_commitments points of `commitments` (NULL: m(g,i) = g t + i, and n_commitments ==
+ * groups x t is required).  With rho_{g,i} = r^g gammas[g]^i:
+ *   c_m = sum_{m(g,i) = m} rho_{g,i},  Cagg = sum_m c_m C_m,  yagg = sum rho_{g,i} y_{g,i};
+ *   P1 = sum_g r^g pi_g,  P2 = sum_g (r^g z_g) pi_g;   *ok = [ e(P1, hs[1]) e(-(P2 + Cagg - [yagg] gs[0]), hs[0]) == 1 ].
+ * zs, gammas: `groups` host scalars each, ys: groups x t, r: one (may be NULL when groups == 1), all in sfmt.  ys are taken as
+ * kzg_verify_eval_batch takes them (a value >= the modulus counts as its residue); zs, gammas and r are range-checked.
+ * WHAT THE CALLER OWES.  gamma_g must be unpredictable to whoever chose the polynomials AND the claimed values of group g: in practice
+ * a hash of the commitments, z and the ys.  With a predictable gamma wrong values cancel inside the fold: for t = 2 the claims
+ * y_0 + D and y_1 - D / gamma have the fold y_F of the true values, so the honest folded witness passes although both values are
+ * wrong (gamma = 1: y_0 + 1 and y_1 - 1).  r must be unpredictable to whoever produced EVERYTHING, witnesses included: draw it after
+ * all inputs are received or hash all of them, as for kzg_verify_eval_batch (with r = 1, pi_a + D and pi_b - D at one z pass).
+ * Honest openings pass for every gamma and r.  *ok == 0 does not say which group or value is bad.
+ * KZG_ERR_SHAPE, before memory is touched and with *ok unwritten: t == 0, a gamma == 0 or >= modulus, r == 0 or >= modulus or NULL
+ * when groups > 1, a z >= modulus, an index >= n_commitments, NULL indices with n_commitments != groups x t, groups x t beyond
+ * size_t, and every condition of kzg_verify_eval_batch (formats, SRS, NULL pointers).  groups == 0: *ok = 1 (if ok is non-NULL),
+ * KZG_OK.  Point validation and KZG_ERR_BAD_POINT (*ok unwritten), the lane, the chunking (option "verify_eval_batch_chunk": witnesses
+ * per chunk, then values and commitments per chunk) and options "host_pairing" / "trusted_points" are kzg_verify_eval_batch's. */
+int kzg_verify_fold(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *zs, const void *ys, int sfmt,
+                    const void *commitments, size_t n_commitments, const uint32_t *commitment_idx, const void *witnesses, int pfmt,
+                    size_t t, size_t groups, const void *gammas, const void *r, int *ok);
 
 /* ---- Fr polynomial helpers on the path (device) ---------------------------------------------- */
 /* Polynomial::eval (src/polynomial.rs:156-165) at one point. */

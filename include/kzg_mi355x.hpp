@@ -185,6 +185,16 @@ inline std::vector<Scalar> eval_form_eval(const Engine &e, const std::vector<Sca
     return ys;
 }
 
+// kzg_fr_fold: out[g d + j] = sum_{i < t} gammas[g]^i vecs[(g t + i) d + j] for gammas.size() groups of t vectors of d scalars (vecs:
+// groups x t x d scalars back to back).  Not a reference method.
+inline std::vector<Scalar> fr_fold(const Engine &e, const std::vector<Scalar> &vecs, size_t d, size_t t, const std::vector<Scalar> &gammas) {
+    static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+    if (d == 0 || t == 0 || vecs.size() / d / t != gammas.size() || vecs.size() != gammas.size() * t * d) throw ReferencePanic("fr_fold: shape");
+    std::vector<Scalar> out(gammas.size() * d);
+    e.check(kzg_fr_fold(e.ctx(), vecs.data(), d, t, gammas.size(), gammas.data(), KZG_FR_CANONICAL_LE_32, 0, out.data()));
+    return out;
+}
+
 struct KZGBatchWitness {  // src/coeff_form.rs:12-35
     Polynomial r;
     G1Affine w;
@@ -223,6 +233,19 @@ class KZGProver {  // src/coeff_form.rs:37-112
             for (size_t j = 0; j < xs.size(); j++) (*ok)[j] = status[j] == 0;
         }
         return out;
+    }
+    // kzg_open_fold_coeff: zs.size() groups of t polynomials of n coefficients each (coeffs: groups x t x n scalars back to back, padded
+    // by the caller), group g opened at zs[g]: the groups x t values and ONE witness per group, the witness of sum_i gammas[g]^i p_{g,i}.
+    // KZGVerifier::verify_fold checks it.  Not a reference method.
+    std::pair<std::vector<Scalar>, std::vector<KZGWitness>> open_fold_batch(const std::vector<Scalar> &coeffs, size_t n, size_t t,
+                                                                              const std::vector<Scalar> &zs, const std::vector<Scalar> &gammas) const {
+        static_assert(sizeof(Scalar) == 32 && sizeof(G1Affine) == 96, "packed encodings");
+        if (n == 0 || t == 0 || gammas.size() != zs.size() || coeffs.size() / n / t != zs.size() || coeffs.size() != zs.size() * t * n)
+            throw ReferencePanic("open_fold_batch: groups x t polynomials of n coefficients, one point and one challenge per group");
+        std::pair<std::vector<Scalar>, std::vector<KZGWitness>> r{std::vector<Scalar>(zs.size() * t), std::vector<KZGWitness>(zs.size())};
+        e_.check(kzg_open_fold_coeff(e_.ctx(), params_.gs, coeffs.data(), n, t, zs.size(), zs.data(), gammas.data(), KZG_FR_CANONICAL_LE_32, 0,
+                                     r.first.data(), r.second.data(), KZG_G1_AFFINE_MONT_96));
+        return r;
     }
     KZGBatchWitness create_witness_batched(const Polynomial &p, const std::vector<Scalar> &xs,
                                            const std::vector<Scalar> &ys) const {  // :83-111
@@ -282,6 +305,27 @@ class KZGVerifier {  // src/coeff_form.rs:114-183; the pairing checks run on the
         e_.check(kzg_verify_eval_batch(e_.ctx(), params_.gs, params_.hs, xs.data(), ys.data(), KZG_FR_CANONICAL_LE_32, cb.data(),
                                        commitments.size(), commitment_idx.empty() ? nullptr : commitment_idx.data(), wb.data(),
                                        KZG_G1_AFFINE_MONT_96, count, r.le.data(), &ok));
+        return ok != 0;
+    }
+    // kzg_verify_fold: true iff ALL zs.size() folded openings verify, from one pairing check.  Group g claims the t values
+    // ys[g t .. g t + t) at zs[g] for commitments[commitment_idx[g t + i]] (empty commitment_idx: commitments[g t + i]) with the ONE
+    // witness witnesses[g], folded with gammas[g]; the groups are combined with the weights r^g.  gammas[g] must be unpredictable to
+    // whoever chose the polynomials and the claimed values, r to whoever produced everything: see the header.
+    bool verify_fold(const std::vector<Scalar> &zs, const std::vector<Scalar> &ys, const std::vector<KZGCommitment> &commitments,
+                     const std::vector<uint32_t> &commitment_idx, const std::vector<KZGWitness> &witnesses, size_t t,
+                     const std::vector<Scalar> &gammas, const Scalar &r) const {
+        if (!params_.hs) throw ReferencePanic("KZGParams.hs is empty (index out of bounds)");
+        const size_t groups = zs.size();
+        if (t == 0 || ys.size() / t != groups || ys.size() != groups * t || witnesses.size() != groups || gammas.size() != groups ||
+            (!commitment_idx.empty() && commitment_idx.size() != ys.size()))
+            throw ReferencePanic("verify_fold: shape");
+        std::vector<uint8_t> cb(commitments.size() * 96), wb(groups * 96);
+        for (size_t i = 0; i < commitments.size(); i++) std::memcpy(cb.data() + 96 * i, commitments[i].bytes.data(), 96);
+        for (size_t i = 0; i < groups; i++) std::memcpy(wb.data() + 96 * i, witnesses[i].bytes.data(), 96);
+        int ok = 0;
+        e_.check(kzg_verify_fold(e_.ctx(), params_.gs, params_.hs, zs.data(), ys.data(), KZG_FR_CANONICAL_LE_32, cb.data(), commitments.size(),
+                                 commitment_idx.empty() ? nullptr : commitment_idx.data(), wb.data(), KZG_G1_AFFINE_MONT_96, t, groups,
+                                 gammas.data(), r.le.data(), &ok));
         return ok != 0;
     }
     bool verify_eval_batched(const std::vector<Scalar> &xs, const KZGCommitment &c, const KZGBatchWitness &w) const {  // :144-182
@@ -508,6 +552,19 @@ class KZGProverEvalForm {  // src/eval_form.rs:39-147
         std::pair<std::vector<Scalar>, std::vector<KZGWitness>> r{std::vector<Scalar>(zs.size()), std::vector<KZGWitness>(zs.size())};
         e_.check(kzg_open_eval(e_.ctx(), lag_, evals.data(), d_, zs.size(), zs.data(), KZG_FR_CANONICAL_LE_32, 0, r.first.data(),
                                r.second.data(), KZG_G1_AFFINE_MONT_96));
+        return r;
+    }
+    // kzg_open_fold_eval: zs.size() groups of t evaluation vectors each (evals: groups x t x degree() scalars back to back), group g
+    // opened at zs[g], any point of Fr: the groups x t values and ONE witness per group, open_at of sum_i gammas[g]^i evals_{g,i}.
+    // KZGVerifier::verify_fold checks it.  Not a reference method.
+    std::pair<std::vector<Scalar>, std::vector<KZGWitness>> open_fold_batch(const std::vector<Scalar> &evals, size_t t, const std::vector<Scalar> &zs,
+                                                                              const std::vector<Scalar> &gammas) const {
+        static_assert(sizeof(Scalar) == 32 && sizeof(G1Affine) == 96, "packed encodings");
+        if (t == 0 || gammas.size() != zs.size() || evals.size() / d_ / t != zs.size() || evals.size() != zs.size() * t * d_)
+            throw ReferencePanic("open_fold_batch: groups x t evaluation vectors of degree() scalars, one point and one challenge per group");
+        std::pair<std::vector<Scalar>, std::vector<KZGWitness>> r{std::vector<Scalar>(zs.size() * t), std::vector<KZGWitness>(zs.size())};
+        e_.check(kzg_open_fold_eval(e_.ctx(), lag_, evals.data(), d_, t, zs.size(), zs.data(), gammas.data(), KZG_FR_CANONICAL_LE_32, 0,
+                                    r.first.data(), r.second.data(), KZG_G1_AFFINE_MONT_96));
         return r;
     }
 

@@ -147,6 +147,10 @@ def load(path=None):
         "kzg_eval_form_eval": (i32, [vp, vp, sz, sz, vp, i32, i32, vp]),
         "kzg_quotient_eval_at": (i32, [vp, vp, sz, vp, i32, i32, vp, vp]),
         "kzg_open_eval": (i32, [vp, vp, vp, sz, sz, vp, i32, i32, vp, vp, i32]),
+        "kzg_fr_fold": (i32, [vp, vp, sz, sz, sz, vp, i32, i32, vp]),
+        "kzg_open_fold_eval": (i32, [vp, vp, vp, sz, sz, sz, vp, vp, i32, i32, vp, vp, i32]),
+        "kzg_open_fold_coeff": (i32, [vp, vp, vp, sz, sz, sz, vp, vp, i32, i32, vp, vp, i32]),
+        "kzg_verify_fold": (i32, [vp, vp, vp, vp, vp, i32, vp, sz, ctypes.POINTER(u32), vp, i32, sz, sz, vp, vp, ctypes.POINTER(i32)]),
         "kzg_poly_mul": (i32, [vp, vp, sz, vp, sz, i32, i32, vp]),
         "kzg_dev_alloc": (i32, [vp, sz, c_void_pp]),
         "kzg_dev_free": (i32, [vp, vp]),

@@ -296,6 +296,69 @@ class Engine:
             _raise(self, rc)
         return [self._scalar_from(out.raw[32 * b:32 * b + 32], sfmt) for b in range(len(zs))]
 
+    def fr_fold(self, vecs, d, t, gammas, out=None):
+        """kzg_fr_fold: out[g d + j] = sum_{i < t} gammas[g]^i vecs[(g t + i) d + j] for len(gammas) groups of t vectors of d scalars.
+        vecs: a flat list of ints, a canonical blob or a DeviceBuffer; gammas: ints in [1, R).  Returns the len(gammas) x d sums as
+        ints, or `out` (a DeviceBuffer of the inputs' scalar format) when one is given."""
+        groups = len(gammas)
+        ptr, have, sfmt, flags, _keep = self._scalars_arg(vecs)
+        if have < groups * t * d:  # the call would read past the buffer
+            raise ReferencePanic("%d scalars given, groups * t * d = %d" % (have, groups * t * d))
+        gb = b"".join(self._host_scalar(int(g), sfmt) if 0 < int(g) < R_MODULUS else int(g).to_bytes(32, "little") for g in gammas)
+        if out is not None:
+            if out.n < groups * d or out.sfmt != sfmt:
+                raise ReferencePanic("fr_fold: out holds %d scalars, groups * d = %d (and has the inputs' format)" % (out.n, groups * d))
+            rc = self.lib.kzg_fr_fold(self.ctx, ptr, d, t, groups, gb, sfmt, flags | L.OUT_DEVICE, out.ptr)
+            if rc:
+                _raise(self, rc)
+            return out
+        buf = ctypes.create_string_buffer(32 * max(groups * d, 1))
+        rc = self.lib.kzg_fr_fold(self.ctx, ptr, d, t, groups, gb, sfmt, flags, buf)
+        if rc:
+            _raise(self, rc)
+        return [self._scalar_from(buf.raw[32 * k:32 * k + 32], sfmt) for k in range(groups * d)]
+
+    def _fold_groups_arg(self, groups_vecs, groups, t=None, d=None, pad=True):
+        """(pointer, d, t, sfmt, flags, keep-alive) of `groups` groups of t vectors of d scalars: a list of groups, each a list of t
+        vectors (lists of ints, EvaluationDomains or Polynomials), or a flat blob / DeviceBuffer (t then given)."""
+        if not isinstance(groups_vecs, (DeviceBuffer, bytes, bytearray, memoryview)):
+            if len(groups_vecs) != groups:
+                raise ReferencePanic("one group of vectors per point")
+            rows = [[v.coeffs if isinstance(v, EvaluationDomain) else (v.slice_coeffs() if isinstance(v, Polynomial) else list(v)) for v in grp]
+                    for grp in groups_vecs]
+            t = len(rows[0]) if rows else (t or 1)
+            d = d if rows else (d or 1)
+            if rows and (t == 0 or any(len(grp) != t for grp in rows)):
+                raise ReferencePanic("every group holds the same number t >= 1 of vectors")
+            if rows and d is None:
+                d = max(len(v) for grp in rows for v in grp)
+            if any(len(v) > d or (not pad and len(v) != d) for grp in rows for v in grp):
+                raise ReferencePanic("a vector does not fit d = %d" % d)
+            groups_vecs = [x for grp in rows for v in grp for x in list(v) + [0] * (d - len(v))]
+        ptr, have, sfmt, flags, keep = self._scalars_arg(groups_vecs)
+        if t is None or d is None:
+            raise ReferencePanic("t and d are needed with a flat buffer")
+        if have < groups * t * d:  # the call would read past the buffer
+            raise ReferencePanic("%d scalars given, groups * t * d = %d" % (have, groups * t * d))
+        return ptr, d, t, sfmt, flags, keep
+
+    def _open_fold(self, fn, srs, groups_vecs, zs, gammas, ofmt, t, d, pad):
+        """the body of KZGProverEvalForm.open_fold_batch and KZGProver.open_fold_batch"""
+        groups = len(zs)
+        if len(gammas) != groups:
+            raise ReferencePanic("one challenge gamma per group")
+        ptr, d, t, sfmt, flags, _keep = self._fold_groups_arg(groups_vecs, groups, t, d, pad)
+        psz = L.POINT_BYTES[ofmt]
+        ys = ctypes.create_string_buffer(32 * max(groups * t, 1))
+        out = ctypes.create_string_buffer(psz * max(groups, 1))
+        zb = b"".join(self._host_scalar(int(z), sfmt) for z in zs)
+        gb = b"".join(self._host_scalar(int(g), sfmt) if 0 < int(g) < R_MODULUS else int(g).to_bytes(32, "little") for g in gammas)
+        rc = fn(self.ctx, srs.handle, ptr, d, t, groups, zb, gb, sfmt, flags, ys, out, ofmt)
+        if rc:
+            _raise(self, rc)
+        return ([[self._scalar_from(ys.raw[32 * (g * t + i):32 * (g * t + i) + 32], sfmt) for i in range(t)] for g in range(groups)],
+                [out.raw[g * psz:(g + 1) * psz] for g in range(groups)])
+
     def _eval_vectors_arg(self, evals, batch, d=None):
         """(pointer, d, sfmt, flags, keep-alive) of `batch` evaluation vectors, stride d"""
         if not isinstance(evals, (DeviceBuffer, bytes, bytearray, memoryview)) and len(evals) and not isinstance(evals[0], int):
@@ -1093,6 +1156,20 @@ class KZGProver:
             _raise(e, rc)
         return out.raw
 
+    def open_fold(self, polynomials, z, gamma, ofmt=L.G1_AFFINE_MONT):
+        """(ys, witness): the values p_i(z) of the polynomials and ONE witness for all of them, the witness of F = sum_i gamma^i p_i
+        at (z, F(z)) (kzg_open_fold_coeff; not a reference method).  KZGVerifier.verify_fold checks it; gamma is the protocol's
+        challenge, a hash of the commitments, z and the values in practice."""
+        ys, ws = self.open_fold_batch([polynomials], [z], [gamma], ofmt)
+        return ys[0], ws[0]
+
+    def open_fold_batch(self, groups, zs, gammas, ofmt=L.G1_AFFINE_MONT, t=None, n=None):
+        """open_fold for len(zs) groups of t polynomials each in one call -> (list of lists of y, list of witnesses).  groups: a list
+        of lists of Polynomials / coefficient lists (padded here to the longest), or a canonical blob / DeviceBuffer of len(zs) x t x n
+        coefficients (t and n then given)."""
+        e = self.engine
+        return e._open_fold(e.lib.kzg_open_fold_coeff, self.parameters.gs, groups, zs, gammas, ofmt, t, n, True)
+
     def create_witness_many(self, polynomial, points, ofmt=L.G1_AFFINE_MONT, coeffs_device=None):
         """Throughput form of create_witness (not a reference method): one witness per (x, y) in `points`, all for the same
         polynomial, pipelined on the engine's lanes.  Returns (witnesses, ok) with ok[j] False where the reference would
@@ -1207,6 +1284,37 @@ class KZGVerifier:
             _raise(e, rc)
         return bool(ok.value)
 
+    def verify_fold(self, z, ys, commitments, witness, gamma, pfmt=L.G1_AFFINE_MONT):
+        """kzg_verify_fold for one group (not a reference method): True iff `witness` opens sum_i gamma^i commitments[i] at z to
+        sum_i gamma^i ys[i] -- what open_fold produced.  Sound for the single values only if gamma was unpredictable to whoever
+        chose the polynomials and the claimed values (a hash of the commitments, z and ys)."""
+        return self.verify_fold_batch([z], [ys], commitments, [witness], [gamma], 1, pfmt=pfmt)
+
+    def verify_fold_batch(self, zs, ys, commitments, witnesses, gammas, r=None, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
+        """kzg_verify_fold: ONE verdict from one pairing check for len(zs) folded openings.  ys[g]: the t claimed values of group g,
+        witnesses[g] its folded witness, gammas[g] its challenge; value (g, i) belongs to commitments[commitment_idx[g * t + i]]
+        (None: commitments[g * t + i]).  r: the challenge that combines the groups, an int in [1, R); r=None draws it here with
+        `secrets`, sound because it is drawn after everything was handed over."""
+        e = self.engine
+        groups = len(zs)
+        t = len(ys[0]) if groups else 1
+        if len(ys) != groups or len(witnesses) != groups or len(gammas) != groups or any(len(y) != t for y in ys):
+            raise ReferencePanic("verify_fold: one point, witness, challenge and list of t values per group")
+        if commitment_idx is not None and len(commitment_idx) != groups * t:
+            raise ReferencePanic("verify_fold: one commitment index per value")
+        if r is None:
+            r = secrets.randbelow(R_MODULUS - 1) + 1
+        idx = None
+        if commitment_idx is not None:
+            idx = (ctypes.c_uint32 * max(groups * t, 1))(*[int(i) % (1 << 32) for i in commitment_idx])
+        ok = ctypes.c_int(-1)
+        rc = e.lib.kzg_verify_fold(e.ctx, self.parameters.gs.handle, self._hs().handle, pack_scalars(zs), pack_scalars([y for g in ys for y in g]),
+                                   L.FR_CANONICAL, b"".join(commitments), len(commitments), idx, b"".join(witnesses), pfmt, t, groups,
+                                   b"".join(int(g).to_bytes(32, "little") for g in gammas), int(r).to_bytes(32, "little"), ctypes.byref(ok))
+        if rc:
+            _raise(e, rc)
+        return bool(ok.value)
+
     def verify_eval_with_fallback(self, points, commitments, witnesses, r=None, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
         """One verdict per opening, as verify_eval_many(): the batch check first, and the per-opening checks only when it says no."""
         if self.verify_eval_batch(points, commitments, witnesses, r, commitment_idx, pfmt):
@@ -1303,6 +1411,18 @@ class KZGProverEvalForm:
         return ([e._scalar_from(ys.raw[32 * b:32 * b + 32], sfmt) for b in range(batch)],
                 [out.raw[b * psz:(b + 1) * psz] for b in range(batch)])
 
+    def open_fold(self, evals_list, z, gamma, ofmt=L.G1_AFFINE_MONT):
+        """(ys, witness): the values p_i(z) of the polynomials with the evaluations evals_list[i], at ANY point z of Fr, and ONE
+        witness for all of them: open_at of the folded vector sum_i gamma^i evals_i (kzg_open_fold_eval; not a reference method)."""
+        ys, ws = self.open_fold_batch([evals_list], [z], [gamma], ofmt)
+        return ys[0], ws[0]
+
+    def open_fold_batch(self, groups, zs, gammas, ofmt=L.G1_AFFINE_MONT, t=None):
+        """open_fold for len(zs) groups of t evaluation vectors each in one call -> (list of lists of y, list of witnesses).  groups: a
+        list of lists of EvaluationDomains / evaluation lists, or a canonical blob / DeviceBuffer of len(zs) x t x d scalars (t given)."""
+        e = self.engine
+        return e._open_fold(e.lib.kzg_open_fold_eval, self.lagrange_basis_g, groups, zs, gammas, ofmt, t, len(self.lagrange_basis_g), False)
+
     def create_witness_many(self, evals, indices, ofmt=L.G1_AFFINE_MONT):
         """Throughput form of create_witness (not a reference method): one witness per index, same evaluation vector."""
         e = self.engine
@@ -1359,6 +1479,14 @@ class KZGVerifierEvalForm:
     def verify_eval_batch(self, points, commitments, witnesses, r=None, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
         """KZGVerifier.verify_eval_batch with points[k] = (i_k, y_k) as verify_eval takes them: opening k is at omega^i_k."""
         return KZGVerifier(self.parameters).verify_eval_batch(self._at_omega(points), commitments, witnesses, r, commitment_idx, pfmt)
+
+    def verify_fold(self, z, ys, commitments, witness, gamma, pfmt=L.G1_AFFINE_MONT):
+        """KZGVerifier.verify_fold: z is a point of Fr as KZGProverEvalForm.open_fold takes it (not a domain index)."""
+        return KZGVerifier(self.parameters).verify_fold(z, ys, commitments, witness, gamma, pfmt)
+
+    def verify_fold_batch(self, zs, ys, commitments, witnesses, gammas, r=None, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
+        """KZGVerifier.verify_fold_batch for what KZGProverEvalForm.open_fold_batch produced."""
+        return KZGVerifier(self.parameters).verify_fold_batch(zs, ys, commitments, witnesses, gammas, r, commitment_idx, pfmt)
 
     def verify_eval_with_fallback(self, points, commitments, witnesses, r=None, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
         """One verdict per opening (points[k] = (i_k, y_k)): the batch check first, the per-opening checks only when it says no."""

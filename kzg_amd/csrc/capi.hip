@@ -758,6 +758,282 @@ extern "C" int kzg_open_eval(kzg_ctx *ctx, const kzg_srs *lagrange, const void *
 }
 
 // ---------------------------------------------------------------------------------------------
+// many polynomials at one point, one folded witness (fold.hip): F = sum_i gamma^i p_i, the witness of F
+// ---------------------------------------------------------------------------------------------
+constexpr size_t FOLD_STAGE_BYTES = (size_t)64 << 20;  // host vectors of kzg_fr_fold are staged in pieces of at most this (one vector at least)
+
+// what the three calls check alike: t, the sizes, the challenges (host scalars in [1, r)) -> Montgomery
+static int fold_args(kzg_ctx *ctx, const char *who, size_t d, size_t t, size_t groups, const void *gammas, int sfmt, std::vector<Fr> *gm) {
+    KZG_TRY(check_sfmt(ctx, sfmt));
+    if (t == 0) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": t == 0");
+    if (d == 0) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": empty vectors");
+    if (!count_ok(d) || !count_ok(t) || !count_ok(groups) || t > (SIZE_MAX >> 6) / d || groups > (SIZE_MAX >> 6) / (t * d))
+        return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": groups x t x d too large");
+    if (groups && !gammas) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL gammas");
+    try {  // (no exception may leave through the C ABI)
+        gm->resize(groups);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, KZG_ERR_ALLOC, "host memory for the challenges");
+    }
+    for (size_t g = 0; g < groups; g++) {
+        Fr x;
+        memcpy(x.v, (const uint8_t *)gammas + 32 * g, 32);
+        if (!is_canonical(x) || x.is_zero()) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": a challenge gamma must be in [1, modulus)");
+        (*gm)[g] = sfmt == KZG_FR_MONT_LE_32 ? x : to_mont(x);
+    }
+    return KZG_OK;
+}
+
+// the opening points of the folded calls: host scalars below r in either format
+static int fold_points_ok(kzg_ctx *ctx, const char *who, const void *zs, size_t groups) {
+    for (size_t g = 0; g < groups; g++) {
+        Fr x;
+        memcpy(x.v, (const uint8_t *)zs + 32 * g, 32);
+        if (!is_canonical(x)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": a point z >= modulus");
+    }
+    return KZG_OK;
+}
+
+// One group's t vectors of d scalars at src (host unless in_dev) folded into d_F on the lane's stream, in pieces of at most P vectors
+// from the last one down (the running sum stays at d_F); d_in: P x d scalars of staging (host input).  each(piece, i0, B), if given,
+// runs on every piece while it is on the device.
+template <typename Each>
+static int fold_group(kzg_ctx *ctx, int lane, const Fr *src, size_t d, size_t t, size_t P, bool in_dev, Fr *d_in, const Fr *d_gamma, Fr *d_F,
+                      Each each) {
+    hipStream_t st = ctx->lanes[lane].stream;
+    for (size_t i1 = t; i1 > 0;) {
+        const size_t i0 = i1 > P ? i1 - P : 0, B = i1 - i0;
+        const Fr *piece = src + i0 * d;
+        if (!in_dev) {
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_in, piece, B * d * 32, hipMemcpyHostToDevice, st));
+            piece = d_in;
+        }
+        KZG_TRY(each(piece, i0, B));
+        if (d_F) KZG_TRY(fold_run(ctx, st, piece, d, B, 0, 1, d_gamma, i1 != t, d_F));
+        i1 = i0;
+    }
+    return KZG_OK;
+}
+
+extern "C" int kzg_fr_fold(kzg_ctx *ctx, const void *vecs, size_t d, size_t t, size_t groups, const void *gammas, int sfmt, int flags, void *out) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    std::vector<Fr> gm;
+    KZG_TRY(fold_args(ctx, "kzg_fr_fold", d, t, groups, gammas, sfmt, &gm));
+    if (groups == 0) return KZG_OK;
+    if (!vecs || !out) return fail(ctx, KZG_ERR_SHAPE, "kzg_fr_fold: NULL vecs or out");
+    Lease ls;
+    KZG_TRY(lease_lane(ctx, &ls));
+    const int lane = ls.lane;
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->lanes[lane].stream;
+    const bool in_dev = (flags & KZG_IN_DEVICE) != 0, out_dev = (flags & KZG_OUT_DEVICE) != 0;
+    const size_t P = std::max<size_t>(1, std::min(t, FOLD_STAGE_BYTES / (d * 32)));      // vectors per staged piece
+    const size_t GC = out_dev ? groups : std::max<size_t>(1, std::min(groups, FOLD_STAGE_BYTES / (d * 32)));  // groups per chunk of host output
+    KZG_TRY(lane_reserve(ctx, lane, stage_bytes(P * d * 32, flags) + (out_dev ? 0 : align_up(GC * d * 32, 256)) + align_up(groups * 32, 256) + 65536));
+    Fr *d_in = in_dev ? nullptr : (Fr *)lane_alloc(ctx, lane, P * d * 32);
+    Fr *d_o = out_dev ? (Fr *)out : (Fr *)lane_alloc(ctx, lane, GC * d * 32);
+    Fr *d_gam = (Fr *)lane_alloc(ctx, lane, groups * 32);
+    if ((!in_dev && !d_in) || !d_o || !d_gam) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    struct Drain {  // nothing of the call is in flight once its host-side buffers go out of scope
+        hipStream_t st;
+        ~Drain() { hipStreamSynchronize(st); }
+    } drain{st};
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_gam, gm.data(), groups * 32, hipMemcpyHostToDevice, st));
+    for (size_t g0 = 0; g0 < groups; g0 += GC) {
+        const size_t G = std::min(GC, groups - g0);
+        Fr *o = out_dev ? d_o + g0 * d : d_o;
+        if (in_dev) {
+            KZG_TRY(fold_run(ctx, st, (const Fr *)vecs + g0 * t * d, d, t, t * d, G, d_gam + g0, false, o));
+        } else {
+            for (size_t g = 0; g < G; g++)
+                KZG_TRY(fold_group(ctx, lane, (const Fr *)vecs + (g0 + g) * t * d, d, t, P, false, d_in, d_gam + g0 + g, o + g * d,
+                                   [](const Fr *, size_t, size_t) { return (int)KZG_OK; }));
+        }
+        if (!out_dev) KZG_HIP_CHECK(ctx, hipMemcpyAsync((uint8_t *)out + g0 * d * 32, o, G * d * 32, hipMemcpyDeviceToHost, st));
+    }
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    KZG_HIP_CHECK(ctx, hipGetLastError());
+    if (ctx->prof) prof_collect(ctx);
+    return KZG_OK;
+}
+
+extern "C" int kzg_open_fold_eval(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals, size_t d, size_t t, size_t groups, const void *zs,
+                                  const void *gammas, int sfmt, int flags, void *ys_out, void *out_w, int ofmt) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    const char *who = "kzg_open_fold_eval";
+    if (!lagrange || (groups && (!evals || !zs))) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL lagrange, evals or zs");
+    if (!ys_out && !out_w) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": no output");
+    const size_t psz = point_format_bytes(ofmt);
+    if (!psz) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 output format");
+    if (d != lagrange->n) return fail(ctx, KZG_ERR_SHAPE, "assert!(self.d == evals.d) (src/eval_form.rs:115)");
+    if (lagrange->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the Lagrange SRS is resident on another GPU than this context's");
+    std::vector<Fr> gm;
+    KZG_TRY(fold_args(ctx, who, d, t, groups, gammas, sfmt, &gm));
+    KZG_TRY(fold_points_ok(ctx, who, zs, groups));
+    uint32_t log_d = 0;
+    std::vector<OpenPoint> pts, rep;  // one per group | a group's point once per polynomial of a piece
+    KZG_TRY(open_args(ctx, d, groups, zs, sfmt, &log_d, &pts));
+    if (groups == 0) return KZG_OK;
+    const bool in_dev = (flags & KZG_IN_DEVICE) != 0;
+    // vectors per piece: a chunk of the evaluation stage; host input is staged piece by piece (the bound of kzg_eval_form_eval)
+    const size_t P = std::max<size_t>(1, std::min<size_t>({(size_t)OE_MAX_CHUNK, t, in_dev ? t : ((size_t)1 << 22) / d}));
+    try {
+        rep.resize(P);
+        if (!out_w) pts.resize(groups * t);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, KZG_ERR_ALLOC, "host memory for the opening points");
+    }
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (!out_w) {  // the values alone: kzg_eval_form_eval with every group's point once per polynomial
+        for (size_t k = groups * t; k-- > 0;) pts[k] = pts[k / t];
+        return open_fr_only(ctx, 0, evals, log_d, groups * t, pts.data(), sfmt, flags & ~KZG_OUT_DEVICE, ys_out, nullptr);
+    }
+    BatchPipe bp;
+    KZG_TRY(batch_begin(ctx, groups, groups * psz, out_w, flags, &bp));
+    // Chunks of one GROUP per lane, on the plan of kzg_open_eval: the Fr stage of a chunk (values and fold of every group, then the
+    // quotients of the folded vectors) on the stream of one extra lane, the MSMs of chunk c on their lanes beside the Fr stage of c + 1.
+    const size_t chunk = (size_t)bp.nl;
+    const int sl = bp.nl;
+    const size_t qset = align_up(chunk * d * 32, 256);
+    int rc = ensure_lanes(ctx, sl + 1);
+    if (rc == KZG_OK)
+        rc = lane_reserve(ctx, sl, stage_bytes(P * d * 32, flags) + 3 * qset + align_up(groups * t * 32, 256) + 2 * align_up(groups * 32, 256) +
+                                       std::max(open_eval_fr_workspace_bytes(d, P, 1), open_eval_fr_workspace_bytes(d, chunk)) + 65536);
+    for (int l = 0; l < bp.nl && rc == KZG_OK; l++) rc = lane_reserve(ctx, l, msm_workspace_bytes(lagrange, d) + 65536);
+    hipStream_t fst = rc == KZG_OK ? ctx->lanes[sl].stream : nullptr;
+    Fr *d_in = nullptr, *d_y = nullptr, *d_yF = nullptr, *d_gam = nullptr, *d_F = nullptr, *d_q[2] = {nullptr, nullptr};
+    if (rc == KZG_OK) {
+        d_in = in_dev ? nullptr : (Fr *)lane_alloc(ctx, sl, P * d * 32);
+        d_y = (Fr *)lane_alloc(ctx, sl, groups * t * 32);
+        d_yF = (Fr *)lane_alloc(ctx, sl, groups * 32);
+        d_gam = (Fr *)lane_alloc(ctx, sl, groups * 32);
+        d_F = (Fr *)lane_alloc(ctx, sl, qset);
+        d_q[0] = (Fr *)lane_alloc(ctx, sl, qset);
+        d_q[1] = (Fr *)lane_alloc(ctx, sl, qset);
+        if ((!in_dev && !d_in) || !d_y || !d_yF || !d_gam || !d_F || !d_q[0] || !d_q[1]) rc = fail(ctx, KZG_ERR_ALLOC, "workspace");
+    }
+    if (rc == KZG_OK && hipMemcpyAsync(d_gam, gm.data(), groups * 32, hipMemcpyHostToDevice, fst) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "copy of the challenges");
+    std::vector<hipEvent_t> evs;
+    try {
+        evs.assign(2 + 2 * chunk, nullptr);
+    } catch (const std::bad_alloc &) {
+        if (rc == KZG_OK) rc = fail(ctx, KZG_ERR_ALLOC, "host memory");
+    }
+    for (size_t i = 0; i < evs.size() && rc == KZG_OK; i++)
+        if (hipEventCreateWithFlags(&evs[i], hipEventDisableTiming) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "hipEventCreate");
+    for (size_t b0 = 0, c = 0; b0 < groups && rc == KZG_OK; b0 += chunk, c++) {
+        const size_t B = std::min(chunk, groups - b0), p = c & 1;
+        hipEvent_t fr_done = evs[p], *lane_done = &evs[2 + p * chunk];
+        if (c >= 2)  // (every chunk but the last is full: all lanes recorded in chunk c - 2)
+            for (size_t l = 0; l < chunk && rc == KZG_OK; l++)
+                if (hipStreamWaitEvent(fst, lane_done[l], 0) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "hipStreamWaitEvent");
+        for (size_t b = 0; b < B && rc == KZG_OK; b++) {
+            const size_t gi = b0 + b;
+            for (size_t k = 0; k < P; k++) rep[k] = pts[gi];
+            rc = fold_group(ctx, sl, (const Fr *)evals + gi * t * d, d, t, P, in_dev, d_in, d_gam + gi, d_F + b * d,
+                            [&](const Fr *piece, size_t i0, size_t n) {
+                                return ys_out ? open_eval_fr_run(ctx, sl, piece, log_d, n, rep.data(), sfmt, d_y + gi * t + i0, nullptr) : (int)KZG_OK;
+                            });
+        }
+        if (rc == KZG_OK) rc = open_eval_fr_run(ctx, sl, d_F, log_d, B, pts.data() + b0, sfmt, d_yF + b0, d_q[p]);
+        if (rc == KZG_OK && hipEventRecord(fr_done, fst) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "hipEventRecord");
+        for (size_t b = 0; b < B && rc == KZG_OK; b++) {
+            const int l = (int)b;
+            hipStream_t st = ctx->lanes[l].stream;
+            ctx->lanes[l].arena_used = 0;  // stream order makes re-use of the lane arena safe
+            if (hipStreamWaitEvent(st, fr_done, 0) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "hipStreamWaitEvent");
+            MsmPoint *res = nullptr;
+            if (rc == KZG_OK) rc = batch_msm(ctx, bp, b0 + b, l, lagrange, 0, d_q[p] + b * d, d, sfmt, &res);
+            if (rc == KZG_OK) rc = emit_point(ctx, l, res, bp.d_out + (b0 + b) * psz, ofmt);
+            if (rc == KZG_OK && hipEventRecord(lane_done[l], st) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "hipEventRecord");
+        }
+    }
+    if (fst && hipStreamSynchronize(fst) != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "folded evaluation-form opening");
+    rc = batch_end(ctx, bp, rc, out_w, groups * psz);
+    for (hipEvent_t e : evs)
+        if (e) (void)hipEventDestroy(e);
+    if (rc == KZG_OK && ys_out) KZG_HIP_CHECK(ctx, hipMemcpy(ys_out, d_y, groups * t * 32, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+extern "C" int kzg_open_fold_coeff(kzg_ctx *ctx, const kzg_srs *srs, const void *coeffs, size_t n, size_t t, size_t groups, const void *zs,
+                                   const void *gammas, int sfmt, int flags, void *ys_out, void *out_w, int ofmt) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    const char *who = "kzg_open_fold_coeff";
+    if (!srs || (groups && (!coeffs || !zs))) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL srs, coeffs or zs");
+    if (!ys_out && !out_w) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": no output");
+    const size_t psz = point_format_bytes(ofmt);
+    if (!psz) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 output format");
+    std::vector<Fr> gm, zm;
+    KZG_TRY(fold_args(ctx, who, n, t, groups, gammas, sfmt, &gm));
+    KZG_TRY(fold_points_ok(ctx, who, zs, groups));
+    if (n - 1 > srs->n) return fail(ctx, KZG_ERR_SHAPE, "quotient longer than the SRS (reference: slice index panic)");
+    if (srs->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the SRS is resident on another GPU than this context's");
+    try {
+        zm.resize(groups);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, KZG_ERR_ALLOC, "host memory for the opening points");
+    }
+    for (size_t g = 0; g < groups; g++) KZG_TRY(host_scalar(ctx, (const uint8_t *)zs + 32 * g, sfmt, &zm[g]));
+    if (groups == 0) return KZG_OK;
+    const bool in_dev = (flags & KZG_IN_DEVICE) != 0;
+    const size_t P = std::max<size_t>(1, std::min<size_t>({(size_t)OE_MAX_CHUNK, t, in_dev ? t : ((size_t)1 << 22) / n}));
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    BatchPipe bp;
+    if (out_w) {
+        KZG_TRY(batch_begin(ctx, groups, groups * psz, out_w, flags, &bp));
+    } else {
+        bp.nl = 1;  // the values alone: lane 0, no MSM
+    }
+    // what the lanes share lives in the arena of one extra lane: the values and the challenges
+    const int sl = bp.nl;
+    int rc = ensure_lanes(ctx, sl + 1);
+    if (rc == KZG_OK) rc = lane_reserve(ctx, sl, align_up(groups * t * 32, 256) + align_up(groups * 32, 256) + 4096);
+    Fr *d_y = nullptr, *d_gam = nullptr;
+    if (rc == KZG_OK) {
+        d_y = (Fr *)lane_alloc(ctx, sl, groups * t * 32);
+        d_gam = (Fr *)lane_alloc(ctx, sl, groups * 32);
+        if (!d_y || !d_gam) rc = fail(ctx, KZG_ERR_ALLOC, "workspace");
+    }
+    if (rc == KZG_OK && hipMemcpy(d_gam, gm.data(), groups * 32, hipMemcpyHostToDevice) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "copy of the challenges");
+    const size_t horner = (n / 2048 + 4) * 64 + 65536;  // one poly_eval_run / quotient_linear_run
+    const size_t per = (out_w ? msm_workspace_bytes(srs, n - 1) + 2 * align_up(n * 32, 256) : 0) + stage_bytes(P * n * 32, flags) + horner + 65536;
+    for (int l = 0; l < bp.nl && rc == KZG_OK; l++) rc = lane_reserve(ctx, l, per);
+    for (size_t gi = 0; gi < groups && rc == KZG_OK; gi++) {
+        const int l = (int)(gi % (size_t)bp.nl);
+        ctx->lanes[l].arena_used = 0;  // stream order makes re-use of the lane arena safe
+        Fr *d_in = in_dev ? nullptr : (Fr *)lane_alloc(ctx, l, P * n * 32);
+        Fr *d_F = out_w ? (Fr *)lane_alloc(ctx, l, n * 32) : nullptr, *dq = out_w ? (Fr *)lane_alloc(ctx, l, n * 32) : nullptr;
+        Fr *dpx = (Fr *)lane_alloc(ctx, l, 256);
+        if ((!in_dev && !d_in) || (out_w && (!d_F || !dq)) || !dpx) rc = fail(ctx, KZG_ERR_ALLOC, "workspace");
+        if (rc == KZG_OK)
+            rc = fold_group(ctx, l, (const Fr *)coeffs + gi * t * n, n, t, P, in_dev, d_in, d_gam + gi, d_F, [&](const Fr *piece, size_t i0, size_t B) {
+                const size_t mark = ctx->lanes[l].arena_used;
+                for (size_t k = 0; k < B && ys_out; k++) {
+                    KZG_TRY(poly_eval_run(ctx, l, piece + k * n, n, zm[gi], d_y + gi * t + i0 + k));
+                    ctx->lanes[l].arena_used = mark;  // (stream order)
+                }
+                return (int)KZG_OK;
+            });
+        if (!out_w) continue;
+        if (rc == KZG_OK) rc = quotient_linear_run(ctx, l, d_F, n, zm[gi], dq, dpx);
+        MsmPoint *res = nullptr;
+        if (rc == KZG_OK) rc = batch_msm(ctx, bp, gi, l, srs, 0, dq, n - 1, sfmt, &res);
+        if (rc == KZG_OK) rc = emit_point(ctx, l, res, bp.d_out + gi * psz, ofmt);
+    }
+    if (out_w) {
+        rc = batch_end(ctx, bp, rc, out_w, groups * psz);
+    } else {
+        if (hipStreamSynchronize(ctx->lanes[0].stream) != hipSuccess && rc == KZG_OK) rc = fail(ctx, KZG_ERR_HIP, "folded coefficient-form opening");
+        if (ctx->prof) prof_collect(ctx);
+    }
+    if (rc == KZG_OK && ys_out) KZG_HIP_CHECK(ctx, hipMemcpy(ys_out, d_y, groups * t * 32, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
 // witnesses
 // ---------------------------------------------------------------------------------------------
 extern "C" int kzg_witness_coeff(kzg_ctx *ctx, const kzg_srs *srs, const void *coeffs, size_t n, const void *x,

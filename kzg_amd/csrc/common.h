@@ -448,7 +448,13 @@ struct OpenPoint {                // an opening point, classified on the host
 };
 int open_point_classify(uint32_t log_d, const Fr &z_mont, OpenPoint *pt);  // KZG_ERR_INTERNAL: the walk over the bits of m broke down
 size_t open_eval_fr_workspace_bytes(size_t d, size_t B);                   // arena bytes one open_eval_fr_run of B polynomials takes
+size_t open_eval_fr_workspace_bytes(size_t d, size_t B, size_t nz);        // ... when they have at most nz distinct points
 // y (d_y + b) and, unless d_q is null, the quotient (d_q + b d) of B <= OE_MAX_CHUNK polynomials (d_evals + b d) at pts[b], on the lane's stream
 int open_eval_fr_run(kzg_ctx *ctx, int lane, const Fr *d_evals, uint32_t log_d, size_t B, const OpenPoint *pts, int sfmt, Fr *d_y, Fr *d_q);
+
+// fold.hip: d_out[g d + j] = sum_{i < t} gamma_g^i d_v[g gstride + i d + j], g < groups (gammas Montgomery, on the device); with carry
+// the sum starts from d_out[g d + j] gamma_g^t: pieces of a group folded from the last one down
+int fold_run(kzg_ctx *ctx, hipStream_t st, const Fr *d_v, size_t d, size_t t, size_t gstride, size_t groups, const Fr *d_gammas_mont,
+             bool carry, Fr *d_out);
 
 }  // namespace kzg

@@ -138,11 +138,12 @@ int open_point_classify(uint32_t log_d, const Fr &z_mont, OpenPoint *pt) {
     return KZG_OK;
 }
 
-size_t open_eval_fr_workspace_bytes(size_t d, size_t B) {
+size_t open_eval_fr_workspace_bytes(size_t d, size_t B, size_t nz) {
     const size_t hi_n = std::max<size_t>(1, d >> OE_LO_LOG), nblk = (d + 255) / 256;
-    // the power tables | denominators and inverses (at most one set per polynomial) | block partials of both paths | slack for alignment
-    return align_up((OE_LO + hi_n) * 32, 256) + 2 * align_up(B * d * 32, 256) + 2 * align_up(B * nblk * 32 + 256, 256) + 8192;
+    // the power tables | denominators and inverses (one set per distinct point) | block partials of both paths | slack for alignment
+    return align_up((OE_LO + hi_n) * 32, 256) + 2 * align_up(nz * d * 32, 256) + 2 * align_up(B * nblk * 32 + 256, 256) + 8192;
 }
+size_t open_eval_fr_workspace_bytes(size_t d, size_t B) { return open_eval_fr_workspace_bytes(d, B, B); }  // at most one point per polynomial
 
 // One chunk on the lane's stream: y (and q unless d_q is null) of B <= OE_MAX_CHUNK polynomials, polynomial b at d_evals + b d,
 // its quotient at d_q + b d, its value at d_y + b.  Takes its scratch from the lane's arena and gives it back (stream order
