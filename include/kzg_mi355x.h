@@ -167,6 +167,7 @@ int kzg_sync(kzg_ctx *ctx);
  * table: 34 GB at 2^20; measured +3.7 % batched throughput at 2^20, nothing below 2^19, +1.3 ms on a lone commit: opt-in);
  * "verify_cosets_chunk" (0 = default; n: kzg_verify_cosets works in chunks of at most n cells),
  * "verify_eval_batch_chunk" (0 = default, 16384; n <= 16384: kzg_verify_eval_batch works in chunks of at most n openings),
+ * "multiopen_points_chunk" (0 = default, min(16, 2^22 / d); n <= 16: kzg_multiopen_eval_commit works in chunks of at most n distinct points),
  * "host_pairing" (1 / 0: the one pairing check that ends kzg_verify_cosets_batch / kzg_verify_eval_batch runs on the calling thread -- the same tower code
  *  compiled for the host -- instead of in a one-thread kernel; the same verdict, default 1),
  * "fk20_cosets_combine" (0 = the shared-doubling Straus kernel, default; 1 = one mul256 per term: the same bytes, for comparison),
@@ -442,6 +443,57 @@ int kzg_open_fold_eval(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals,
  * of the folded coefficients, one MSM.  Outputs, errors and groups == 0 as above (n == 0 and n - 1 > kzg_srs_len(srs): KZG_ERR_SHAPE). */
 int kzg_open_fold_coeff(kzg_ctx *ctx, const kzg_srs *srs, const void *coeffs, size_t n, size_t t, size_t groups, const void *zs,
                         const void *gammas, int sfmt, int flags, void *ys_out, void *out_w, int ofmt);
+/* ---- many polynomials at MANY points with one two-element proof (not a reference method) -----------------------------------------
+ * N = count claims p_{m(k)}(z_k) = y_k, claim k naming polynomial m(k) = poly_idx[k] < n_polys (NULL: m(k) = k, count == n_polys
+ * required) and any point z_k of Fr, are answered by the N values and TWO group elements, whatever N and however many distinct points:
+ *   g(X) = sum_k r^k (p_{m(k)}(X) - y_k) / (X - z_k),   D = [g(tau)]_1                                  (first phase:  *_commit)
+ *   w_k = r^k / (t - z_k),  W_m = sum_{m(k) = m} w_k,  v = sum_m W_m p_m - g,  pi = [(v - v(t)) / (X - t)]_1   (second phase: *_finish)
+ * and v(t) = g2 = sum_k w_k y_k identically.  kzg_verify_multiopen (below) checks (D, pi): one pairing check.  The shape of PLONK-family
+ * provers (openings at z, z w and beyond) and of Verkle-style / aggregate-blob provers (thousands of openings at points of the domain).
+ * Against kzg_open_eval (one MSM and one witness per claim) and kzg_open_fold_* (one per distinct point) a call costs one streaming
+ * pass per claim and ONE MSM per phase.
+ * WHAT THE CALLER OWES.  r must be unpredictable to whoever chose the polynomials, points and values: a hash of the commitments, zs
+ * and ys.  t MUST BE DRAWN AFTER D EXISTS: a hash that includes D.  With a t known in advance a single wrong claim (C, z, y') passes
+ * without any knowledge of tau: take pi = the identity and D = (C - [y'] gs[0]) / (t - z).  This is why the prover is TWO calls: the
+ * library has no hash.  The phases are stateless; the caller carries g (and may drop everything else) between them.  If t equals
+ * some z_k the second phase and the verifier return KZG_ERR_SHAPE and the caller draws another t.
+ * The linear combination alone: out[j] = sum_{k < count} weights[k] vecs[idx[k] d + j] for j < d (any d >= 1), idx[k] < n_vecs; weights:
+ * host scalars below the modulus in sfmt.  vecs and out are host memory, or device memory with KZG_IN_DEVICE / KZG_OUT_DEVICE; out
+ * has the form of the inputs; canonical inputs may hold any 256-bit value (they count as their residue).  Host vectors are staged in
+ * pieces of at most 64 MiB with the running sum on the device.  Leases one lane.  count == 0: out is zeroed. */
+int kzg_fr_lincomb(kzg_ctx *ctx, const void *vecs, size_t d, size_t n_vecs, const uint32_t *idx, const void *weights, size_t count, int sfmt,
+                   int flags, void *out);
+/* Evaluation form: evals holds n_polys vectors of d values (stride d), d a power of two == kzg_srs_len(lagrange).  First phase:
+ * ys_out[k] = p_{m(k)}(z_k) (host, count scalars: the values of kzg_eval_form_eval), g_out = the d values of g on the domain, D at out_d
+ * in ofmt (each of the three optional, not all NULL).  evals and g / g_out are host memory, or device memory with KZG_IN_DEVICE; g has the
+ * form (canonical or Montgomery) of the inputs; D and pi follow KZG_OUT_DEVICE; zs, r, t, ys_out and y_out are host memory.  Second
+ * phase: the same claims and r, the t drawn from D, g as the first phase left it; pi at out_pi and v(t) at y_out (optional; a caller
+ * may check v(t) == g2).  Both take the context exclusively and run ONE MSM each.  The claims are sorted by point on the host; distinct
+ * points off the domain are worked off in chunks of at most min(16, 2^22 / d) (option "multiopen_points_chunk": 0 = that, 1..16 lowers
+ * it): per chunk the denominators w^i - z_u are inverted once per distinct point, the chunk's values are formed, and ONE pass
+ * (k_multiopen_accum) adds the chunk's share to g in device memory -- no quotient and no combined polynomial is written.  Points
+ * w^m of the domain take the materialised route one by one (combination, the quotient of kzg_quotient_eval, an add into g).
+ * Limits: host polynomials are uploaded once, whole, per call (both phases read them at random through the indices): n_polys x d x 32
+ * bytes of workspace, KZG_ERR_ALLOC if that does not fit -- callers with large sets keep them resident (KZG_IN_DEVICE).  Beyond that:
+ * g, per chunk 2 x min(16, 2^22 / d) x d scalars, 72 bytes per claim, one MSM workspace.
+ * KZG_ERR_SHAPE, before memory is touched: d not a power of two or != kzg_srs_len(lagrange), a z, r or t >= modulus, r == 0, t equal to a
+ * z_k, an index >= n_polys, NULL indices with count != n_polys, an unknown format, a NULL pointer with count > 0, an SRS on another
+ * GPU.  count == 0: g_out is zeroed, D and pi are the identity, KZG_OK. */
+int kzg_multiopen_eval_commit(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals, size_t d, size_t n_polys, const uint32_t *poly_idx,
+                              const void *zs, size_t count, const void *r, int sfmt, int flags, void *ys_out, void *g_out, void *out_d, int ofmt);
+int kzg_multiopen_eval_finish(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals, size_t d, size_t n_polys, const uint32_t *poly_idx,
+                              const void *zs, size_t count, const void *r, const void *t, const void *g, int sfmt, int flags, void *y_out,
+                              void *out_pi, int ofmt);
+/* Coefficient form: coeffs holds n_polys polynomials of n >= 1 coefficients each (the caller pads to the common length; stride n),
+ * n - 1 <= kzg_srs_len(srs); g has n - 1 coefficients.  Values from kzg_poly_eval's stage per claim, per distinct point the combination
+ * (k_fr_lincomb) and the linear quotient of kzg_quotient_linear accumulated into g, one MSM of n - 1 scalars; the second phase is the
+ * combination minus g, the linear quotient at t, one MSM.  Outputs, flags, errors and count == 0 as above (n == 0, n - 1 >
+ * kzg_srs_len(srs): KZG_ERR_SHAPE). */
+int kzg_multiopen_coeff_commit(kzg_ctx *ctx, const kzg_srs *srs, const void *coeffs, size_t n, size_t n_polys, const uint32_t *poly_idx,
+                               const void *zs, size_t count, const void *r, int sfmt, int flags, void *ys_out, void *g_out, void *out_d, int ofmt);
+int kzg_multiopen_coeff_finish(kzg_ctx *ctx, const kzg_srs *srs, const void *coeffs, size_t n, size_t n_polys, const uint32_t *poly_idx,
+                               const void *zs, size_t count, const void *r, const void *t, const void *g, int sfmt, int flags, void *y_out,
+                               void *out_pi, int ofmt);
 /* ---- all openings over the domain (FK20, single-point case; not a reference method) ---------------------------------
  * Every witness of a polynomial at every point w^m of its size-N domain (w = compute_omega(N).omega) in O(N log N) group
  * operations instead of N MSMs: two G1 DFTs, 2N variable-base scalar multiplications and one Fr NTT per polynomial, against a
@@ -660,6 +712,24 @@ int kzg_verify_eval_batch(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs,
 int kzg_verify_fold(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *zs, const void *ys, int sfmt,
                     const void *commitments, size_t n_commitments, const uint32_t *commitment_idx, const void *witnesses, int pfmt,
                     size_t t, size_t groups, const void *gammas, const void *r, int *ok);
+/* The verifier of kzg_multiopen_*_commit / _finish: ONE verdict from one pairing check for count claims p_{m(k)}(zs[k]) = ys[k] answered
+ * by the two elements d_point (D) and pi; m(k) = commitment_idx[k] names one of the n_commitments points of `commitments` (NULL:
+ * m(k) = k, n_commitments == count required).  With w_k = r^k / (t - z_k):
+ *   E = sum_m W_m C_m,  W_m = sum_{m(k) = m} w_k,  g2 = sum_k w_k y_k;   *ok = [ e(pi, hs[1]) e(-(t pi + E - D - [g2] gs[0]), hs[0]) == 1 ]:
+ * kzg_verify_eval of the commitment E - D at (t, g2) with the witness pi.  zs, ys: count host scalars, r, t: one each, all in sfmt; ys
+ * are taken as kzg_verify_eval_batch takes them (a value >= the modulus counts as its residue); zs, r and t are range-checked.
+ * WHAT THE CALLER OWES.  r must be unpredictable to whoever chose the polynomials, points and values; t MUST BE DRAWN AFTER D WAS
+ * RECEIVED, as a hash that includes D.  With a t the prover knew before it chose D, ONE WRONG claim (C, z, y') passes: pi = the
+ * identity and D = (C - [y'] gs[0]) / (t - z), which needs no knowledge of tau.  Honest proofs pass for every r and every t that is
+ * no z_k.  *ok == 0 does not say which claim is bad.
+ * KZG_ERR_SHAPE, before memory is touched and with *ok unwritten: r == 0 or >= modulus, t or a z >= modulus, t equal to a z_k (the
+ * caller draws another t), an index >= n_commitments, NULL indices with n_commitments != count, and every condition of
+ * kzg_verify_eval_batch (formats, SRS, NULL pointers).  count == 0: *ok = 1 (if ok is non-NULL), KZG_OK.  Point validation of every
+ * C_m, D and pi and KZG_ERR_BAD_POINT (*ok unwritten), the lane, the chunking (option "verify_eval_batch_chunk": the weights are
+ * formed on the host with one inversion per chunk) and options "host_pairing" / "trusted_points" are kzg_verify_eval_batch's. */
+int kzg_verify_multiopen(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *zs, const void *ys, int sfmt,
+                         const void *commitments, size_t n_commitments, const uint32_t *commitment_idx, size_t count, const void *r,
+                         const void *t, const void *d_point, const void *pi, int pfmt, int *ok);
 
 /* ---- Fr polynomial helpers on the path (device) ---------------------------------------------- */
 /* Polynomial::eval (src/polynomial.rs:156-165) at one point. */

@@ -195,11 +195,28 @@ inline std::vector<Scalar> fr_fold(const Engine &e, const std::vector<Scalar> &v
     return out;
 }
 
+// kzg_fr_lincomb: out[j] = sum_k weights[k] vecs[idx[k] d + j], j < d (vecs: n_vecs x d scalars back to back).  Not a reference method.
+inline std::vector<Scalar> fr_lincomb(const Engine &e, const std::vector<Scalar> &vecs, size_t d, const std::vector<uint32_t> &idx,
+                                      const std::vector<Scalar> &weights) {
+    static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+    if (d == 0 || vecs.size() % d != 0 || idx.size() != weights.size()) throw ReferencePanic("fr_lincomb: shape");
+    std::vector<Scalar> out(d);
+    e.check(kzg_fr_lincomb(e.ctx(), vecs.data(), d, vecs.size() / d, idx.data(), weights.data(), idx.size(), KZG_FR_CANONICAL_LE_32, 0, out.data()));
+    return out;
+}
+
 struct KZGBatchWitness {  // src/coeff_form.rs:12-35
     Polynomial r;
     G1Affine w;
     const G1Affine &elem() const { return w; }
     const Polynomial &polynomial() const { return r; }
+};
+
+// The first phase of the two-element multiproof (kzg_multiopen_*_commit): the claimed values, the quotient polynomial g the caller
+// carries to the second phase, and its commitment D.  The second phase returns (pi, v(t)).  Not reference methods.
+struct KZGMultiopenCommit {
+    std::vector<Scalar> ys, g;
+    KZGCommitment d;
 };
 
 class KZGProver {  // src/coeff_form.rs:37-112
@@ -246,6 +263,31 @@ class KZGProver {  // src/coeff_form.rs:37-112
         e_.check(kzg_open_fold_coeff(e_.ctx(), params_.gs, coeffs.data(), n, t, zs.size(), zs.data(), gammas.data(), KZG_FR_CANONICAL_LE_32, 0,
                                      r.first.data(), r.second.data(), KZG_G1_AFFINE_MONT_96));
         return r;
+    }
+    // kzg_multiopen_coeff_commit / _finish: claim k is polynomial poly_idx[k] (empty poly_idx: k) of the coeffs.size() / n polynomials of n
+    // coefficients (back to back, padded by the caller) at zs[k].  t MUST be drawn after D exists (a hash that includes D): see the header.
+    KZGMultiopenCommit multiopen_commit(const std::vector<Scalar> &coeffs, size_t n, const std::vector<uint32_t> &poly_idx, const std::vector<Scalar> &zs,
+                                        const Scalar &r) const {
+        static_assert(sizeof(Scalar) == 32 && sizeof(G1Affine) == 96, "packed encodings");
+        if (n == 0 || coeffs.size() % n != 0 || (!poly_idx.empty() && poly_idx.size() != zs.size())) throw ReferencePanic("multiopen_commit: shape");
+        KZGMultiopenCommit c{std::vector<Scalar>(zs.size()), std::vector<Scalar>(n - 1), KZGCommitment{}};
+        std::vector<Scalar> g(n);  // (never an empty buffer)
+        e_.check(kzg_multiopen_coeff_commit(e_.ctx(), params_.gs, coeffs.data(), n, coeffs.size() / n, poly_idx.empty() ? nullptr : poly_idx.data(),
+                                            zs.data(), zs.size(), r.le.data(), KZG_FR_CANONICAL_LE_32, 0, c.ys.data(), g.data(), &c.d, KZG_G1_AFFINE_MONT_96));
+        std::copy(g.begin(), g.begin() + (n - 1), c.g.begin());
+        return c;
+    }
+    std::pair<KZGWitness, Scalar> multiopen_finish(const std::vector<Scalar> &coeffs, size_t n, const std::vector<uint32_t> &poly_idx,
+                                                   const std::vector<Scalar> &zs, const Scalar &r, const Scalar &t, const std::vector<Scalar> &g) const {
+        if (n == 0 || coeffs.size() % n != 0 || g.size() != n - 1 || (!poly_idx.empty() && poly_idx.size() != zs.size()))
+            throw ReferencePanic("multiopen_finish: shape");
+        std::pair<KZGWitness, Scalar> out;
+        std::vector<Scalar> gp(g);
+        gp.resize(n);
+        e_.check(kzg_multiopen_coeff_finish(e_.ctx(), params_.gs, coeffs.data(), n, coeffs.size() / n, poly_idx.empty() ? nullptr : poly_idx.data(),
+                                            zs.data(), zs.size(), r.le.data(), t.le.data(), gp.data(), KZG_FR_CANONICAL_LE_32, 0, &out.second, &out.first,
+                                            KZG_G1_AFFINE_MONT_96));
+        return out;
     }
     KZGBatchWitness create_witness_batched(const Polynomial &p, const std::vector<Scalar> &xs,
                                            const std::vector<Scalar> &ys) const {  // :83-111
@@ -326,6 +368,21 @@ class KZGVerifier {  // src/coeff_form.rs:114-183; the pairing checks run on the
         e_.check(kzg_verify_fold(e_.ctx(), params_.gs, params_.hs, zs.data(), ys.data(), KZG_FR_CANONICAL_LE_32, cb.data(), commitments.size(),
                                  commitment_idx.empty() ? nullptr : commitment_idx.data(), wb.data(), KZG_G1_AFFINE_MONT_96, t, groups,
                                  gammas.data(), r.le.data(), &ok));
+        return ok != 0;
+    }
+    // kzg_verify_multiopen: true iff the two elements (d, pi) answer ALL claims p_{m(k)}(zs[k]) = ys[k], m(k) = commitment_idx[k] (empty:
+    // k), from one pairing check.  r as the prover used it; t MUST have been drawn after d was received: see the header.
+    bool verify_multiopen(const std::vector<Scalar> &zs, const std::vector<Scalar> &ys, const std::vector<KZGCommitment> &commitments,
+                          const std::vector<uint32_t> &commitment_idx, const Scalar &r, const Scalar &t, const KZGCommitment &d,
+                          const KZGWitness &pi) const {
+        if (!params_.hs) throw ReferencePanic("KZGParams.hs is empty (index out of bounds)");
+        if (ys.size() != zs.size() || (!commitment_idx.empty() && commitment_idx.size() != zs.size())) throw ReferencePanic("verify_multiopen: shape");
+        std::vector<uint8_t> cb(commitments.size() * 96);
+        for (size_t i = 0; i < commitments.size(); i++) std::memcpy(cb.data() + 96 * i, commitments[i].bytes.data(), 96);
+        int ok = 0;
+        e_.check(kzg_verify_multiopen(e_.ctx(), params_.gs, params_.hs, zs.data(), ys.data(), KZG_FR_CANONICAL_LE_32, cb.data(), commitments.size(),
+                                      commitment_idx.empty() ? nullptr : commitment_idx.data(), zs.size(), r.le.data(), t.le.data(), d.bytes.data(),
+                                      pi.bytes.data(), KZG_G1_AFFINE_MONT_96, &ok));
         return ok != 0;
     }
     bool verify_eval_batched(const std::vector<Scalar> &xs, const KZGCommitment &c, const KZGBatchWitness &w) const {  // :144-182
@@ -566,6 +623,27 @@ class KZGProverEvalForm {  // src/eval_form.rs:39-147
         e_.check(kzg_open_fold_eval(e_.ctx(), lag_, evals.data(), d_, t, zs.size(), zs.data(), gammas.data(), KZG_FR_CANONICAL_LE_32, 0,
                                     r.first.data(), r.second.data(), KZG_G1_AFFINE_MONT_96));
         return r;
+    }
+
+    // kzg_multiopen_eval_commit / _finish: claim k is the polynomial with the evaluations number poly_idx[k] (empty poly_idx: k) of the
+    // evals.size() / degree() vectors (back to back) at zs[k], any point of Fr.  t MUST be drawn after D exists: see the header.
+    KZGMultiopenCommit multiopen_commit(const std::vector<Scalar> &evals, const std::vector<uint32_t> &poly_idx, const std::vector<Scalar> &zs,
+                                        const Scalar &r) const {
+        static_assert(sizeof(Scalar) == 32 && sizeof(G1Affine) == 96, "packed encodings");
+        if (evals.size() % d_ != 0 || (!poly_idx.empty() && poly_idx.size() != zs.size())) throw ReferencePanic("multiopen_commit: shape");
+        KZGMultiopenCommit c{std::vector<Scalar>(zs.size()), std::vector<Scalar>(d_), KZGCommitment{}};
+        e_.check(kzg_multiopen_eval_commit(e_.ctx(), lag_, evals.data(), d_, evals.size() / d_, poly_idx.empty() ? nullptr : poly_idx.data(), zs.data(),
+                                           zs.size(), r.le.data(), KZG_FR_CANONICAL_LE_32, 0, c.ys.data(), c.g.data(), &c.d, KZG_G1_AFFINE_MONT_96));
+        return c;
+    }
+    std::pair<KZGWitness, Scalar> multiopen_finish(const std::vector<Scalar> &evals, const std::vector<uint32_t> &poly_idx, const std::vector<Scalar> &zs,
+                                                   const Scalar &r, const Scalar &t, const std::vector<Scalar> &g) const {
+        if (evals.size() % d_ != 0 || g.size() != d_ || (!poly_idx.empty() && poly_idx.size() != zs.size())) throw ReferencePanic("multiopen_finish: shape");
+        std::pair<KZGWitness, Scalar> out;
+        e_.check(kzg_multiopen_eval_finish(e_.ctx(), lag_, evals.data(), d_, evals.size() / d_, poly_idx.empty() ? nullptr : poly_idx.data(), zs.data(),
+                                           zs.size(), r.le.data(), t.le.data(), g.data(), KZG_FR_CANONICAL_LE_32, 0, &out.second, &out.first,
+                                           KZG_G1_AFFINE_MONT_96));
+        return out;
     }
 
   private:

@@ -151,6 +151,12 @@ def load(path=None):
         "kzg_open_fold_eval": (i32, [vp, vp, vp, sz, sz, sz, vp, vp, i32, i32, vp, vp, i32]),
         "kzg_open_fold_coeff": (i32, [vp, vp, vp, sz, sz, sz, vp, vp, i32, i32, vp, vp, i32]),
         "kzg_verify_fold": (i32, [vp, vp, vp, vp, vp, i32, vp, sz, ctypes.POINTER(u32), vp, i32, sz, sz, vp, vp, ctypes.POINTER(i32)]),
+        "kzg_fr_lincomb": (i32, [vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, i32, i32, vp]),
+        "kzg_multiopen_eval_commit": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, i32, i32, vp, vp, vp, i32]),
+        "kzg_multiopen_eval_finish": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, vp, vp, i32, i32, vp, vp, i32]),
+        "kzg_multiopen_coeff_commit": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, i32, i32, vp, vp, vp, i32]),
+        "kzg_multiopen_coeff_finish": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, vp, vp, i32, i32, vp, vp, i32]),
+        "kzg_verify_multiopen": (i32, [vp, vp, vp, vp, vp, i32, vp, sz, ctypes.POINTER(u32), sz, vp, vp, vp, vp, i32, ctypes.POINTER(i32)]),
         "kzg_poly_mul": (i32, [vp, vp, sz, vp, sz, i32, i32, vp]),
         "kzg_dev_alloc": (i32, [vp, sz, c_void_pp]),
         "kzg_dev_free": (i32, [vp, vp]),

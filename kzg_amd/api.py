@@ -359,6 +359,113 @@ class Engine:
         return ([[self._scalar_from(ys.raw[32 * (g * t + i):32 * (g * t + i) + 32], sfmt) for i in range(t)] for g in range(groups)],
                 [out.raw[g * psz:(g + 1) * psz] for g in range(groups)])
 
+    def _enc_scalar(self, x, sfmt):
+        """a host scalar in sfmt; a value outside [0, R) goes through as it is, for the library to refuse"""
+        x = int(x)
+        if not 0 <= x < (1 << 256):
+            raise ReferencePanic("a scalar is no 256-bit unsigned value")
+        return self._host_scalar(x, sfmt) if x < R_MODULUS else x.to_bytes(32, "little")
+
+    def fr_lincomb(self, vecs, d, idx, weights, out=None):
+        """kzg_fr_lincomb: out[j] = sum_k weights[k] vecs[idx[k] d + j] for j < d.  vecs: a flat list of ints, a canonical blob or a
+        DeviceBuffer of n_vecs x d scalars; idx: vector indices; weights: ints in [0, R).  Returns the d sums as ints, or `out` (a
+        DeviceBuffer of the inputs' scalar format) when one is given."""
+        count = len(idx)
+        if len(weights) != count:
+            raise ReferencePanic("fr_lincomb: one weight per index")
+        ptr, have, sfmt, flags, _keep = self._scalars_arg(vecs)
+        n_vecs = have // d if d else 0
+        ia = (ctypes.c_uint32 * max(count, 1))(*[int(i) % (1 << 32) for i in idx])
+        wb = b"".join(self._enc_scalar(w, sfmt) for w in weights)
+        if out is not None:
+            if out.n < d or out.sfmt != sfmt:
+                raise ReferencePanic("fr_lincomb: out holds %d scalars, d = %d (and has the inputs' format)" % (out.n, d))
+            rc = self.lib.kzg_fr_lincomb(self.ctx, ptr, d, n_vecs, ia, wb, count, sfmt, flags | L.OUT_DEVICE, out.ptr)
+            if rc:
+                _raise(self, rc)
+            return out
+        buf = ctypes.create_string_buffer(32 * max(d, 1))
+        rc = self.lib.kzg_fr_lincomb(self.ctx, ptr, d, n_vecs, ia, wb, count, sfmt, flags, buf)
+        if rc:
+            _raise(self, rc)
+        return [self._scalar_from(buf.raw[32 * k:32 * k + 32], sfmt) for k in range(d)]
+
+    def _multiopen_vectors_arg(self, vecs, length, pad):
+        """(pointer, length, n_polys, sfmt, flags, keep-alive) of the polynomials of a multiopen call: a list of vectors (lists of ints,
+        EvaluationDomains or Polynomials; with `pad` filled with zeros to the longest) or a flat blob / DeviceBuffer (length given)"""
+        if not isinstance(vecs, (DeviceBuffer, bytes, bytearray, memoryview)):
+            rows = [v.coeffs if isinstance(v, EvaluationDomain) else (v.slice_coeffs() if isinstance(v, Polynomial) else list(v)) for v in vecs]
+            if length is None:
+                length = max([len(v) for v in rows] + [1])
+            if any(len(v) > length or (not pad and len(v) != length) for v in rows):
+                raise ReferencePanic("a vector does not fit the length %d" % length)
+            vecs = [x for v in rows for x in list(v) + [0] * (length - len(v))]
+        ptr, have, sfmt, flags, keep = self._scalars_arg(vecs)
+        if not length:
+            raise ReferencePanic("the length of the vectors is needed with a flat buffer")
+        return ptr, length, have // length, sfmt, flags, keep
+
+    @staticmethod
+    def _index_arg(poly_idx, count):
+        if poly_idx is None:
+            return None
+        if len(poly_idx) != count:
+            raise ReferencePanic("one polynomial index per claim")
+        return (ctypes.c_uint32 * max(count, 1))(*[int(i) % (1 << 32) for i in poly_idx])
+
+    def _multiopen_commit(self, fn, srs, vecs, length, glen_of, pad, zs, r, poly_idx, ofmt):
+        """the body of multiopen_commit of both provers -> (ys, g, D); g: ints, or a DeviceBuffer when the polynomials are one"""
+        count = len(zs)
+        ptr, length, n_polys, sfmt, flags, _keep = self._multiopen_vectors_arg(vecs, length, pad)
+        glen = glen_of(length)
+        ys = ctypes.create_string_buffer(32 * max(count, 1))
+        out = ctypes.create_string_buffer(L.POINT_BYTES[ofmt])
+        zb = b"".join(self._enc_scalar(z, sfmt) for z in zs)
+        g_dev = DeviceBuffer(self, max(glen, 1), sfmt) if flags & L.IN_DEVICE else None
+        g_host = None if g_dev else ctypes.create_string_buffer(32 * max(glen, 1))
+        rc = fn(self.ctx, srs.handle, ptr, length, n_polys, self._index_arg(poly_idx, count), zb, count, self._enc_scalar(r, sfmt), sfmt, flags, ys,
+                g_dev.ptr if g_dev else g_host, out, ofmt)
+        if rc:
+            if g_dev:
+                g_dev.free()
+            _raise(self, rc)
+        g = g_dev if g_dev else [self._scalar_from(g_host.raw[32 * j:32 * j + 32], sfmt) for j in range(glen)]
+        return [self._scalar_from(ys.raw[32 * k:32 * k + 32], sfmt) for k in range(count)], g, out.raw
+
+    def _multiopen_finish(self, fn, srs, vecs, length, glen_of, pad, zs, r, t, g, poly_idx, ofmt):
+        """the body of multiopen_finish of both provers -> (pi, v(t))"""
+        count = len(zs)
+        ptr, length, n_polys, sfmt, flags, _keep = self._multiopen_vectors_arg(vecs, length, pad)
+        glen = glen_of(length)
+        if isinstance(g, DeviceBuffer) != bool(flags & L.IN_DEVICE):
+            raise ReferencePanic("multiopen_finish: g lives where the polynomials live (host lists, or DeviceBuffers)")
+        if isinstance(g, DeviceBuffer):
+            if g.n < glen or g.sfmt != sfmt:
+                raise ReferencePanic("multiopen_finish: g holds %d scalars of format %d, the call needs %d of format %d" % (g.n, g.sfmt, glen, sfmt))
+            gp = g.ptr
+        else:
+            if len(g) != glen:
+                raise ReferencePanic("multiopen_finish: g has %d scalars, the call needs %d" % (len(g), glen))
+            gp = pack_scalars(g) + bytes(32)
+        y = ctypes.create_string_buffer(32)
+        out = ctypes.create_string_buffer(L.POINT_BYTES[ofmt])
+        zb = b"".join(self._enc_scalar(z, sfmt) for z in zs)
+        rc = fn(self.ctx, srs.handle, ptr, length, n_polys, self._index_arg(poly_idx, count), zb, count, self._enc_scalar(r, sfmt),
+                self._enc_scalar(t, sfmt), gp, sfmt, flags, y, out, ofmt)
+        if rc:
+            _raise(self, rc)
+        return out.raw, self._scalar_from(y.raw, sfmt)
+
+    def _multiopen(self, commit, finish, vecs, zs, r, challenge_t, poly_idx, ofmt, **kw):
+        ys, g, D = commit(vecs, zs, r, poly_idx, ofmt, **kw)
+        try:
+            t = challenge_t(D)  # t is drawn AFTER D exists: the caller's hash of D (and of whatever else the protocol binds)
+            pi, _ = finish(vecs, zs, r, t, g, poly_idx, ofmt, **kw)
+        finally:
+            if isinstance(g, DeviceBuffer):
+                g.free()
+        return ys, D, pi, t
+
     def _eval_vectors_arg(self, evals, batch, d=None):
         """(pointer, d, sfmt, flags, keep-alive) of `batch` evaluation vectors, stride d"""
         if not isinstance(evals, (DeviceBuffer, bytes, bytearray, memoryview)) and len(evals) and not isinstance(evals[0], int):
@@ -1170,6 +1277,25 @@ class KZGProver:
         e = self.engine
         return e._open_fold(e.lib.kzg_open_fold_coeff, self.parameters.gs, groups, zs, gammas, ofmt, t, n, True)
 
+    def multiopen_commit(self, polynomials, zs, r, poly_idx=None, ofmt=L.G1_AFFINE_MONT, n=None):
+        """First phase of the two-element multiproof (kzg_multiopen_coeff_commit; not a reference method): claim k is polynomial
+        poly_idx[k] (None: k) at zs[k].  -> (ys, g, D): the values, the n - 1 coefficients of g = sum_k r^k (p - y_k)/(X - z_k) (the
+        caller carries them to multiopen_finish; a DeviceBuffer when the polynomials are one) and D = [g(tau)].  polynomials: a list of
+        Polynomials / coefficient lists (padded here to the longest), or a canonical blob / DeviceBuffer of n_polys x n coefficients (n
+        given).  r must be unpredictable to whoever chose polynomials, points and values."""
+        e = self.engine
+        return e._multiopen_commit(e.lib.kzg_multiopen_coeff_commit, self.parameters.gs, polynomials, n, lambda n_: n_ - 1, True, zs, r, poly_idx, ofmt)
+
+    def multiopen_finish(self, polynomials, zs, r, t, g, poly_idx=None, ofmt=L.G1_AFFINE_MONT, n=None):
+        """Second phase (kzg_multiopen_coeff_finish) -> (pi, v(t)).  t MUST have been drawn after D existed (a hash that includes D):
+        see the header.  t equal to a z_k raises ReferencePanic; draw another."""
+        e = self.engine
+        return e._multiopen_finish(e.lib.kzg_multiopen_coeff_finish, self.parameters.gs, polynomials, n, lambda n_: n_ - 1, True, zs, r, t, g, poly_idx, ofmt)
+
+    def multiopen(self, polynomials, zs, r, challenge_t, poly_idx=None, ofmt=L.G1_AFFINE_MONT, n=None):
+        """Both phases -> (ys, D, pi, t): challenge_t(D) is called between them and returns t, the caller's hash of D."""
+        return self.engine._multiopen(self.multiopen_commit, self.multiopen_finish, polynomials, zs, r, challenge_t, poly_idx, ofmt, n=n)
+
     def create_witness_many(self, polynomial, points, ofmt=L.G1_AFFINE_MONT, coeffs_device=None):
         """Throughput form of create_witness (not a reference method): one witness per (x, y) in `points`, all for the same
         polynomial, pipelined on the engine's lanes.  Returns (witnesses, ok) with ok[j] False where the reference would
@@ -1315,6 +1441,25 @@ class KZGVerifier:
             _raise(e, rc)
         return bool(ok.value)
 
+    def verify_multiopen(self, zs, ys, commitments, D, pi, r, t, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
+        """kzg_verify_multiopen (not a reference method): ONE verdict from one pairing check for the claims p_{m(k)}(zs[k]) = ys[k]
+        answered by the two elements (D, pi) of multiopen; m(k) = commitment_idx[k] (None: k).  r: the challenge the prover used,
+        unpredictable to whoever chose polynomials, points and values; t MUST have been drawn after D was received (a hash that
+        includes D): with a predictable t one wrong claim passes, see the header."""
+        e = self.engine
+        count = len(zs)
+        if len(ys) != count:
+            raise ReferencePanic("verify_multiopen: one value per point")
+        idx = Engine._index_arg(commitment_idx, count)
+        ok = ctypes.c_int(-1)
+        enc = lambda x: int(x).to_bytes(32, "little")
+        rc = e.lib.kzg_verify_multiopen(e.ctx, self.parameters.gs.handle, self._hs().handle, b"".join(enc(z) for z in zs), pack_scalars(ys),
+                                        L.FR_CANONICAL, b"".join(commitments), len(commitments), idx, count, enc(r), enc(t), D, pi, pfmt,
+                                        ctypes.byref(ok))
+        if rc:
+            _raise(e, rc)
+        return bool(ok.value)
+
     def verify_eval_with_fallback(self, points, commitments, witnesses, r=None, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
         """One verdict per opening, as verify_eval_many(): the batch check first, and the per-opening checks only when it says no."""
         if self.verify_eval_batch(points, commitments, witnesses, r, commitment_idx, pfmt):
@@ -1423,6 +1568,27 @@ class KZGProverEvalForm:
         e = self.engine
         return e._open_fold(e.lib.kzg_open_fold_eval, self.lagrange_basis_g, groups, zs, gammas, ofmt, t, len(self.lagrange_basis_g), False)
 
+    def multiopen_commit(self, evals, zs, r, poly_idx=None, ofmt=L.G1_AFFINE_MONT):
+        """First phase of the two-element multiproof (kzg_multiopen_eval_commit; not a reference method): claim k is the polynomial with
+        the evaluations evals[poly_idx[k]] (None: k) at zs[k], ANY point of Fr.  -> (ys, g, D): the values, the d values of
+        g = sum_k r^k (p - y_k)/(X - z_k) on the domain (the caller carries them to multiopen_finish; a DeviceBuffer when the
+        evaluations are one) and D = [g(tau)].  evals: a list of EvaluationDomains / evaluation lists, or a canonical blob / DeviceBuffer
+        of n_polys x d scalars.  r must be unpredictable to whoever chose polynomials, points and values."""
+        e = self.engine
+        return e._multiopen_commit(e.lib.kzg_multiopen_eval_commit, self.lagrange_basis_g, evals, len(self.lagrange_basis_g), lambda d: d, False, zs, r,
+                                   poly_idx, ofmt)
+
+    def multiopen_finish(self, evals, zs, r, t, g, poly_idx=None, ofmt=L.G1_AFFINE_MONT):
+        """Second phase (kzg_multiopen_eval_finish) -> (pi, v(t)).  t MUST have been drawn after D existed (a hash that includes D):
+        see the header.  t equal to a z_k raises ReferencePanic; draw another."""
+        e = self.engine
+        return e._multiopen_finish(e.lib.kzg_multiopen_eval_finish, self.lagrange_basis_g, evals, len(self.lagrange_basis_g), lambda d: d, False, zs, r, t,
+                                   g, poly_idx, ofmt)
+
+    def multiopen(self, evals, zs, r, challenge_t, poly_idx=None, ofmt=L.G1_AFFINE_MONT):
+        """Both phases -> (ys, D, pi, t): challenge_t(D) is called between them and returns t, the caller's hash of D."""
+        return self.engine._multiopen(self.multiopen_commit, self.multiopen_finish, evals, zs, r, challenge_t, poly_idx, ofmt)
+
     def create_witness_many(self, evals, indices, ofmt=L.G1_AFFINE_MONT):
         """Throughput form of create_witness (not a reference method): one witness per index, same evaluation vector."""
         e = self.engine
@@ -1487,6 +1653,10 @@ class KZGVerifierEvalForm:
     def verify_fold_batch(self, zs, ys, commitments, witnesses, gammas, r=None, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
         """KZGVerifier.verify_fold_batch for what KZGProverEvalForm.open_fold_batch produced."""
         return KZGVerifier(self.parameters).verify_fold_batch(zs, ys, commitments, witnesses, gammas, r, commitment_idx, pfmt)
+
+    def verify_multiopen(self, zs, ys, commitments, D, pi, r, t, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
+        """KZGVerifier.verify_multiopen: zs are points of Fr as KZGProverEvalForm.multiopen takes them (not domain indices)."""
+        return KZGVerifier(self.parameters).verify_multiopen(zs, ys, commitments, D, pi, r, t, commitment_idx, pfmt)
 
     def verify_eval_with_fallback(self, points, commitments, witnesses, r=None, commitment_idx=None, pfmt=L.G1_AFFINE_MONT):
         """One verdict per opening (points[k] = (i_k, y_k)): the batch check first, the per-opening checks only when it says no."""

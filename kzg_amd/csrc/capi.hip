@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "emit.h"
+#include "multiopen_plan.h"
 
 namespace kzg {
 
@@ -1031,6 +1032,498 @@ extern "C" int kzg_open_fold_coeff(kzg_ctx *ctx, const kzg_srs *srs, const void 
     }
     if (rc == KZG_OK && ys_out) KZG_HIP_CHECK(ctx, hipMemcpy(ys_out, d_y, groups * t * 32, hipMemcpyDeviceToHost));
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// many polynomials at many points, one two-element proof (multiopen.hip, multiopen_plan.h): D = [g]_1 and pi, DESIGN.md section 3.4d
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct MoArgs {            // what the calls check alike, before memory is touched
+    std::vector<Fr> z;     // the claims' points, Montgomery
+    Fr r, t;               // the challenges, Montgomery
+};
+
+// sizes, formats, pointers, indices, every z and the challenges; t_in null: a first phase
+int mo_args(kzg_ctx *ctx, const char *who, size_t len, size_t n_polys, const uint32_t *poly_idx, const void *zs, size_t count, const void *r,
+            const void *t_in, int sfmt, MoArgs *a) {
+    KZG_TRY(check_sfmt(ctx, sfmt));
+    if (!count_ok(len) || !count_ok(n_polys) || count > ((size_t)1 << 31) || n_polys > ((size_t)1 << 31) || (n_polys && len > (SIZE_MAX >> 6) / n_polys))
+        return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": n_polys x length or count too large");
+    if (!poly_idx && count != n_polys) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": without indices there is one claim per polynomial");
+    if (count && (!zs || !r || !n_polys)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL zs or r, or no polynomial");
+    if (poly_idx)
+        for (size_t k = 0; k < count; k++)
+            if (poly_idx[k] >= n_polys) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": polynomial index >= n_polys");
+    try {  // (no exception may leave through the C ABI)
+        a->z.resize(count);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, KZG_ERR_ALLOC, "host memory for the opening points");
+    }
+    auto challenge = [&](const void *src, bool nonzero, const char *what, Fr *out) {
+        Fr x;
+        memcpy(x.v, src, 32);
+        if (!is_canonical(x) || (nonzero && x.is_zero())) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": " + what);
+        *out = sfmt == KZG_FR_MONT_LE_32 ? x : to_mont(x);
+        return (int)KZG_OK;
+    };
+    a->r = a->t = Fr::one();
+    if (r) KZG_TRY(challenge(r, true, "the challenge r must be in [1, modulus)", &a->r));
+    if (t_in) KZG_TRY(challenge(t_in, false, "the challenge t >= modulus", &a->t));
+    for (size_t k = 0; k < count; k++) {
+        KZG_TRY(challenge((const uint8_t *)zs + 32 * k, false, "a point z >= modulus", &a->z[k]));
+        if (t_in && a->z[k] == a->t) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": t equals a point z_k (draw another t)");
+    }
+    return KZG_OK;
+}
+
+struct MoBlob {  // host tables that go to the device in one copy
+    std::vector<uint8_t> h;
+    size_t add(const void *src, size_t bytes) {
+        const size_t off = align_up(h.size(), 256);
+        h.resize(off + std::max<size_t>(bytes, 16));
+        if (src && bytes) memcpy(h.data() + off, src, bytes);
+        return off;
+    }
+};
+
+struct MoDrain {  // nothing of the call is in flight once its host-side buffers go out of scope
+    hipStream_t st;
+    ~MoDrain() { hipStreamSynchronize(st); }
+};
+
+// the end of the four calls: g (len scalars on the device, sfmt) against the SRS -> the point at `out`; len == 0: the identity
+int mo_commit_point(kzg_ctx *ctx, const kzg_srs *srs, const Fr *d_g, size_t len, int sfmt, int flags, void *out, int ofmt) {
+    MsmPoint *res = nullptr;
+    if (len) {
+        KZG_TRY(msm_run(ctx, 0, srs, 0, d_g, len, sfmt, &res));
+    } else {
+        if (!(res = (MsmPoint *)lane_alloc(ctx, 0, sizeof(MsmPoint)))) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+        KZG_TRY(point_set_infinity(ctx, ctx->lanes[0].stream, res));
+    }
+    return finish_point(ctx, 0, res, out, ofmt, flags);
+}
+
+// the weights of the second phase on the host: W_m = sum_{m(k) = m} r^k / (t - z_k), the one batch inversion of the call
+int mo_poly_weights_host(kzg_ctx *ctx, const MoArgs &a, const uint32_t *poly_idx, size_t n_polys, std::vector<Fr> *W) {
+    try {
+        std::vector<Fr> w(a.z.size());
+        W->assign(n_polys, Fr::zero());
+        Fr rk = Fr::one();
+        if (!mo_weights(a.z.data(), a.z.size(), a.r, a.t, &rk, w.data())) return fail(ctx, KZG_ERR_SHAPE, "t equals a point z_k");
+        mo_poly_weights(w.data(), poly_idx, 0, a.z.size(), W->data());
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, KZG_ERR_ALLOC, "host memory for the weights");
+    }
+    return KZG_OK;
+}
+
+// v = sum_m W_m p_m - g on lane 0: g (glen <= len scalars) enters at weight -1, then the n_polys vectors; consts: W | -1 | the indices 0 .. n_polys - 1 | 0
+int mo_second_phase_vector(kzg_ctx *ctx, const Fr *d_polys, size_t len, size_t n_polys, const Fr *d_g, size_t glen, const std::vector<Fr> &W, MoBlob *blob,
+                           Fr *d_v) {
+    hipStream_t st = ctx->lanes[0].stream;
+    const Fr minus_one = neg(Fr::one());
+    std::vector<uint32_t> ident(n_polys + 1);
+    for (size_t m = 0; m < n_polys; m++) ident[m] = (uint32_t)m;
+    ident[n_polys] = 0;
+    const size_t o_w = blob->add(W.data(), n_polys * 32), o_m1 = blob->add(minus_one.v, 32), o_id = blob->add(ident.data(), (n_polys + 1) * 4);
+    uint8_t *d_tab = (uint8_t *)lane_alloc(ctx, 0, blob->h.size());
+    if (!d_tab) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_tab, blob->h.data(), blob->h.size(), hipMemcpyHostToDevice, st));
+    if (glen < len) KZG_HIP_CHECK(ctx, hipMemsetAsync(d_v, 0, len * 32, st));
+    KZG_TRY(lincomb_run(ctx, st, d_g, glen, (const uint32_t *)(d_tab + o_id) + n_polys, (const Fr *)(d_tab + o_m1), 1, false, d_v));
+    return lincomb_run(ctx, st, d_polys, len, (const uint32_t *)(d_tab + o_id), (const Fr *)(d_tab + o_w), n_polys, true, d_v);
+}
+}  // namespace
+
+extern "C" int kzg_fr_lincomb(kzg_ctx *ctx, const void *vecs, size_t d, size_t n_vecs, const uint32_t *idx, const void *weights, size_t count,
+                              int sfmt, int flags, void *out) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    const char *who = "kzg_fr_lincomb";
+    KZG_TRY(check_sfmt(ctx, sfmt));
+    if (d == 0) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": empty vectors");
+    if (!count_ok(d) || !count_ok(n_vecs) || !count_ok(count) || n_vecs > ((size_t)1 << 31) || (n_vecs && d > (SIZE_MAX >> 6) / n_vecs))
+        return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": n_vecs x d or count too large");
+    if (!out || (count && (!vecs || !idx || !weights))) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL vecs, idx, weights or out");
+    for (size_t k = 0; k < count; k++)
+        if (idx[k] >= n_vecs) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": index >= n_vecs");
+    std::vector<Fr> wm;
+    try {
+        wm.resize(count);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, KZG_ERR_ALLOC, "host memory for the weights");
+    }
+    for (size_t k = 0; k < count; k++) {
+        Fr x;
+        memcpy(x.v, (const uint8_t *)weights + 32 * k, 32);
+        if (!is_canonical(x)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": a weight >= modulus");
+        wm[k] = sfmt == KZG_FR_MONT_LE_32 ? x : to_mont(x);
+    }
+    Lease ls;
+    KZG_TRY(lease_lane(ctx, &ls));
+    const int lane = ls.lane;
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->lanes[lane].stream;
+    const bool in_dev = (flags & KZG_IN_DEVICE) != 0, out_dev = (flags & KZG_OUT_DEVICE) != 0;
+    // host vectors are staged one piece of named vectors at a time, with the running sum on the device (carry)
+    const size_t P = in_dev ? count : std::max<size_t>(1, std::min(std::max<size_t>(count, 1), FOLD_STAGE_BYTES / (d * 32)));
+    KZG_TRY(lane_reserve(ctx, lane, stage_bytes(P * d * 32, flags) + (out_dev ? 0 : align_up(d * 32, 256)) + align_up(count * 32 + 32, 256) +
+                                        align_up(std::max(count, P) * 4 + 4, 256) + 65536));
+    Fr *d_in = in_dev ? nullptr : (Fr *)lane_alloc(ctx, lane, P * d * 32);
+    Fr *d_o = out_dev ? (Fr *)out : (Fr *)lane_alloc(ctx, lane, d * 32);
+    Fr *d_w = (Fr *)lane_alloc(ctx, lane, count * 32 + 32);
+    uint32_t *d_idx = (uint32_t *)lane_alloc(ctx, lane, std::max(count, P) * 4 + 4);
+    if ((!in_dev && !d_in) || !d_o || !d_w || !d_idx) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    std::vector<uint32_t> local;
+    MoDrain drain{st};
+    if (count) KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_w, wm.data(), count * 32, hipMemcpyHostToDevice, st));
+    if (in_dev) {
+        if (count) KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_idx, idx, count * 4, hipMemcpyHostToDevice, st));
+        KZG_TRY(lincomb_run(ctx, st, (const Fr *)vecs, d, d_idx, d_w, count, false, d_o));
+    } else {
+        try {
+            local.resize(P);
+        } catch (const std::bad_alloc &) {
+            return fail(ctx, KZG_ERR_ALLOC, "host memory for the indices");
+        }
+        for (size_t k = 0; k < P; k++) local[k] = (uint32_t)k;
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_idx, local.data(), P * 4, hipMemcpyHostToDevice, st));
+        if (!count) KZG_TRY(lincomb_run(ctx, st, d_in, d, d_idx, d_w, 0, false, d_o));
+        for (size_t k0 = 0; k0 < count; k0 += P) {
+            const size_t B = std::min(P, count - k0);
+            for (size_t k = 0; k < B; k++)
+                KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_in + k * d, (const Fr *)vecs + (size_t)idx[k0 + k] * d, d * 32, hipMemcpyHostToDevice, st));
+            KZG_TRY(lincomb_run(ctx, st, d_in, d, d_idx, d_w + k0, B, k0 != 0, d_o));
+        }
+    }
+    if (!out_dev) KZG_HIP_CHECK(ctx, hipMemcpyAsync(out, d_o, d * 32, hipMemcpyDeviceToHost, st));
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    KZG_HIP_CHECK(ctx, hipGetLastError());
+    if (ctx->prof) prof_collect(ctx);
+    return KZG_OK;
+}
+
+extern "C" int kzg_multiopen_eval_commit(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals, size_t d, size_t n_polys, const uint32_t *poly_idx,
+                                         const void *zs, size_t count, const void *r, int sfmt, int flags, void *ys_out, void *g_out, void *out_d,
+                                         int ofmt) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    const char *who = "kzg_multiopen_eval_commit";
+    if (!lagrange) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL lagrange");
+    if (!point_format_bytes(ofmt)) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 output format");
+    if (!is_pow2(d)) return fail(ctx, KZG_ERR_SHAPE, "evaluation domain size must be a power of two");
+    if (d != lagrange->n) return fail(ctx, KZG_ERR_SHAPE, "assert!(self.d == evals.d) (src/eval_form.rs:115)");
+    if (lagrange->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the Lagrange SRS is resident on another GPU than this context's");
+    const uint32_t log_d = (uint32_t)ilog2_ceil(d);
+    if (log_d >= FR_TWO_ADICITY) return fail(ctx, KZG_ERR_DEGREE_TOO_LARGE, "domain too large");
+    MoArgs a;
+    KZG_TRY(mo_args(ctx, who, d, n_polys, poly_idx, zs, count, r, nullptr, sfmt, &a));
+    if (count && !evals) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL evals");
+    if (!ys_out && !g_out && !out_d) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": no output");
+    // ---- the plan: claims sorted by point, the distinct points classified, the off-domain ones first ----
+    MoPlan plan;
+    std::vector<OpenPoint> pts;
+    std::vector<uint32_t> vidx, pu, src;
+    std::vector<Fr> cw, cs;
+    size_t n_off = 0, max_claims = 1;
+    const size_t cap = mo_chunk_points(d, ctx->opt_multiopen_points_chunk);
+    MoBlob blob;
+    size_t o_vidx = 0, o_pu = 0, o_cw = 0, o_ps = 0, o_z = 0, o_c = 0, o_one = 0, o_zero = 0;
+    try {
+        mo_plan(a.z.data(), count, a.r, &plan);
+        const size_t U = plan.points();
+        std::vector<OpenPoint> cls(U);
+        std::vector<uint8_t> on(U);
+        for (size_t u = 0; u < U; u++) {
+            if (open_point_classify(log_d, plan.z[u], &cls[u]) != KZG_OK) return fail(ctx, KZG_ERR_INTERNAL, "z^d == 1 but z is no power of omega");
+            on[u] = cls[u].on_domain ? 1 : 0;
+        }
+        n_off = mo_off_domain_first(&plan, on.data(), &src);
+        pts.resize(U);
+        cs.resize(U);
+        for (size_t u = 0; u < U; u++) {
+            pts[u] = cls[src[u]];
+            cs[u] = pts[u].c;
+        }
+        vidx.resize(count);
+        pu.resize(count);
+        cw.resize(count);
+        for (size_t u = 0; u < U; u++)
+            for (uint32_t s = plan.pstart[u]; s < plan.pstart[u + 1]; s++) {
+                const uint32_t k = plan.order[s];
+                vidx[s] = poly_idx ? poly_idx[k] : k;
+                pu[s] = u < n_off ? (uint32_t)(u % cap) : (uint32_t)pts[u].m;  // its point of the chunk | its place on the domain
+                cw[s] = plan.rk[k];
+            }
+        for (size_t u0 = 0; u0 < n_off; u0 += cap)
+            max_claims = std::max<size_t>(max_claims, plan.pstart[std::min(u0 + cap, n_off)] - plan.pstart[u0]);
+        const Fr one = Fr::one();
+        const uint32_t zero = 0;
+        o_vidx = blob.add(vidx.data(), count * 4);
+        o_pu = blob.add(pu.data(), count * 4);
+        o_cw = blob.add(cw.data(), count * 32);
+        o_ps = blob.add(plan.pstart.data(), (U + 1) * 4);
+        o_z = blob.add(plan.z.data(), U * 32);
+        o_c = blob.add(cs.data(), U * 32);
+        o_one = blob.add(one.v, 32);
+        o_zero = blob.add(&zero, 4);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, KZG_ERR_ALLOC, "host memory for the plan");
+    }
+    const size_t U = plan.points(), n_on = U - n_off;
+    const bool in_dev = (flags & KZG_IN_DEVICE) != 0, g_dev = in_dev && g_out;
+    const bool want_g = g_out || out_d;  // the values alone: no quotient work (as the coefficient form)
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->lanes[0].stream;
+    const size_t vec = align_up(d * 32, 256), nblk = (d + 255) / 256, ncap = std::min(cap, std::max<size_t>(n_off, 1));
+    KZG_TRY(lane_reserve(ctx, 0, stage_bytes(n_polys * d * 32, flags) + (g_dev ? 0 : vec) + align_up(blob.h.size(), 256) + align_up(count * 32 + 32, 256) +
+                                     align_up(U * 32 + 32, 256) +
+                                     (n_off ? align_up(open_powtab_bytes(d), 256) + 2 * align_up(ncap * d * 32, 256) + align_up(std::min<size_t>(max_claims, 65535) * nblk * 32, 256) : 0) +
+                                     (n_on ? 2 * vec + align_up(nblk * 32, 256) : 0) + msm_workspace_bytes(lagrange, d) + 65536));
+    std::vector<uint8_t> ys_sorted;  // (outlives the drain of the stream that fills it)
+    MoDrain drain{st};
+    const void *d_polys = nullptr;
+    if (count) KZG_TRY(stage_in(ctx, 0, evals, n_polys * d * 32, flags, &d_polys));  // host polynomials: once, whole
+    Fr *d_g = g_dev ? (Fr *)g_out : (Fr *)lane_alloc(ctx, 0, d * 32);
+    uint8_t *d_tab = (uint8_t *)lane_alloc(ctx, 0, blob.h.size());
+    Fr *d_y = (Fr *)lane_alloc(ctx, 0, count * 32 + 32), *d_Y = (Fr *)lane_alloc(ctx, 0, U * 32 + 32);
+    if (!d_g || !d_tab || !d_y || !d_Y) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_tab, blob.h.data(), blob.h.size(), hipMemcpyHostToDevice, st));
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(d_g, 0, d * 32, st));
+    const uint32_t *t_vidx = (const uint32_t *)(d_tab + o_vidx), *t_pu = (const uint32_t *)(d_tab + o_pu), *t_ps = (const uint32_t *)(d_tab + o_ps);
+    const Fr *t_cw = (const Fr *)(d_tab + o_cw), *t_z = (const Fr *)(d_tab + o_z), *t_c = (const Fr *)(d_tab + o_c);
+    if (n_off) {  // chunks of at most `cap` distinct points: inverses, the values of the chunk's claims, one accumulation pass
+        Fr *tab = (Fr *)lane_alloc(ctx, 0, open_powtab_bytes(d));
+        Fr *den = (Fr *)lane_alloc(ctx, 0, ncap * d * 32), *iv = (Fr *)lane_alloc(ctx, 0, ncap * d * 32);
+        Fr *partial = (Fr *)lane_alloc(ctx, 0, std::min<size_t>(max_claims, 65535) * nblk * 32);
+        if (!tab || !den || !iv || !partial) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+        KZG_TRY(open_powtab_run(ctx, st, log_d, tab));
+        for (size_t u0 = 0; u0 < n_off; u0 += cap) {
+            const int nz = (int)std::min(cap, n_off - u0);
+            const size_t s0 = plan.pstart[u0], s1 = plan.pstart[u0 + nz];
+            KZG_TRY(open_inverses_run(ctx, st, log_d, tab, plan.z.data() + u0, nz, den, iv));
+            KZG_TRY(open_eval_values_idx_run(ctx, st, (const Fr *)d_polys, log_d, iv, t_vidx + s0, t_pu + s0, t_z + u0, t_c + u0, s1 - s0, partial, d_y + s0));
+            if (want_g) KZG_TRY(multiopen_accum_run(ctx, st, (const Fr *)d_polys, d, t_vidx, t_cw, t_ps + u0, nz, d_y, d_Y + u0, iv, d_g));
+        }
+    }
+    if (n_on) {  // points of the domain: the values as they are stored; F_u materialised, the unchanged quotient, added into g
+        const size_t s0 = plan.pstart[n_off];
+        KZG_TRY(multiopen_gather_run(ctx, st, (const Fr *)d_polys, d, t_vidx + s0, t_pu + s0, count - s0, d_y + s0));
+        Fr *d_F = (Fr *)lane_alloc(ctx, 0, d * 32), *d_q = (Fr *)lane_alloc(ctx, 0, d * 32);
+        if (!d_F || !d_q) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+        const size_t mark = ctx->lanes[0].arena_used;
+        for (size_t u = n_off; u < U && want_g; u++) {
+            const size_t a0 = plan.pstart[u], a1 = plan.pstart[u + 1];
+            KZG_TRY(lincomb_run(ctx, st, (const Fr *)d_polys, d, t_vidx + a0, t_cw + a0, a1 - a0, false, d_F));
+            KZG_TRY(quotient_eval_run(ctx, 0, d_F, log_d, pts[u].m, sfmt, d_q));
+            ctx->lanes[0].arena_used = mark;  // (stream order)
+            KZG_TRY(lincomb_run(ctx, st, d_q, d, (const uint32_t *)(d_tab + o_zero), (const Fr *)(d_tab + o_one), 1, true, d_g));
+        }
+    }
+    if (ys_out && count) {
+        try {
+            ys_sorted.resize(count * 32);
+        } catch (const std::bad_alloc &) {
+            return fail(ctx, KZG_ERR_ALLOC, "host memory for the values");
+        }
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(ys_sorted.data(), d_y, count * 32, hipMemcpyDeviceToHost, st));
+    }
+    if (g_out && !g_dev) KZG_HIP_CHECK(ctx, hipMemcpyAsync(g_out, d_g, d * 32, hipMemcpyDeviceToHost, st));
+    if (out_d) {
+        KZG_TRY(mo_commit_point(ctx, lagrange, d_g, count ? d : 0, sfmt, flags, out_d, ofmt));  // the ONE MSM of the call
+    } else {
+        KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        if (ctx->prof) prof_collect(ctx);
+    }
+    for (size_t s = 0; s < ys_sorted.size() / 32; s++) memcpy((uint8_t *)ys_out + 32 * (size_t)plan.order[s], ys_sorted.data() + 32 * s, 32);
+    return KZG_OK;
+}
+
+extern "C" int kzg_multiopen_eval_finish(kzg_ctx *ctx, const kzg_srs *lagrange, const void *evals, size_t d, size_t n_polys, const uint32_t *poly_idx,
+                                         const void *zs, size_t count, const void *r, const void *t, const void *g_in, int sfmt, int flags, void *y_out,
+                                         void *out_pi, int ofmt) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    const char *who = "kzg_multiopen_eval_finish";
+    if (!lagrange || !t) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL lagrange or t");
+    if (!point_format_bytes(ofmt)) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 output format");
+    if (!is_pow2(d)) return fail(ctx, KZG_ERR_SHAPE, "evaluation domain size must be a power of two");
+    if (d != lagrange->n) return fail(ctx, KZG_ERR_SHAPE, "assert!(self.d == evals.d) (src/eval_form.rs:115)");
+    if (lagrange->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the Lagrange SRS is resident on another GPU than this context's");
+    const uint32_t log_d = (uint32_t)ilog2_ceil(d);
+    if (log_d >= FR_TWO_ADICITY) return fail(ctx, KZG_ERR_DEGREE_TOO_LARGE, "domain too large");
+    MoArgs a;
+    KZG_TRY(mo_args(ctx, who, d, n_polys, poly_idx, zs, count, r, t, sfmt, &a));
+    if (count && (!evals || !g_in)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL evals or g");
+    if (!y_out && !out_pi) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": no output");
+    OpenPoint pt;
+    if (open_point_classify(log_d, a.t, &pt) != KZG_OK) return fail(ctx, KZG_ERR_INTERNAL, "t^d == 1 but t is no power of omega");
+    std::vector<Fr> W;
+    KZG_TRY(mo_poly_weights_host(ctx, a, poly_idx, n_polys, &W));
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->lanes[0].stream;
+    const size_t vec = align_up(d * 32, 256);
+    KZG_TRY(lane_reserve(ctx, 0, stage_bytes(n_polys * d * 32, flags) + stage_bytes(d * 32, flags) + 2 * vec + align_up(n_polys * 36 + 1024, 256) + 1024 +
+                                     open_eval_fr_workspace_bytes(d, 1) + msm_workspace_bytes(lagrange, d) + 65536));
+    MoBlob blob;  // (outlives the drain of the stream that reads it)
+    MoDrain drain{st};
+    if (!count) {  // no claim: v = 0
+        if (y_out) memset(y_out, 0, 32);
+        if (out_pi) return mo_commit_point(ctx, lagrange, nullptr, 0, sfmt, flags, out_pi, ofmt);
+        return KZG_OK;
+    }
+    const void *d_polys = nullptr, *d_g = nullptr;
+    KZG_TRY(stage_in(ctx, 0, evals, n_polys * d * 32, flags, &d_polys));  // host polynomials: once, whole
+    KZG_TRY(stage_in(ctx, 0, g_in, d * 32, flags, &d_g));
+    Fr *d_v = (Fr *)lane_alloc(ctx, 0, d * 32), *d_q = (Fr *)lane_alloc(ctx, 0, d * 32), *d_y = (Fr *)lane_alloc(ctx, 0, 256);
+    if (!d_v || !d_q || !d_y) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    try {
+        KZG_TRY(mo_second_phase_vector(ctx, (const Fr *)d_polys, d, n_polys, (const Fr *)d_g, d, W, &blob, d_v));
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, KZG_ERR_ALLOC, "host memory for the tables");
+    }
+    KZG_TRY(open_eval_fr_run(ctx, 0, d_v, log_d, 1, &pt, sfmt, d_y, out_pi ? d_q : nullptr));  // v(t) and the values of (v - v(t)) / (X - t)
+    if (y_out) KZG_HIP_CHECK(ctx, hipMemcpyAsync(y_out, d_y, 32, hipMemcpyDeviceToHost, st));
+    if (out_pi) return mo_commit_point(ctx, lagrange, d_q, d, sfmt, flags, out_pi, ofmt);  // the ONE MSM of the call
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (ctx->prof) prof_collect(ctx);
+    return KZG_OK;
+}
+
+extern "C" int kzg_multiopen_coeff_commit(kzg_ctx *ctx, const kzg_srs *srs, const void *coeffs, size_t n, size_t n_polys, const uint32_t *poly_idx,
+                                          const void *zs, size_t count, const void *r, int sfmt, int flags, void *ys_out, void *g_out, void *out_d,
+                                          int ofmt) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    const char *who = "kzg_multiopen_coeff_commit";
+    if (!srs) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL srs");
+    if (!point_format_bytes(ofmt)) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 output format");
+    if (n == 0) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": empty polynomials");
+    if (n - 1 > srs->n) return fail(ctx, KZG_ERR_SHAPE, "quotient longer than the SRS (reference: slice index panic)");
+    if (srs->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the SRS is resident on another GPU than this context's");
+    MoArgs a;
+    KZG_TRY(mo_args(ctx, who, n, n_polys, poly_idx, zs, count, r, nullptr, sfmt, &a));
+    if (count && !coeffs) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL coeffs");
+    if (!ys_out && !g_out && !out_d) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": no output");
+    MoPlan plan;
+    std::vector<uint32_t> vidx;
+    std::vector<Fr> cw;
+    MoBlob blob;
+    size_t o_vidx = 0, o_cw = 0, o_one = 0, o_zero = 0;
+    try {
+        mo_plan(a.z.data(), count, a.r, &plan);
+        vidx.resize(count);
+        cw.resize(count);
+        for (size_t s = 0; s < count; s++) {
+            vidx[s] = poly_idx ? poly_idx[plan.order[s]] : plan.order[s];
+            cw[s] = plan.rk[plan.order[s]];
+        }
+        const Fr one = Fr::one();
+        const uint32_t zero = 0;
+        o_vidx = blob.add(vidx.data(), count * 4);
+        o_cw = blob.add(cw.data(), count * 32);
+        o_one = blob.add(one.v, 32);
+        o_zero = blob.add(&zero, 4);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, KZG_ERR_ALLOC, "host memory for the plan");
+    }
+    const size_t U = plan.points(), glen = n - 1;
+    const bool in_dev = (flags & KZG_IN_DEVICE) != 0, g_dev = in_dev && g_out;
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->lanes[0].stream;
+    const size_t vec = align_up(n * 32, 256), horner = (n / 2048 + 4) * 64 + 65536;  // one poly_eval_run / quotient_linear_run
+    KZG_TRY(lane_reserve(ctx, 0, stage_bytes(n_polys * n * 32, flags) + 3 * vec + align_up(blob.h.size(), 256) + align_up(count * 32 + 32, 256) + 1024 + horner +
+                                     msm_workspace_bytes(srs, glen) + 65536));
+    std::vector<uint8_t> ys_sorted;  // (outlives the drain of the stream that fills it)
+    MoDrain drain{st};
+    const void *d_polys = nullptr;
+    if (count) KZG_TRY(stage_in(ctx, 0, coeffs, n_polys * n * 32, flags, &d_polys));  // host polynomials: once, whole
+    Fr *d_g = g_dev ? (Fr *)g_out : (Fr *)lane_alloc(ctx, 0, glen * 32 + 32);
+    uint8_t *d_tab = (uint8_t *)lane_alloc(ctx, 0, blob.h.size());
+    Fr *d_y = (Fr *)lane_alloc(ctx, 0, count * 32 + 32), *d_F = (Fr *)lane_alloc(ctx, 0, n * 32), *d_q = (Fr *)lane_alloc(ctx, 0, n * 32);
+    Fr *d_px = (Fr *)lane_alloc(ctx, 0, 256);
+    if (!d_g || !d_tab || !d_y || !d_F || !d_q || !d_px) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_tab, blob.h.data(), blob.h.size(), hipMemcpyHostToDevice, st));
+    if (glen) KZG_HIP_CHECK(ctx, hipMemsetAsync(d_g, 0, glen * 32, st));
+    const uint32_t *t_vidx = (const uint32_t *)(d_tab + o_vidx);
+    const Fr *t_cw = (const Fr *)(d_tab + o_cw);
+    const size_t mark = ctx->lanes[0].arena_used;
+    for (size_t u = 0; u < U; u++) {
+        const size_t a0 = plan.pstart[u], a1 = plan.pstart[u + 1];
+        for (size_t s = a0; s < a1 && ys_out; s++) {  // the values: Polynomial::eval per claim
+            KZG_TRY(poly_eval_run(ctx, 0, (const Fr *)d_polys + (size_t)vidx[s] * n, n, plan.z[u], d_y + s));
+            ctx->lanes[0].arena_used = mark;  // (stream order)
+        }
+        if (!glen || (!g_out && !out_d)) continue;
+        KZG_TRY(lincomb_run(ctx, st, (const Fr *)d_polys, n, t_vidx + a0, t_cw + a0, a1 - a0, false, d_F));
+        KZG_TRY(quotient_linear_run(ctx, 0, d_F, n, plan.z[u], d_q, d_px));  // (F_u - F_u(z_u)) / (X - z_u): n - 1 coefficients
+        ctx->lanes[0].arena_used = mark;
+        KZG_TRY(lincomb_run(ctx, st, d_q, glen, (const uint32_t *)(d_tab + o_zero), (const Fr *)(d_tab + o_one), 1, true, d_g));
+    }
+    if (ys_out && count) {
+        try {
+            ys_sorted.resize(count * 32);
+        } catch (const std::bad_alloc &) {
+            return fail(ctx, KZG_ERR_ALLOC, "host memory for the values");
+        }
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(ys_sorted.data(), d_y, count * 32, hipMemcpyDeviceToHost, st));
+    }
+    if (g_out && !g_dev && glen) KZG_HIP_CHECK(ctx, hipMemcpyAsync(g_out, d_g, glen * 32, hipMemcpyDeviceToHost, st));
+    if (out_d) {
+        KZG_TRY(mo_commit_point(ctx, srs, d_g, count ? glen : 0, sfmt, flags, out_d, ofmt));  // the ONE MSM of the call
+    } else {
+        KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        if (ctx->prof) prof_collect(ctx);
+    }
+    for (size_t s = 0; s < ys_sorted.size() / 32; s++) memcpy((uint8_t *)ys_out + 32 * (size_t)plan.order[s], ys_sorted.data() + 32 * s, 32);
+    return KZG_OK;
+}
+
+extern "C" int kzg_multiopen_coeff_finish(kzg_ctx *ctx, const kzg_srs *srs, const void *coeffs, size_t n, size_t n_polys, const uint32_t *poly_idx,
+                                          const void *zs, size_t count, const void *r, const void *t, const void *g_in, int sfmt, int flags, void *y_out,
+                                          void *out_pi, int ofmt) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    const char *who = "kzg_multiopen_coeff_finish";
+    if (!srs || !t) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL srs or t");
+    if (!point_format_bytes(ofmt)) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 output format");
+    if (n == 0) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": empty polynomials");
+    if (n - 1 > srs->n) return fail(ctx, KZG_ERR_SHAPE, "quotient longer than the SRS (reference: slice index panic)");
+    if (srs->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the SRS is resident on another GPU than this context's");
+    MoArgs a;
+    KZG_TRY(mo_args(ctx, who, n, n_polys, poly_idx, zs, count, r, t, sfmt, &a));
+    const size_t glen = n - 1;
+    if (count && (!coeffs || (!g_in && glen))) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL coeffs or g");
+    if (!y_out && !out_pi) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": no output");
+    std::vector<Fr> W;
+    KZG_TRY(mo_poly_weights_host(ctx, a, poly_idx, n_polys, &W));
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->lanes[0].stream;
+    const size_t vec = align_up(n * 32, 256), horner = (n / 2048 + 4) * 64 + 65536;
+    KZG_TRY(lane_reserve(ctx, 0, stage_bytes(n_polys * n * 32, flags) + stage_bytes(n * 32, flags) + 2 * vec + align_up(n_polys * 36 + 1024, 256) + 1024 + horner +
+                                     msm_workspace_bytes(srs, glen) + 65536));
+    MoBlob blob;  // (outlives the drain of the stream that reads it)
+    MoDrain drain{st};
+    if (!count) {
+        if (y_out) memset(y_out, 0, 32);
+        if (out_pi) return mo_commit_point(ctx, srs, nullptr, 0, sfmt, flags, out_pi, ofmt);
+        return KZG_OK;
+    }
+    const void *d_polys = nullptr, *d_g = nullptr;
+    KZG_TRY(stage_in(ctx, 0, coeffs, n_polys * n * 32, flags, &d_polys));  // host polynomials: once, whole
+    KZG_TRY(stage_in(ctx, 0, g_in, glen * 32, flags, &d_g));
+    Fr *d_v = (Fr *)lane_alloc(ctx, 0, n * 32), *d_q = (Fr *)lane_alloc(ctx, 0, n * 32), *d_y = (Fr *)lane_alloc(ctx, 0, 256);
+    if (!d_v || !d_q || !d_y) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    try {
+        KZG_TRY(mo_second_phase_vector(ctx, (const Fr *)d_polys, n, n_polys, (const Fr *)d_g, glen, W, &blob, d_v));
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, KZG_ERR_ALLOC, "host memory for the tables");
+    }
+    KZG_TRY(quotient_linear_run(ctx, 0, d_v, n, a.t, d_q, d_y));  // (v - v(t)) / (X - t) and v(t)
+    if (y_out) KZG_HIP_CHECK(ctx, hipMemcpyAsync(y_out, d_y, 32, hipMemcpyDeviceToHost, st));
+    if (out_pi) return mo_commit_point(ctx, srs, d_q, glen, sfmt, flags, out_pi, ofmt);  // the ONE MSM of the call
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (ctx->prof) prof_collect(ctx);
+    return KZG_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

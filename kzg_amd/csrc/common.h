@@ -142,6 +142,7 @@ struct kzg_ctx {
     int opt_ntt_vec_log = 2;           // NTT passes: 2^v adjacent columns / rows per LDS tile
     int opt_verify_cosets_chunk = 0;   // kzg_verify_cosets: at most this many cells per chunk (0 = the rule min(16384, 2^20 / l) alone)
     int opt_verify_eval_batch_chunk = 0;  // kzg_verify_eval_batch: at most this many openings per chunk (0 = 16384 alone)
+    int opt_multiopen_points_chunk = 0;   // kzg_multiopen_eval_commit: at most this many distinct points per chunk (0 = min(16, 2^22 / d) alone)
     int opt_host_pairing = 1;          // kzg_verify_cosets_batch, kzg_verify_eval_batch: the one pairing check runs on the calling thread (vcb_finish.h); 0 = in a one-thread kernel
     int opt_fk20_cosets_combine = 0;   // the coset combination of kzg_witness_cosets_*: 0 = Straus (shared doublings), 1 = mul256 per term
     int opt_ntt_kernel = KZG_NTT_KERNEL_DEFAULT;  // 0: three-phase passes (k_ntt_pass1/2); 1: load/store fused into the first/last stage pair (k_ntt_tile); 2: 1 + two butterflies per thread
@@ -452,9 +453,29 @@ size_t open_eval_fr_workspace_bytes(size_t d, size_t B, size_t nz);        // ..
 // y (d_y + b) and, unless d_q is null, the quotient (d_q + b d) of B <= OE_MAX_CHUNK polynomials (d_evals + b d) at pts[b], on the lane's stream
 int open_eval_fr_run(kzg_ctx *ctx, int lane, const Fr *d_evals, uint32_t log_d, size_t B, const OpenPoint *pts, int sfmt, Fr *d_y, Fr *d_q);
 
+// the evaluation stage with the polynomial of a claim named by an index (kzg_multiopen_eval_commit): the power table of the domain
+// (open_powtab_bytes(d) bytes at d_tab), the inverses d_inv[u d + i] = 1 / (w^i - z_u) of nz <= OE_MAX_CHUNK off-domain points (d_den:
+// scratch of the same nz x d scalars), and y[b] = p_{vidx[b]}(z_{pu[b]}) for B claims from them; every table is device memory
+size_t open_powtab_bytes(size_t d);
+int open_powtab_run(kzg_ctx *ctx, hipStream_t st, uint32_t log_d, Fr *d_tab);
+int open_inverses_run(kzg_ctx *ctx, hipStream_t st, uint32_t log_d, const Fr *d_tab, const Fr *z_mont, int nz, Fr *d_den, Fr *d_inv);
+int open_eval_values_idx_run(kzg_ctx *ctx, hipStream_t st, const Fr *d_evals, uint32_t log_d, const Fr *d_inv, const uint32_t *d_vidx,
+                             const uint32_t *d_pu, const Fr *d_z, const Fr *d_c, size_t B, Fr *d_partial, Fr *d_y);
+
 // fold.hip: d_out[g d + j] = sum_{i < t} gamma_g^i d_v[g gstride + i d + j], g < groups (gammas Montgomery, on the device); with carry
 // the sum starts from d_out[g d + j] gamma_g^t: pieces of a group folded from the last one down
 int fold_run(kzg_ctx *ctx, hipStream_t st, const Fr *d_v, size_t d, size_t t, size_t gstride, size_t groups, const Fr *d_gammas_mont,
              bool carry, Fr *d_out);
+
+// multiopen.hip: d_out[j] (+)= sum_{k < count} d_weight[k] d_v[d_idx[k] d + j], j < d (weights Montgomery; the output has the inputs' form)
+int lincomb_run(kzg_ctx *ctx, hipStream_t st, const Fr *d_v, size_t d, const uint32_t *d_idx, const Fr *d_weight, size_t count, bool carry,
+                Fr *d_out);
+// d_y[s] = d_v[d_idx[s] d + d_at[s]] for s < count (the values at points of the domain, as they are stored)
+int multiopen_gather_run(kzg_ctx *ctx, hipStream_t st, const Fr *d_v, size_t d, const uint32_t *d_idx, const uint32_t *d_at, size_t count, Fr *d_y);
+// One chunk of nz <= OE_MAX_CHUNK distinct off-domain points: d_Y[u] = sum_{k in u} d_w[k] d_y[k] on the device, then
+// d_g[j] += sum_u (sum_{k in u} d_w[k] d_v[d_idx[k] d + j] - d_Y[u]) d_inv[u d + j]; the claims of point u are [d_pstart[u], d_pstart[u + 1])
+int multiopen_accum_run(kzg_ctx *ctx, hipStream_t st, const Fr *d_v, size_t d, const uint32_t *d_idx, const Fr *d_w, const uint32_t *d_pstart,
+                        int nz, const Fr *d_y, Fr *d_Y, const Fr *d_inv, Fr *d_g);
+
 
 }  // namespace kzg

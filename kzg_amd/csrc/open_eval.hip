@@ -101,6 +101,31 @@ __global__ __launch_bounds__(256) void k_open_quotient(const Fr *evals, size_t d
     q[(size_t)b * d + i] = mul(sub(oe_load(evals + (size_t)b * d + i), y[b]), inv[(size_t)u * d + i]);
 }
 
+// The two evaluation kernels with an indirection (kzg_multiopen_eval_commit): claim b of the launch names its polynomial, vidx[b], and
+// its point of the chunk, pu[b]; the tables and the points' constants are device memory, read uniformly per block.
+__global__ __launch_bounds__(256) void k_open_eval_partials_idx(const Fr *evals, size_t d, const Fr *inv, const uint32_t *vidx, const uint32_t *pu,
+                                                                const Fr *z, Fr *partial) {
+    __shared__ Fr sh[512];
+    const size_t b = blockIdx.y, u = pu[b];
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Fr f = Fr::zero(), g = Fr::zero();
+    if (i < d) {
+        f = oe_load(evals + (size_t)vidx[b] * d + i);
+        g = mul(f, inv[u * d + i]);
+    }
+    block_sum2(f, g, sh);
+    if (threadIdx.x == 0) partial[b * gridDim.x + blockIdx.x] = add(f, mul(z[u], g));
+}
+
+__global__ __launch_bounds__(256) void k_open_eval_finish_idx(const Fr *partial, uint32_t nblk, const uint32_t *pu, const Fr *c, Fr *y) {
+    __shared__ Fr sh[512];
+    const size_t b = blockIdx.x;
+    Fr acc = Fr::zero(), none = Fr::zero();
+    for (uint32_t k = threadIdx.x; k < nblk; k += blockDim.x) acc = add(acc, partial[b * nblk + k]);
+    block_sum2(acc, none, sh);
+    if (threadIdx.x == 0) y[b] = neg(mul(c[pu[b]], acc));
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -192,6 +217,42 @@ int open_eval_fr_run(kzg_ctx *ctx, int lane, const Fr *d_evals, uint32_t log_d, 
     }
     ctx->lanes[lane].arena_used = mark;
     return rc;
+}
+
+// ---- the stages above for a caller with its own tables (kzg_multiopen_eval_commit) ----
+size_t open_powtab_bytes(size_t d) { return (OE_LO + std::max<size_t>(1, d >> OE_LO_LOG)) * 32; }
+
+int open_powtab_run(kzg_ctx *ctx, hipStream_t st, uint32_t log_d, Fr *d_tab) {
+    const uint32_t hi_n = (uint32_t)std::max<size_t>(1, ((size_t)1 << log_d) >> OE_LO_LOG);
+    const Fr w = host_omega(log_d);
+    KZG_LAUNCH(ctx, st, "k_open_powtab", k_open_powtab, (OE_LO + hi_n + 255) / 256, 256, 0, w, pow_u64(w, (uint64_t)OE_LO), hi_n, d_tab);
+    return KZG_OK;
+}
+
+int open_inverses_run(kzg_ctx *ctx, hipStream_t st, uint32_t log_d, const Fr *d_tab, const Fr *z_mont, int nz, Fr *d_den, Fr *d_inv) {
+    if (nz <= 0) return KZG_OK;
+    if (nz > OE_MAX_CHUNK) return fail(ctx, KZG_ERR_INTERNAL, "open_eval chunk");
+    const size_t d = (size_t)1 << log_d;
+    OpenZs zs;
+    for (int u = 0; u < OE_MAX_CHUNK; u++) {
+        zs.z[u] = u < nz ? z_mont[u] : Fr::zero();
+        zs.c[u] = Fr::zero();  // (k_open_denoms reads the points alone)
+    }
+    KZG_LAUNCH(ctx, st, "k_open_denoms", k_open_denoms, (unsigned)((d + 255) / 256), 256, 0, d_tab, d, zs, nz, d_den);
+    return batch_inverse(ctx, st, d_den, d_inv, (size_t)nz * d);
+}
+
+int open_eval_values_idx_run(kzg_ctx *ctx, hipStream_t st, const Fr *d_evals, uint32_t log_d, const Fr *d_inv, const uint32_t *d_vidx,
+                             const uint32_t *d_pu, const Fr *d_z, const Fr *d_c, size_t B, Fr *d_partial, Fr *d_y) {
+    const size_t d = (size_t)1 << log_d;
+    const uint32_t nblk = (uint32_t)((d + 255) / 256);
+    for (size_t b0 = 0; b0 < B; b0 += 65535) {  // (gridDim.y); d_partial: min(B, 65535) x nblk scalars
+        const size_t n = std::min<size_t>(65535, B - b0);
+        KZG_LAUNCH(ctx, st, "k_open_eval_partials_idx", k_open_eval_partials_idx, dim3(nblk, (unsigned)n), 256, 0, d_evals, d, d_inv, d_vidx + b0,
+                   d_pu + b0, d_z, d_partial);
+        KZG_LAUNCH(ctx, st, "k_open_eval_finish_idx", k_open_eval_finish_idx, (unsigned)n, 256, 0, (const Fr *)d_partial, nblk, d_pu + b0, d_c, d_y + b0);
+    }
+    return KZG_OK;
 }
 
 }  // namespace kzg

@@ -421,6 +421,9 @@ extern "C" int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value) 
     } else if (k == "verify_eval_batch_chunk") {
         if (value < 0 || value > 16384) return fail(ctx, KZG_ERR_SHAPE, "verify_eval_batch_chunk must be 0 (16384 openings) or 1..16384 openings");
         ctx->opt_verify_eval_batch_chunk = (int)value;
+    } else if (k == "multiopen_points_chunk") {
+        if (value < 0 || value > 16) return fail(ctx, KZG_ERR_SHAPE, "multiopen_points_chunk must be 0 (min(16, 2^22 / d) points) or 1..16 points");
+        ctx->opt_multiopen_points_chunk = (int)value;
     } else if (k == "ntt_vec_log") {
         if (value < 0 || value > 2) return fail(ctx, KZG_ERR_SHAPE, "ntt_vec_log must be 0..2");
         ctx->opt_ntt_vec_log = (int)value;

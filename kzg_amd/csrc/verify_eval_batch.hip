@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "multiopen_plan.h"
 #include "vcb_shared.h"
 
 namespace kzg {
@@ -357,11 +358,175 @@ int vf_run(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *zs
     KZG_TRY(vb_reduce(ctx, st, bk, (uint32_t)slots, sums));
     return vcb_conclude(ctx, lane, sums, hs->pts, hs->lines, hs->h_pts, hs->h_lines, bad, d_ok, d_parts, nullptr, ok);
 }
+// kzg_verify_multiopen: N claims at any points answered by the two elements D and pi (kzg_multiopen_*_commit / _finish; DESIGN.md section
+// 3.4d).  With w_k = r^k / (t - z_k): E = sum_m W_m C_m, W_m = sum_{m(k) = m} w_k, g2 = sum_k w_k y_k, and the proof is a plain opening of
+// E - D at (t, g2) with the witness pi.  So this is vf_run with other weights: the ONE witness against 1 and t (k_veb_scalars), D as
+// one more pair of the third set against -1, then the values and commitments against w_k, formed on the host per chunk (one inversion
+// each, multiopen_plan.h): the fold gives g2, k_vcb_cweights or the third set gives E.  The end is veb_run's.
+int vm_run(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *zs, const void *ys, int sfmt, const void *commitments,
+           size_t n_commitments, const uint32_t *commitment_idx, size_t count, const void *r, const void *t, const void *d_point, const void *pi,
+           int pfmt, int *ok) {
+    const char *who = "kzg_verify_multiopen";
+    // ---- shape: everything is decided before memory is touched or a kernel launched ----
+    if (!ctx) return KZG_ERR_SHAPE;
+    if (!gs || !hs) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL SRS");
+    if (sfmt != KZG_FR_MONT_LE_32 && sfmt != KZG_FR_CANONICAL_LE_32) return fail(ctx, KZG_ERR_SHAPE, "unknown scalar format");
+    const size_t psz = point_format_bytes(pfmt);
+    if (!psz || pfmt == KZG_G1_JACOBIAN_MONT_144) return fail(ctx, KZG_ERR_SHAPE, "commitments / D / pi are affine (G1Affine)");
+    if (gs->n < 1 || hs->n < 2) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + " needs gs[0], hs[0], hs[1]");
+    if (gs->device != ctx->device || hs->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the SRS is resident on another GPU than this context's");
+    if (!count) {
+        if (ok) *ok = 1;
+        return KZG_OK;
+    }
+    if (!zs || !ys || !commitments || !r || !t || !d_point || !pi || !ok) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL argument");
+    if (count > (SIZE_MAX >> 9) || n_commitments > (SIZE_MAX >> 9)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": count too large");
+    Fr rm, tm;
+    KZG_TRY(load_challenge(ctx, who, r, sfmt, &rm));
+    memcpy(tm.v, t, 32);
+    if (!is_canonical(tm)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": the challenge t >= modulus");
+    if (sfmt != KZG_FR_MONT_LE_32) tm = to_mont(tm);
+    const bool indexed = commitment_idx != nullptr;
+    if (!indexed && n_commitments != count) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": without indices there is one commitment per claim");
+    size_t chunk = VEB_CHUNK;
+    if (ctx->opt_verify_eval_batch_chunk > 0) chunk = std::min(chunk, (size_t)ctx->opt_verify_eval_batch_chunk);
+    const size_t B0 = std::min(chunk, count), BP = indexed ? std::min(chunk, std::max(count, n_commitments)) : B0;
+    std::vector<uint32_t> cnt, which, start, order;  // the counting sort of a chunk's claims by commitment
+    std::vector<Fr> zm, w;                           // the points (Montgomery) | a chunk's weights
+    try {  // (no exception may leave through the C ABI)
+        zm.resize(count);
+        w.resize(B0);
+        if (indexed) {
+            cnt.assign(n_commitments, 0);
+            which.resize(B0);
+            start.resize(B0 + 1);
+            order.resize(B0);
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, KZG_ERR_ALLOC, std::string(who) + ": host memory for the weights and indices");
+    }
+    for (size_t k = 0; k < count; k++) {
+        Fr x;
+        memcpy(x.v, (const uint8_t *)zs + 32 * k, 32);
+        if (!is_canonical(x)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": a point z >= modulus");
+        zm[k] = sfmt == KZG_FR_MONT_LE_32 ? x : to_mont(x);
+        if (zm[k] == tm) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": t equals a point z_k (draw another t)");
+        if (indexed && commitment_idx[k] >= n_commitments) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": commitment index >= n_commitments");
+    }
+    const Fr one = Fr::one(), minus_one = from_mont(neg(Fr::one()));  // the witness's weight (Montgomery) | D's scalar (canonical)
+
+    kzg::Lease ls;
+    KZG_TRY(lease_lane(ctx, &ls));
+    const int lane = ls.lane;
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->lanes[lane].stream;
+    const int is_mont = sfmt == KZG_FR_MONT_LE_32 ? 1 : 0;
+    const size_t fold_blocks = (B0 + VCB_FOLD_CELLS - 1) / VCB_FOLD_CELLS, bucket_bytes = 3 * (size_t)VCB_G * VCB_SET * sizeof(G1Xyzz);
+    const size_t c_bytes = indexed ? std::max<size_t>(n_commitments, 1) * 32 : 32;
+    KZG_TRY(lane_reserve(ctx, lane, bucket_bytes + sizeof(VcbSums) + c_bytes + BP * (psz + sizeof(G1Xyzz)) + B0 * (3 * 4 + 5 * 32) + (fold_blocks + 4) * 32 + 65536));
+    struct Drain {  // nothing of the call is in flight once its host-side buffers go out of scope
+        hipStream_t st;
+        ~Drain() { hipStreamSynchronize(st); }
+    } drain{st};
+    int *bad = (int *)lane_alloc(ctx, lane, 256);
+    uint8_t *d_ok = (uint8_t *)lane_alloc(ctx, lane, 256);
+    G1Affine *d_parts = (G1Affine *)lane_alloc(ctx, lane, 4 * sizeof(G1Affine));
+    G1Xyzz *bk = (G1Xyzz *)lane_alloc(ctx, lane, bucket_bytes);
+    VcbSums *sums = (VcbSums *)lane_alloc(ctx, lane, sizeof(VcbSums));
+    Fr *d_yagg = (Fr *)lane_alloc(ctx, lane, 3 * 32), *d_part = (Fr *)lane_alloc(ctx, lane, fold_blocks * 32);  // g2 (sfmt), g2, -g2
+    Fr *d_c = (Fr *)lane_alloc(ctx, lane, c_bytes);
+    uint32_t *d_which = (uint32_t *)lane_alloc(ctx, lane, B0 * 4), *d_start = (uint32_t *)lane_alloc(ctx, lane, (B0 + 1) * 4);
+    uint32_t *d_order = (uint32_t *)lane_alloc(ctx, lane, B0 * 4);
+    Fr *d_rho = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_s1 = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_s2 = (Fr *)lane_alloc(ctx, lane, B0 * 32);
+    Fr *d_x = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_y = (Fr *)lane_alloc(ctx, lane, B0 * 32);
+    uint8_t *raw = (uint8_t *)lane_alloc(ctx, lane, BP * psz);
+    G1Xyzz *W = (G1Xyzz *)lane_alloc(ctx, lane, BP * sizeof(G1Xyzz));
+    if (!bad || !d_ok || !d_parts || !bk || !sums || !d_yagg || !d_part || !d_c || !d_which || !d_start || !d_order || !d_rho || !d_s1 || !d_s2 ||
+        !d_x || !d_y || !raw || !W)
+        return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    G1Xyzz *bk1 = bk, *bk2 = bk + (size_t)VCB_G * VCB_SET, *bk3 = bk + 2 * (size_t)VCB_G * VCB_SET;
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(bad, 0, sizeof(int), st));
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(bk, 0, bucket_bytes, st));         // zz = 0: the identity
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(sums, 0, sizeof(VcbSums), st));    // the Ragg slot stays the identity
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(d_yagg, 0, 3 * 32, st));
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(d_c, 0, c_bytes, st));
+    size_t slots = 1;  // slice slots any chunk has used (gs[0], pi and D take slot 0)
+    // ---- the witness: P1 = pi, P2 = t pi ----
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_rho, one.v, 32, hipMemcpyHostToDevice, st));
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_x, t, 32, hipMemcpyHostToDevice, st));
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, pi, psz, hipMemcpyHostToDevice, st));
+    KZG_TRY(decode_points(ctx, st, raw, 1, pfmt, W, bad, untrusted_level(ctx)));
+    KZG_LAUNCH(ctx, st, "k_veb_scalars", k_veb_scalars, 1, 256, 0, (const Fr *)d_rho, (const Fr *)d_x, (size_t)1, is_mont, d_s1, d_s2);
+    KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_s1, d_s2, 1, bk1, bk2, 2));
+    // ---- D: one more commitment, of weight -1 ----
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_s1, minus_one.v, 32, hipMemcpyHostToDevice, st));
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, d_point, psz, hipMemcpyHostToDevice, st));
+    KZG_TRY(decode_points(ctx, st, raw, 1, pfmt, W, bad, untrusted_level(ctx)));
+    KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_s1, d_s1, 1, bk3, bk3, 1));
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    // ---- values and commitments against w_k = r^k / (t - z_k); r^k walks across the chunk boundaries ----
+    Fr rk = Fr::one();
+    for (size_t k0 = 0; k0 < count; k0 += chunk) {
+        const size_t B = std::min(chunk, count - k0);
+        if (!mo_weights(zm.data() + k0, B, rm, tm, &rk, w.data())) return fail(ctx, KZG_ERR_INTERNAL, std::string(who) + ": t equals a point");
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_rho, w.data(), B * 32, hipMemcpyHostToDevice, st));
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_y, (const uint8_t *)ys + k0 * 32, B * 32, hipMemcpyHostToDevice, st));
+        KZG_TRY(vcb_fold(ctx, st, d_y, d_rho, B, 0, d_part, d_yagg));
+        if (indexed) {  // the chunk's claims listed per commitment, commitments in the order of their first claim
+            size_t lists = 0;
+            const uint32_t *cm = commitment_idx + k0;
+            for (size_t k = 0; k < B; k++)
+                if (!cnt[cm[k]]++) which[lists++] = cm[k];
+            uint32_t at = 0;
+            for (size_t g = 0; g < lists; g++) {
+                start[g] = at;
+                at += cnt[which[g]];
+                cnt[which[g]] = start[g];
+            }
+            start[lists] = at;
+            for (size_t k = 0; k < B; k++) order[cnt[cm[k]]++] = (uint32_t)k;
+            for (size_t g = 0; g < lists; g++) cnt[which[g]] = 0;
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_which, which.data(), lists * 4, hipMemcpyHostToDevice, st));
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_start, start.data(), (lists + 1) * 4, hipMemcpyHostToDevice, st));
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_order, order.data(), B * 4, hipMemcpyHostToDevice, st));
+            KZG_TRY(vcb_cweights(ctx, st, d_rho, d_which, d_start, d_order, lists, d_c));
+        } else {  // W_k = w_k: the chunk's commitments into the third set at once
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)commitments + k0 * psz, B * psz, hipMemcpyHostToDevice, st));
+            KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
+            KZG_TRY(vcb_canon(ctx, st, d_rho, B, 1, d_s1));
+            KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_s1, d_s1, B, bk3, bk3, 1));
+        }
+        slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
+        // the host lists and the chunk's device buffers are free again
+        KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    }
+    if (indexed) {  // E: the commitments against the canonical W, in chunks like the claims
+        for (size_t m0 = 0; m0 < n_commitments; m0 += BP) {
+            const size_t B = std::min(BP, n_commitments - m0);
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)commitments + m0 * psz, B * psz, hipMemcpyHostToDevice, st));
+            KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
+            KZG_TRY(vcb_canon(ctx, st, d_c + m0, B, 1, d_c + m0));
+            KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_c + m0, d_c + m0, B, bk3, bk3, 1));
+            slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
+        }
+    }
+    // - [g2] gs[0]: one more pair of the third set (row 0 of the SRS table is gs itself)
+    KZG_LAUNCH(ctx, st, "k_veb_yagg", k_veb_yagg, 1, 1, 0, (const Fr *)d_yagg, is_mont, d_yagg + 1, d_yagg + 2);
+    KZG_TRY(vb_accumulate(ctx, st, (const G1Affine *)gs->table, d_yagg + 2, d_yagg + 2, 1, bk3, bk3, 1));
+    KZG_TRY(vb_reduce(ctx, st, bk, (uint32_t)slots, sums));
+    return vcb_conclude(ctx, lane, sums, hs->pts, hs->lines, hs->h_pts, hs->h_lines, bad, d_ok, d_parts, nullptr, ok);
+}
 }  // namespace
 
 }  // namespace kzg
 
 using namespace kzg;
+
+extern "C" int kzg_verify_multiopen(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *zs, const void *ys, int sfmt,
+                                    const void *commitments, size_t n_commitments, const uint32_t *commitment_idx, size_t count, const void *r,
+                                    const void *t, const void *d_point, const void *pi, int pfmt, int *ok) {
+    return vm_run(ctx, gs, hs, zs, ys, sfmt, commitments, n_commitments, commitment_idx, count, r, t, d_point, pi, pfmt, ok);
+}
 
 extern "C" int kzg_verify_fold(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *zs, const void *ys, int sfmt,
                                const void *commitments, size_t n_commitments, const uint32_t *commitment_idx, const void *witnesses, int pfmt,
