@@ -126,6 +126,27 @@ KZG_HD G1Xyzz30 g1_dbl30(const G1Xyzz30 &p) {
     return r;
 }
 
+// the same doubling for a table point (ZZ = ZZZ = 1), negated first if asked: ZZ3 = V and ZZZ3 = W as they are -- two products
+// fewer, and no limbs of one30() alive next to the doubling's intermediates.  |y| < 0.51: |U| < 1.1, V and W products below 0.6.
+// The identity entry (y = 0) gives V = 0: infinity.
+KZG_HD G1Xyzz30 g1_dbl_affine30(const G1Affine30 &a, bool negate) {
+    Fq30 y = cneg30(a.y, negate);
+    Fq30 U = times2_30(y);
+    Fq30 V = sqr30(U);
+    if (is_zero30(V)) return G1Xyzz30::infinity();
+    Fq30 W = mul30(U, V);
+    Fq30 S = mul30(a.x, V);
+    Fq30 Mm = times3_30(sqr30(a.x));
+    G1Xyzz30 r;
+    r.inf = 0;
+    r.pad[0] = r.pad[1] = r.pad[2] = 0;
+    r.x = sub30(sqr30(Mm), times2_30(S));
+    r.y = sub30(mul30(Mm, sub30(S, r.x)), mul30(W, y));
+    r.zz = V;
+    r.zzz = W;
+    return r;
+}
+
 // add-2008-s: 12M + 2S.  In: |X|, |Y| < 8 on both sides.  Out: |X| < 2.2, |Y| < 1.1.
 KZG_HD G1Xyzz30 g1_add30(const G1Xyzz30 &p, const G1Xyzz30 &q) {
     if (q.inf) return p;
@@ -201,6 +222,87 @@ KZG_HD G1Xyzz30 g1_normalize30(G1Xyzz30 p) {
     p.zz = normalize30(p.zz);
     p.zzz = normalize30(p.zzz);
     return p;
+}
+
+// ---- sign-tracked accumulator (k_accum_affine's loop) ----------------------------------------------------------------------
+// The accumulator is kept as (X, Yt, ZZ, ZZZ) plus a per-lane sign sigma (+1 or -1, one register) with true Y = sigma * Yt.  For
+// a table point (x2, y2) that enters with sign s, put tau = -s * sigma.  Then
+//     true R = s y2 ZZZ1 - sigma Yt1 = s R',   R' = y2 ZZZ1 + tau Yt1          (mul30_sgn: the multiplier of the merged term)
+//     P, PP, PPP, Q, ZZ3, ZZZ3 and X3 = R'^2 - PPP - 2Q carry no sign
+//     true Y3 = R (Q - X3) - Y1 PPP = s (R' (Q - X3) + (tau Yt1) PPP),         so Yt3 = that bracket and sigma3 = s:
+// neither the sign of the table point nor the accumulator's is ever applied to a coordinate; the one sign operation left is
+// tau * Yt1 for the fused product (sgn30, where neg30 stands in the plain form).  Bounds are those of the plain form: every value
+// has the magnitude it has there.  A restart takes Yt = y2, sigma = s as they are.
+KZG_HD int32_t g1_sign30(bool negate) { return negate ? -1 : 1; }
+KZG_HD int32_t g1_tau30(int32_t sigma, bool negate) { return negate ? sigma : -sigma; }
+
+// the accumulator restarted from a VALIDATED table entry (is_inf_table), y2 unsigned: sigma = s
+KZG_HD G1Xyzz30 g1_from_table30s(const G1Affine30 &a, bool negate, int32_t &sigma) {
+    G1Xyzz30 p;
+    p.inf = a.is_inf_table() ? 1u : 0u;
+    p.pad[0] = p.pad[1] = p.pad[2] = 0;
+    p.x = a.x;
+    p.y = a.y;
+    p.zz = one30();
+    p.zzz = one30();
+    sigma = g1_sign30(negate);
+    return p;
+}
+
+KZG_HD Madd30Mid g1_madd30s_phase1(const G1Xyzz30 &p, const G1Affine30 &a, int32_t tau) {
+    Madd30Mid m;
+    m.P = mul30_sub(a.x, p.zz, p.x);
+    m.R = mul30_sgn(a.y, p.zzz, p.y, tau);  // R'
+    return m;
+}
+
+// sigma: the accumulator's sign, updated.  tau = g1_tau30(sigma before, negate), the value phase 1 was given.
+template <class Reload>
+KZG_HD G1Xyzz30 g1_madd30s_phase2(const G1Xyzz30 &p, const Madd30Mid &m, int32_t tau, bool negate, int32_t &sigma, Reload reload) {
+    const Fq30 &Pp = m.P, &R = m.R;
+    Fq30 PP = sqr30(Pp);
+    if (is_zero30(PP)) {
+        // same x.  R' = 0 iff R = 0 (they differ by the sign s): the same point, doubled with the sign applied to the reloaded point as
+        // in the plain form (balanced digits, true Y: sigma = +1); otherwise its inverse
+        sigma = 1;
+        if (!is_zero30(sqr30(R))) return G1Xyzz30::infinity();
+        return g1_dbl_affine30(reload(), negate);
+    }
+    Fq30 PPP = mul30(Pp, PP);
+    Fq30 Q = mul30u(p.x, PP);
+    G1Xyzz30 r;
+    r.inf = 0;
+    r.pad[0] = r.pad[1] = r.pad[2] = 0;
+    r.zz = mul30u(p.zz, PP);
+    r.zzz = mul30u(p.zzz, PPP);
+    r.x = sqr30_sub2u(R, PPP, Q);
+    r.y = muladd30(R, sub30(Q, r.x), sgn30(p.y, tau), PPP);
+    sigma = g1_sign30(negate);
+    return r;
+}
+
+// A sign-tracked accumulator as it is written to a partial-sum list: the coordinates raw (X, ZZ, ZZZ possibly with unsigned digits),
+// the sign in the first pad word (1 = true Y is -Yt).  g1_partial_load30 is what every reader of such a list applies to an element:
+// balanced digits and the true Y, the form g1_add30 and every later kernel expects.  It leaves an element that is already in that
+// form (pad word 0) as it is.
+KZG_HD G1Xyzz30 g1_partial_store30(G1Xyzz30 p, int32_t sigma) {
+    p.pad[0] = (uint32_t)sigma >> 31;
+    return p;
+}
+KZG_HD G1Xyzz30 g1_partial_load30(G1Xyzz30 p) {
+    p = g1_normalize30(p);
+    p.y = cneg30(p.y, p.pad[0] != 0);
+    p.pad[0] = 0;
+    return p;
+}
+
+// acc += (negate ? -a : a) on a sign-tracked accumulator (the host-side reference of the kernel's loop body)
+KZG_HD G1Xyzz30 g1_madd30s(const G1Xyzz30 &p, int32_t &sigma, const G1Affine30 &a, bool negate) {
+    if (a.is_inf_table()) return p;
+    if (p.inf) return g1_from_table30s(a, negate, sigma);
+    const int32_t tau = g1_tau30(sigma, negate);
+    Madd30Mid m = g1_madd30s_phase1(p, a, tau);
+    return g1_madd30s_phase2(p, m, tau, negate, sigma, [&]() { return a; });
 }
 
 KZG_HD G1Xyzz30 g1_madd30(const G1Xyzz30 &p, const G1Affine30 &a, bool negate) {

@@ -128,6 +128,41 @@ KZG_HD Fq30 mul30_sub_inline(const Fq30 &a, const Fq30 &b, const Fq30 &c) {
     return r;
 }
 
+// a*b/R30 + t*c for a per-lane sign t (+1 or -1): mul30_sub with the merged term's multiplier in a register instead of the
+// constant -1 -- the same 13 multiply-adds, the same instruction count.  The caller folds the sign of a table point and the
+// sign carried next to a sign-tracked accumulator (curve30.h) into t, so neither is ever applied to a coordinate.
+// |result| <= |a*b|/R30 + q/2 + |c|.  c: any limbs below 2^31 in magnitude, as for mul30_sub (|t| = 1 leaves the products
+// c.v[j] * t where c.v[j] * -1 was).
+KZG_HD Fq30 mul30_sgn_inline(const Fq30 &a, const Fq30 &b, const Fq30 &c, int32_t t) {
+    int32_t m[F30_N];
+    Fq30 r;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < F30_N; k++) {
+#pragma unroll
+        for (int i = 0; i <= k; i++) acc = mac30(acc, a.v[i], b.v[k - i]);
+#pragma unroll
+        for (int i = 0; i < k; i++) acc = mac30(acc, m[i], Fq30Consts::mod(k - i));
+        m[k] = sext30((uint32_t)acc * Fq30Consts::INV);
+        acc = mac30(acc, m[k], Fq30Consts::mod(0));
+        acc = sar30(acc);
+    }
+#pragma unroll
+    for (int k = F30_N; k < 2 * F30_N - 1; k++) {
+#pragma unroll
+        for (int i = k - F30_N + 1; i < F30_N; i++) {
+            acc = mac30(acc, a.v[i], b.v[k - i]);
+            acc = mac30(acc, m[i], Fq30Consts::mod(k - i));
+        }
+        acc = mac30(acc, c.v[k - F30_N], t);
+        r.v[k - F30_N] = sext30((uint32_t)acc);
+        acc = sar30(acc + (uint64_t)F30_HALF);
+    }
+    acc = mac30(acc, c.v[F30_N - 1], t);
+    r.v[F30_N - 1] = (int32_t)acc;
+    return r;
+}
+
 // (a*b + c*d)/R30 with ONE reduction.  A column of the fused scan holds up to 39 products of magnitude 2^58, which
 // would overflow the signed accumulator; in the five columns with more than 30 products the multiple of 2^30
 // accumulated so far is set aside before the c*d products go in and rejoins the carry afterwards.
@@ -330,6 +365,13 @@ KZG_HD Fq30 mul30_sub(const Fq30 &a, const Fq30 &b, const Fq30 &c) {
     return mul30_sub_inline(a, b, c);
 #endif
 }
+KZG_HD Fq30 mul30_sgn(const Fq30 &a, const Fq30 &b, const Fq30 &c, int32_t t) {
+#if defined(KZG_HAVE_MULADD30_ASM) && !defined(KZG_NO_MERGED_SUB)
+    return mul30_sgn_asm(a, b, c, t);
+#else
+    return mul30_sgn_inline(a, b, c, t);
+#endif
+}
 KZG_HD Fq30 sqr30_sub2(const Fq30 &a, const Fq30 &c, const Fq30 &e) {
 #if defined(KZG_NO_MERGED_SUB)
     return sub30(sqr30(a), add2x30(c, e));
@@ -384,6 +426,14 @@ KZG_HD Fq30 neg30(const Fq30 &a) {
     return r;
 }
 
+// t * a for a per-lane sign t (+1 or -1), limb-wise (one v_mul_lo_u32 per limb): |limb| <= 2^29 is kept, as for neg30
+KZG_HD Fq30 sgn30(const Fq30 &a, int32_t t) {
+    Fq30 r;
+#pragma unroll
+    for (int i = 0; i < F30_N; i++) r.v[i] = a.v[i] * t;
+    return r;
+}
+
 // negate ? -a : a, branch-free
 KZG_HD Fq30 cneg30(const Fq30 &a, bool negate) {
     const int32_t s = negate ? -1 : 0;
@@ -398,6 +448,14 @@ KZG_HD Fq30 sub30(const Fq30 &a, const Fq30 &b) {
     Fq30 r;
 #pragma unroll
     for (int i = 0; i < F30_N; i++) r.v[i] = a.v[i] - b.v[i];
+    return normalize30(r);
+}
+
+// a + b, normalised.  Operand limbs |.| <= 2^29.
+KZG_HD Fq30 add30(const Fq30 &a, const Fq30 &b) {
+    Fq30 r;
+#pragma unroll
+    for (int i = 0; i < F30_N; i++) r.v[i] = a.v[i] + b.v[i];
     return normalize30(r);
 }
 

@@ -509,7 +509,12 @@ __device__ __forceinline__ G1Affine30 load_entry_point30(const uint4 *table30, u
 // resident 30-bit table (next point prefetched under the add), and writes one partial per bucket it
 // touches.  Every thread has the same amount of work,
 // so the kernel ends without a straggler round.
-__global__ __launch_bounds__(256, KZG_ACCUM_WAVES) void k_accum_affine(const uint32_t *entries, const uint32_t *bucket_start,
+// Exactly KZG_ACCUM_WAVES waves per SIMD, no more: the kernel needs fewer registers than a (KZG_ACCUM_WAVES + 1)-th wave would leave it,
+// and the batched pipeline counts on the register file this kernel does NOT take -- the sort and tail kernels of the neighbouring MSMs
+// run beside two accumulation waves, not behind three (measured: 324 against 435 commitments/s with three resident).
+// (The bound is spelt as the waves-per-SIMD attribute with both ends given: the second argument of __launch_bounds__ sets the lower end
+// only, and overrides the attribute.)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KZG_ACCUM_WAVES, KZG_ACCUM_WAVES))) void k_accum_affine(const uint32_t *entries, const uint32_t *bucket_start,
                                                       const uint32_t *s1, int B, const uint4 *table30,
                                                       MsmPoint *out, const MsmState *st) {
     const uint32_t E = st->E, M = st->M;
@@ -526,12 +531,17 @@ __global__ __launch_bounds__(256, KZG_ACCUM_WAVES) void k_accum_affine(const uin
     }
     uint32_t b = bl;
     uint32_t bend = bucket_start[b + 1];
+    // the end of the bucket after this one is fetched when this one is taken, so a boundary never waits for a load of its own
+    // (bucket_start has B + 1 entries; the last one is M, which no k reaches)
+    uint32_t bend_next = bucket_start[b + 2 < (uint32_t)B ? b + 2 : (uint32_t)B];
     // first output slot: run starts before lo = s multiples of E + non-aligned non-empty bucket starts < lo
     uint32_t f_next = s1[b + 1] - (bucket_start[b + 1] + E - 1) / E;  // F[b+1]
     uint32_t pos = s + f_next;
     uint32_t ent = entries[lo];
     G1Affine30 cur = load_entry_point30(table30, ent);
-    G1Xyzz30 acc = g1_from_affine30(cur, ent >> 31);
+    // sign-tracked accumulator (curve30.h): true Y = sigma * acc.y; a partial is written raw, its readers normalise it
+    int32_t sigma;
+    G1Xyzz30 acc = g1_from_table30s(cur, ent >> 31, sigma);
     // the entry words run one step ahead of the gathers (ent_next = entry k+1 while entry k is being added), so a gather's address
     // never waits for the load of its own index
     uint32_t ent_next = 0;
@@ -545,23 +555,28 @@ __global__ __launch_bounds__(256, KZG_ACCUM_WAVES) void k_accum_affine(const uin
     for (uint32_t k = lo + 1; k < hi; k++) {
         // `cur` / `ent` hold entry k.  mode 0: mixed add; 1: restart the accumulator from cur; 2: skip (identity point)
         const bool neg_k = (ent >> 31) != 0;
-        const uint32_t ent_k = ent;
         int mode = 0;
         Madd30Mid mid;
         if (k == bend) {  // bucket boundary: flush and restart
-            out[pos++] = g1_normalize30(acc);
-            do {
+            out[pos++] = g1_partial_store30(acc, sigma);
+            for (;;) {
                 b++;
-                bend = bucket_start[b + 1];
-            } while (bend <= k);
+                bend = bend_next;
+                bend_next = bucket_start[b + 2 < (uint32_t)B ? b + 2 : (uint32_t)B];
+                if (bend > k) break;
+            }
             mode = 1;
         } else if (cur.is_inf_table()) {
             mode = 2;
         } else if (acc.inf) {
             mode = 1;
         }
-        if (mode == 0) mid = g1_madd30_phase1(acc, cur, neg_k);
-        if (mode == 1) acc = g1_from_affine30(cur, neg_k);
+        // mode 0: `sigma` holds tau between the two phases (the old sign is dead once tau is formed; phase 2 leaves the new one)
+        if (mode == 0) {
+            sigma = g1_tau30(sigma, neg_k);
+            mid = g1_madd30s_phase1(acc, cur, sigma);
+        }
+        if (mode == 1) acc = g1_from_table30s(cur, neg_k, sigma);
         // entry k's point is dead now: start the gather of entry k+1 into the same registers; its latency
         // hides under the eight remaining multiplies of this addition
         if (k + 1 < hi) {
@@ -573,9 +588,10 @@ __global__ __launch_bounds__(256, KZG_ACCUM_WAVES) void k_accum_affine(const uin
 #endif
             cur = load_entry_point30(table30, ent);
         }
-        if (mode == 0) acc = g1_madd30_phase2(acc, mid, neg_k, [&]() { return load_entry_point30(table30, ent_k); });
+        // (the rare doubling re-reads entry k's word: holding it across the addition would cost a register for nothing)
+        if (mode == 0) acc = g1_madd30s_phase2(acc, mid, sigma, neg_k, sigma, [&]() { return load_entry_point30(table30, entries[k]); });
     }
-    out[pos] = g1_normalize30(acc);
+    out[pos] = g1_partial_store30(acc, sigma);
 }
 
 __global__ __launch_bounds__(256) void k_sum_level(const MsmPoint *in, uint32_t count, int L, MsmPoint *out) {

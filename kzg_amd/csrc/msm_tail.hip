@@ -59,10 +59,18 @@ __device__ __forceinline__ MsmPoint butterfly_sum(MsmPoint acc) {
     return acc;
 }
 
-// sum of p[lo .. hi) by one wave; every lane returns the total
+// The round-1 partial list holds k_accum_affine's accumulators as they stood at a bucket boundary: X, ZZ, ZZZ with unsigned digits, Y
+// up to the sign kept in the first pad word (curve30.h, g1_partial_store30).  Every read of that list goes through here, which
+// returns the point with balanced digits and its true Y -- also when it is the only partial of its bucket and goes to `dense` as it
+// is (k_rc_sums and g1_add30 expect that form).  One normalisation per partial written, where round 1 used to normalise its
+// accumulator at every boundary any lane of the wave crossed.
+__device__ __forceinline__ MsmPoint load_partial(const MsmPoint *part, uint32_t k) { return g1_partial_load30(part[k]); }
+
+// sum of p[lo .. hi) by one wave; every lane returns the total.  RAW: p is the round-1 partial list
+template <bool RAW>
 __device__ __forceinline__ MsmPoint wave_sum(const MsmPoint *p, uint32_t lo, uint32_t hi, int lane) {
     MsmPoint acc = MsmPoint::infinity();
-    for (uint32_t k = lo + (uint32_t)lane; k < hi; k += 64) acc = g1_add30(acc, p[k]);
+    for (uint32_t k = lo + (uint32_t)lane; k < hi; k += 64) acc = g1_add30(acc, RAW ? load_partial(p, k) : p[k]);
     return butterfly_sum<64>(acc);
 }
 
@@ -84,7 +92,7 @@ __global__ KZG_TAIL_LB void k_fold_dense(const MsmPoint *part, const uint32_t *s
         return;
     }
     MsmPoint acc = MsmPoint::infinity();
-    for (uint32_t k = g; k < cnt; k += G) acc = g1_add30(acc, part[s + k]);
+    for (uint32_t k = g; k < cnt; k += G) acc = g1_add30(acc, load_partial(part, s + k));
     acc = butterfly_sum<G>(acc);
     if (g == 0) dense[b] = acc;
 }
@@ -100,7 +108,7 @@ __global__ KZG_TAIL_LB void k_fold_overflow(const MsmPoint *part, MsmPoint *scra
         const uint32_t e = tasks[t], b = e >> 12, sl = e & 0xfffu;
         const uint32_t s0 = s1[b], cnt = s1[b + 1] - s0, nsl = (cnt + OVF_SLICE - 1) / OVF_SLICE;
         const uint32_t lo = s0 + sl * OVF_SLICE, end = s0 + cnt, hi = lo + OVF_SLICE < end ? lo + OVF_SLICE : end;
-        MsmPoint acc = wave_sum(part, lo, hi, lane);
+        MsmPoint acc = wave_sum<true>(part, lo, hi, lane);
         if (nsl == 1) {
             if (lane == 0) dense[b] = acc;
             continue;
@@ -113,7 +121,7 @@ __global__ KZG_TAIL_LB void k_fold_overflow(const MsmPoint *part, MsmPoint *scra
         old = (uint32_t)__shfl((int)old, 0, 64);
         if (old == nsl - 1) {
             __threadfence();
-            acc = wave_sum(scratch, s0, s0 + nsl, lane);
+            acc = wave_sum<false>(scratch, s0, s0 + nsl, lane);
             if (lane == 0) dense[b] = acc;
         }
     }

@@ -70,8 +70,9 @@ def digit_out(k, unsigned_out):
 def gen_mul(name="mul30_asm", subs=(), unsigned_out=False):
     """subs: ((operand, constant), ...): the result is a*b/R + sum constant * operand, the extra terms entering the output
     columns as one v_mad_i64_i32 by an inline constant each (a subtraction merged into the product: no separate limb-wise
-    subtraction and carry pass, and the result comes out normalised)."""
-    args = "".join(f", const Fq30 &{o}" for o, _ in subs)
+    subtraction and carry pass, and the result comes out normalised).  A constant given as a NAME instead of a number is a per-lane
+    int32_t argument of the function (a sign, +1 or -1, held in one VGPR): the same multiply-add, its multiplier a register."""
+    args = "".join(f", const Fq30 &{o}" for o, _ in subs) + "".join(f", int32_t {c}" for _, c in subs if isinstance(c, str))
     s = f"__device__ __forceinline__ Fq30 {name}(const Fq30 &a, const Fq30 &b{args}) {{\n    int32_t m[F30_N];\n    Fq30 r;\n    uint64_t acc = 0;\n"
     for k in range(N):
         prods = [(f"a.v[{i}]", "v", f"b.v[{k - i}]", "v") for i in range(k + 1)]
@@ -83,11 +84,11 @@ def gen_mul(name="mul30_asm", subs=(), unsigned_out=False):
         for i in range(k - N + 1, N):
             prods.append((f"a.v[{i}]", "v", f"b.v[{k - i}]", "v"))
             prods.append((f"m[{i}]", "v", q(k - i), "s"))
-        prods += [(f"{o}.v[{k - N}]", "v", str(c), "i") for o, c in subs]
+        prods += [(f"{o}.v[{k - N}]", "v", str(c), "v" if isinstance(c, str) else "i") for o, c in subs]
         s += emit_products(prods)
         s += digit_out(k, unsigned_out)
     if subs:
-        s += emit_products([(f"{o}.v[{N - 1}]", "v", str(c), "i") for o, c in subs])
+        s += emit_products([(f"{o}.v[{N - 1}]", "v", str(c), "v" if isinstance(c, str) else "i") for o, c in subs])
     s += f"    r.v[{N - 1}] = (int32_t)acc;\n    return r;\n}}\n"
     return s
 
@@ -281,7 +282,8 @@ def gen_shoup29_dual():
 def main(dst):
     out = ("// GENERATED by tools/gen_mul30.py -- do not edit.\n" + gen_mul() + gen_sqr() + gen_muladd() +
            gen_mul("mul30_sub_asm", (("c", -1),)) + gen_sqr("sqr30_sub2_asm", (("c", -1), ("e", -2))) +
-           gen_mul("mul30u_asm", unsigned_out=True) + gen_sqr("sqr30_sub2u_asm", (("c", -1), ("e", -2)), unsigned_out=True))
+           gen_mul("mul30u_asm", unsigned_out=True) + gen_sqr("sqr30_sub2u_asm", (("c", -1), ("e", -2)), unsigned_out=True) +
+           gen_mul("mul30_sgn_asm", (("c", "t"),)))
     open(dst, "w").write(out)
     print("wrote", dst)
     if len(sys.argv) > 2:
