@@ -12,8 +12,8 @@
  *     <0 = runtime failure (HIP).  kzg_last_error(ctx) gives a human-readable string.
  *   - a kzg_ctx is bound to one GPU and is thread-safe.  The reference's blocking calls -- kzg_commit_coeff,
  *     kzg_commit_eval, kzg_msm_g1, kzg_witness_coeff, kzg_witness_coeff_batched, kzg_witness_eval, kzg_verify_poly_coeff /
- *     _eval, kzg_ntt_fr, kzg_coset_ntt_fr, kzg_poly_mul, kzg_poly_eval, kzg_quotient_linear / _eval, kzg_fr_vec_mul / _sub,
- *     kzg_divide_by_z_on_coset (KZGProver / KZGProverEvalForm / KZGVerifier are Clone + &self, src/coeff_form.rs:37-124; an
+ *     _eval, kzg_ntt_fr, kzg_coset_ntt_fr, kzg_poly_mul, kzg_poly_eval, kzg_poly_multi_eval, kzg_interpolate, kzg_quotient_linear / _eval,
+ *     kzg_fr_vec_mul / _sub, kzg_divide_by_z_on_coset (KZGProver / KZGProverEvalForm / KZGVerifier are Clone + &self, src/coeff_form.rs:37-124; an
  *     EvaluationDomain is the caller's own) -- run CONCURRENTLY on one ctx: each call leases one of the context's lanes
  *     (option "streams", default and maximum 16), submits its kernels there and waits for its own result only, so N host
  *     threads calling commit() / create_witness_batched() against one resident SRS fill the GPU like kzg_msm_g1_batch does.
@@ -78,6 +78,10 @@ extern "C" {
  *   kzg_verify_poly_eval                    as far as the monomial SRS goes (MSM limit below)
  *   kzg_witness_coeff_batched,
  *   kzg_verify_eval_batched                 k <= 16384 opening points         (the interpolation works on a k x k matrix: 8.6 GB there)
+ *   kzg_poly_multi_eval                     n <= 2^28; any k and batch: points go in passes of at most 4096, polynomials in chunks that
+ *                                                                             fill the grid; the workspace is at most 17 MiB of partial sums
+ *                                                                             beside one chunk's staged coefficients (host input: <= 256 MiB)
+ *   kzg_interpolate                         k <= 16384 points                (the k x k basis matrix: 8.6 GB there); any batch
  *   kzg_srs_lagrange_from_monomial_g1       d <= 2^24;  _g2: d <= 1024
  *   kzg_fk20_setup                          log_n <= 22                      (the plan holds 2N points of 224 B: 1.9 GB there)
  *   kzg_fk20_cosets_setup                   log_n <= 22, 1 <= log_l <= log_n (the plan holds 8 x 2N rows of 128 B: 8.6 GB there)
@@ -168,6 +172,9 @@ int kzg_sync(kzg_ctx *ctx);
  * "verify_cosets_chunk" (0 = default; n: kzg_verify_cosets works in chunks of at most n cells),
  * "verify_eval_batch_chunk" (0 = default, 16384; n <= 16384: kzg_verify_eval_batch works in chunks of at most n openings),
  * "multiopen_points_chunk" (0 = default, min(16, 2^22 / d); n <= 16: kzg_multiopen_eval_commit works in chunks of at most n distinct points),
+ * "multi_eval_segment" (0 = planned from n, k and batch; a power of two >= 8: kzg_poly_multi_eval cuts the coefficients into segments of
+ *  that length) and "multi_eval_points_chunk" (0 = default, 4096; n: at most min(n, 4096) points per pass); either one set also keeps the
+ *  call on its own kernels where it would take one kzg_poly_eval scan per value (up to 7 values): the same bytes, for A/B and tests,
  * "host_pairing" (1 / 0: the one pairing check that ends kzg_verify_cosets_batch / kzg_verify_eval_batch runs on the calling thread -- the same tower code
  *  compiled for the host -- instead of in a one-thread kernel; the same verdict, default 1),
  * "fk20_cosets_combine" (0 = the shared-doubling Straus kernel, default; 1 = one mul256 per term: the same bytes, for comparison),
@@ -734,6 +741,25 @@ int kzg_verify_multiopen(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, 
 /* ---- Fr polynomial helpers on the path (device) ---------------------------------------------- */
 /* Polynomial::eval (src/polynomial.rs:156-165) at one point. */
 int kzg_poly_eval(kzg_ctx *ctx, const void *coeffs, size_t n, const void *x, int sfmt, int flags, void *y_out);
+/* Polynomial::multi_eval (src/polynomial.rs:229-233) without its xs.len() > degree restriction, for `batch` polynomials at one
+ * point set: ys_out[b * k + i] = p_b(xs[i]).  coeffs: batch x n scalars in sfmt, stride n (KZG_IN_DEVICE applies to it);
+ * xs: k host scalars in sfmt; ys_out: batch x k scalars in sfmt, host, or device with KZG_OUT_DEVICE.
+ * One call instead of k x batch kzg_poly_eval calls, and the same bytes: every value is the residue below r in the form of sfmt.
+ * Coefficients may be any 256-bit value and count as their residue; each xs[i] must be below r; repeated points give repeated
+ * values.  KZG_ERR_SHAPE, before memory is touched: n == 0 or n > 2^28, an unknown format, a NULL context or buffer, an x >= r.
+ * k == 0 or batch == 0: KZG_OK, nothing written.  Blocking, on one leased lane.  Cost: n k batch field products in two kernels per
+ * pass (Horner per point and segment, then over the segments); up to 7 values in all (k x batch; 12 with k <= 2) one kzg_poly_eval
+ * scan per value instead, which is faster there (options "multi_eval_segment" / "multi_eval_points_chunk"; measurements: DESIGN.md
+ * section 3.4e). */
+int kzg_poly_multi_eval(kzg_ctx *ctx, const void *coeffs, size_t n, size_t batch, const void *xs, size_t k, int sfmt, int flags,
+                        void *ys_out);
+/* Polynomial::lagrange_interpolation (src/polynomial.rs:266-293): out[b * k + j] = coefficient j of the unique polynomial of degree < k
+ * through (xs[i], ys[b * k + i]).  One point set, `batch` value vectors; xs, ys host scalars; out host, or device with KZG_OUT_DEVICE.
+ * k <= 16384 (the k x k basis matrix).  Two equal xs: KZG_ERR_SHAPE (the reference panics in invert().unwrap()).
+ * k == 1 gives the constant y (the reference returns X + (y - x) there, src/polynomial.rs:269-272: that quirk is the caller's to
+ * mirror).  Also KZG_ERR_SHAPE, before `out` is written: k == 0, k > 16384, an x >= r, an unknown format, a NULL context or buffer.
+ * batch == 0: KZG_OK.  The basis matrix is built once per call, each value vector costs one k x k matrix-vector product. */
+int kzg_interpolate(kzg_ctx *ctx, const void *xs, const void *ys, size_t k, size_t batch, int sfmt, int flags, void *out);
 /* quotient of create_witness without the MSM: q = (p - y)/(X - x), n-1 scalars, in place allowed.
  * Returns KZG_ERR_POINT_NOT_ON_POLY if the remainder is non-zero. */
 int kzg_quotient_linear(kzg_ctx *ctx, const void *coeffs, size_t n, const void *x, const void *y, int sfmt,

@@ -126,7 +126,49 @@ struct Polynomial {  // src/polynomial.rs:24-27
         e.check(kzg_poly_eval(e.ctx(), coeffs.data(), num_coeffs(), x.le.data(), KZG_FR_CANONICAL_LE_32, 0, y.le.data()));
         return y;
     }
+    // :229-233 (the reference asserts xs.len() > degree; its values are p(xs[i]) either way)
+    std::vector<Scalar> multi_eval(const Engine &e, const std::vector<Scalar> &xs) const;
+    // :266-293; one point: X + (y - x), as the reference returns it
+    static Polynomial lagrange_interpolation(const Engine &e, const std::vector<Scalar> &xs, const std::vector<Scalar> &ys);
 };
+
+// kzg_poly_multi_eval: ys[b k + i] = p_b(xs[i]) for `batch` polynomials of n coefficients each (coeffs: batch x n scalars back to
+// back) at the k = xs.size() points
+inline std::vector<Scalar> poly_multi_eval(const Engine &e, const std::vector<Scalar> &coeffs, size_t n, size_t batch, const std::vector<Scalar> &xs) {
+    static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+    if (n == 0 || coeffs.size() / n != batch || coeffs.size() != batch * n) throw ReferencePanic("poly_multi_eval: shape");
+    std::vector<Scalar> ys(batch * xs.size());
+    Scalar none;
+    e.check(kzg_poly_multi_eval(e.ctx(), coeffs.data(), n, batch, xs.empty() ? &none : xs.data(), xs.size(), KZG_FR_CANONICAL_LE_32, 0,
+                                ys.empty() ? &none : ys.data()));
+    return ys;
+}
+
+// kzg_interpolate: out[b k + j] = coefficient j of the polynomial of degree < k through (xs[i], ys[b k + i]), k = xs.size(); one point
+// gives the constant
+inline std::vector<Scalar> interpolate(const Engine &e, const std::vector<Scalar> &xs, const std::vector<Scalar> &ys) {
+    const size_t k = xs.size();
+    if (k == 0 || ys.size() % k) throw ReferencePanic("interpolate: shape");
+    std::vector<Scalar> out(ys.size());
+    Scalar none;
+    e.check(kzg_interpolate(e.ctx(), xs.data(), ys.empty() ? &none : ys.data(), k, ys.size() / k, KZG_FR_CANONICAL_LE_32, 0, ys.empty() ? &none : out.data()));
+    return out;
+}
+
+inline std::vector<Scalar> Polynomial::multi_eval(const Engine &e, const std::vector<Scalar> &xs) const {
+    if (xs.size() <= degree) throw ReferencePanic("assert!(xs.len() > self.degree())");
+    std::vector<Scalar> c(coeffs.begin(), coeffs.begin() + num_coeffs());
+    return poly_multi_eval(e, c, num_coeffs(), 1, xs);
+}
+
+inline Polynomial Polynomial::lagrange_interpolation(const Engine &e, const std::vector<Scalar> &xs, const std::vector<Scalar> &ys) {
+    if (xs.size() != ys.size()) throw ReferencePanic("assert_eq!(xs.len(), ys.len())");
+    std::vector<Scalar> c = interpolate(e, xs, ys);
+    if (xs.size() != 1) return Polynomial::make(std::move(c));
+    Scalar d = ys[0];  // X + (y - x): the subtraction is the engine's, on one element
+    e.check(kzg_fr_vec_sub(e.ctx(), d.le.data(), xs[0].le.data(), 1, KZG_FR_CANONICAL_LE_32, 0));
+    return Polynomial::new_from_coeffs({d, Scalar::from_u64(1)}, 1);
+}
 
 struct EvaluationDomain {  // src/ft.rs:17-25
     std::vector<Scalar> coeffs;

@@ -142,6 +142,8 @@ def load(path=None):
                                           ctypes.POINTER(i32)]),
         "kzg_verify_eval_batch": (i32, [vp, vp, vp, vp, vp, i32, vp, sz, ctypes.POINTER(u32), vp, i32, sz, vp, ctypes.POINTER(i32)]),
         "kzg_poly_eval": (i32, [vp, vp, sz, vp, i32, i32, vp]),
+        "kzg_poly_multi_eval": (i32, [vp, vp, sz, sz, vp, sz, i32, i32, vp]),
+        "kzg_interpolate": (i32, [vp, vp, vp, sz, sz, i32, i32, vp]),
         "kzg_quotient_linear": (i32, [vp, vp, sz, vp, vp, i32, i32, vp]),
         "kzg_quotient_eval": (i32, [vp, vp, sz, sz, i32, i32, vp]),
         "kzg_eval_form_eval": (i32, [vp, vp, sz, sz, vp, i32, i32, vp]),

@@ -255,6 +255,50 @@ class Engine:
             _raise(self, rc)
         return self._scalar_from(out.raw, sfmt)
 
+    def poly_multi_eval(self, coeffs, xs, n=None, batch=1, out=None):
+        """kzg_poly_multi_eval: the values p_b(xs[i]) of `batch` polynomials of n coefficients each (coeffs: ints, a canonical blob or
+        a DeviceBuffer of batch x n scalars back to back) at the points xs (ints below R), in one call.  Returns a list of `batch`
+        lists of len(xs) ints -- one flat list for batch = 1 -- or `out` (a DeviceBuffer of batch x len(xs) scalars in the
+        coefficients' format) when one is given."""
+        ptr, nn, sfmt, flags, _keep = self._scalars_arg(coeffs)
+        if n is None:
+            if batch < 1 or nn % batch:
+                raise ReferencePanic("%d scalars are not %d polynomials of equal length" % (nn, batch))
+            n = nn // batch
+        if nn < n * batch:  # the call would read past the buffer
+            raise ReferencePanic("%d scalars given, batch * n = %d" % (nn, batch * n))
+        k = len(xs)
+        xb = b"".join(self._host_scalar(int(x), sfmt) if 0 <= int(x) < R_MODULUS else (int(x) % (1 << 256)).to_bytes(32, "little") for x in xs)
+        if out is not None:
+            if out.n < batch * k or out.sfmt != sfmt:
+                raise ReferencePanic("poly_multi_eval: out holds %d scalars, batch * k = %d (and has the coefficients' format)" % (out.n, batch * k))
+            rc = self.lib.kzg_poly_multi_eval(self.ctx, ptr, n, batch, xb, k, sfmt, flags | L.OUT_DEVICE, out.ptr)
+            if rc:
+                _raise(self, rc)
+            return out
+        buf = ctypes.create_string_buffer(32 * max(batch * k, 1))
+        rc = self.lib.kzg_poly_multi_eval(self.ctx, ptr, n, batch, xb, k, sfmt, flags, buf)
+        if rc:
+            _raise(self, rc)
+        ys = [self._scalar_from(buf.raw[32 * j:32 * j + 32], sfmt) for j in range(batch * k)]
+        return ys if batch == 1 else [ys[b * k:(b + 1) * k] for b in range(batch)]
+
+    def interpolate(self, xs, ys):
+        """kzg_interpolate: the coefficients (k ints, lowest first) of the polynomial of degree < k through (xs[i], ys[i]); ys may be
+        a list of value vectors on the one point set (then a list of coefficient lists comes back).  One point gives the constant."""
+        k = len(xs)
+        many = k > 0 and len(ys) > 0 and isinstance(ys[0], (list, tuple))
+        rows = [list(v) for v in ys] if many else [list(ys)]
+        if any(len(v) != k for v in rows):
+            raise ReferencePanic("assert_eq!(xs.len(), ys.len())")
+        xb = b"".join(int(x).to_bytes(32, "little") if 0 <= int(x) < (1 << 256) else pack_scalars([x]) for x in xs)
+        out = ctypes.create_string_buffer(32 * max(len(rows) * k, 1))
+        rc = self.lib.kzg_interpolate(self.ctx, xb, pack_scalars([y for v in rows for y in v]), k, len(rows), L.FR_CANONICAL, 0, out)
+        if rc:
+            _raise(self, rc)
+        cs = unpack_scalars(out.raw[: 32 * len(rows) * k])
+        return [cs[b * k:(b + 1) * k] for b in range(len(rows))] if many else cs
+
     def quotient_linear(self, coeffs, x, y):
         blob = pack_scalars(coeffs)
         n = len(blob) // 32
@@ -1155,6 +1199,19 @@ class Polynomial:
     def eval(self, engine, x):  # :156-165
         return engine.poly_eval(self.slice_coeffs(), x)
 
+    def multi_eval(self, engine, xs):  # :229-233
+        if len(xs) <= self.degree:
+            raise ReferencePanic("assert!(xs.len() > self.degree())")
+        return engine.poly_multi_eval(self.slice_coeffs(), xs)
+
+    @staticmethod
+    def lagrange_interpolation(engine, xs, ys):  # :266-293
+        if len(xs) != len(ys):
+            raise ReferencePanic("assert_eq!(xs.len(), ys.len())")
+        if len(xs) == 1:  # :269-272: the reference returns X + (y - x) for one point
+            return Polynomial.new_from_coeffs([(int(ys[0]) - int(xs[0])) % R_MODULUS, 1], 1)
+        return Polynomial(engine.interpolate(xs, ys))
+
     def fft_mul(self, engine, other):  # :167-183 (and best_mul :185-191: the product is the same polynomial)
         coeffs = engine.poly_mul(self.slice_coeffs(), other.slice_coeffs())
         return Polynomial(coeffs)  # From<EvaluationDomain> = Polynomial::new (src/ft.rs:27-31)
@@ -1339,6 +1396,12 @@ class KZGProver:
         n = max(p.num_coeffs() for p in polynomials)
         blob = b"".join(pack_scalars(p.slice_coeffs() + [0] * (n - p.num_coeffs())) for p in polynomials)
         return _witness_cosets(self.engine, self.engine.lib.kzg_witness_cosets_coeff, plan, blob, n, len(polynomials), ofmt)
+
+    def open_at_points(self, polynomial, xs, ofmt=L.G1_AFFINE_MONT):
+        """(ys, KZGBatchWitness): the values of the polynomial at xs from one kzg_poly_multi_eval call, then create_witness_batched
+        at (xs, ys) (not a reference method: the reference's caller evaluates point by point)."""
+        ys = self.engine.poly_multi_eval(polynomial.slice_coeffs(), xs)
+        return ys, self.create_witness_batched(polynomial, xs, ys, ofmt)
 
     def create_witness_batched(self, polynomial, xs, ys, ofmt=L.G1_AFFINE_MONT):  # :83-111
         e = self.engine

@@ -424,6 +424,12 @@ extern "C" int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value) 
     } else if (k == "multiopen_points_chunk") {
         if (value < 0 || value > 16) return fail(ctx, KZG_ERR_SHAPE, "multiopen_points_chunk must be 0 (min(16, 2^22 / d) points) or 1..16 points");
         ctx->opt_multiopen_points_chunk = (int)value;
+    } else if (k == "multi_eval_segment") {
+        if (value != 0 && (value < 8 || value > (1 << 28) || (value & (value - 1)))) return fail(ctx, KZG_ERR_SHAPE, "multi_eval_segment must be 0 (auto) or a power of two in 8..2^28");
+        ctx->opt_multi_eval_segment = (int)value;
+    } else if (k == "multi_eval_points_chunk") {
+        if (value < 0 || value > (1 << 30)) return fail(ctx, KZG_ERR_SHAPE, "multi_eval_points_chunk must be 0 (auto) or 1..2^30 points");
+        ctx->opt_multi_eval_points_chunk = (int)value;
     } else if (k == "ntt_vec_log") {
         if (value < 0 || value > 2) return fail(ctx, KZG_ERR_SHAPE, "ntt_vec_log must be 0..2");
         ctx->opt_ntt_vec_log = (int)value;

@@ -402,6 +402,86 @@ extern "C" int kzg_witness_coeff_batched(kzg_ctx *ctx, const kzg_srs *srs, const
     return witness_coeff_batched_run(ctx, sink, coeffs, n, xs, ys, k, sfmt, flags, out_w, ofmt, out_r, out_r_len);
 }
 
+// Polynomial::lagrange_interpolation (src/polynomial.rs:266-293) for `batch` value vectors on one point set, from the interpolation
+// kernels above: Z and the barycentric weights 1 / Z'(x_i) as witness_coeff_batched_run makes them, the k x k basis matrix
+// (row j, column i: coefficient j of L_i) once, then one k_bary_colsum per value vector.  k = 1 is the constant y.
+extern "C" int kzg_interpolate(kzg_ctx *ctx, const void *xs, const void *ys, size_t k, size_t batch, int sfmt, int flags, void *out) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    if (!xs || !ys || !out) return fail(ctx, KZG_ERR_SHAPE, "kzg_interpolate: NULL xs, ys or out");
+    if (sfmt != KZG_FR_MONT_LE_32 && sfmt != KZG_FR_CANONICAL_LE_32) return fail(ctx, KZG_ERR_SHAPE, "unknown scalar format");
+    if (k == 0) return fail(ctx, KZG_ERR_SHAPE, "no interpolation points");
+    if (k > 16384) return fail(ctx, KZG_ERR_SHAPE, "kzg_interpolate supports at most 16384 points (the interpolation works on a k x k matrix)");
+    if (batch > ((size_t)1 << 40) / k) return fail(ctx, KZG_ERR_SHAPE, "kzg_interpolate: batch x k too large");
+    for (size_t i = 0; i < k; i++) {
+        Fr v;
+        memcpy(v.v, (const uint8_t *)xs + 32 * i, 32);
+        if (!is_canonical(v)) return fail(ctx, KZG_ERR_SHAPE, "kzg_interpolate: a point is not below r");
+    }
+    if (batch == 0) return KZG_OK;
+    const bool out_dev = (flags & KZG_OUT_DEVICE) != 0;
+    kzg::Lease ls;
+    KZG_TRY(lease_lane(ctx, &ls));
+    const int lane = ls.lane;
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->lanes[lane].stream;
+    const int to_m = sfmt == KZG_FR_CANONICAL_LE_32;
+    const uint32_t log_M = (uint32_t)ilog2_ceil(k + 1);
+    const size_t Mz = (size_t)1 << log_M;
+    KZG_TRY(lane_reserve(ctx, lane, (k == 1 ? 0 : (size_t)k * k * 32 + 2 * Mz * 32 + ntt_workspace_bytes(log_M)) + 8 * (k + 8) * 32 + (1 << 20)));
+    Fr *dy = (Fr *)lane_alloc(ctx, lane, k * 32), *I = out_dev ? nullptr : (Fr *)lane_alloc(ctx, lane, k * 32);
+    if (!dy || (!out_dev && !I)) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    if (k == 1) {  // the true interpolant (the reference's X + (y - x) is the caller's: kzg_amd.api, Polynomial.lagrange_interpolation)
+        for (size_t b = 0; b < batch; b++) {
+            Fr *dst = out_dev ? (Fr *)out + b : I;
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(dst, (const Fr *)ys + b, 32, hipMemcpyHostToDevice, st));
+            KZG_TRY(fr_convert(ctx, st, dst, 1, 1));  // (a product: any 256-bit value leaves as its residue)
+            KZG_TRY(fr_convert(ctx, st, dst, 1, 0));
+            if (!out_dev) KZG_HIP_CHECK(ctx, hipMemcpyAsync((Fr *)out + b, I, 32, hipMemcpyDeviceToHost, st));
+        }
+        KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        if (ctx->prof) prof_collect(ctx);
+        return KZG_OK;
+    }
+    Fr *dx = (Fr *)lane_alloc(ctx, lane, k * 32), *z0 = (Fr *)lane_alloc(ctx, lane, (k + 1) * 32);
+    Fr *den = (Fr *)lane_alloc(ctx, lane, k * 32), *deni = (Fr *)lane_alloc(ctx, lane, k * 32);
+    Fr *rows = (Fr *)lane_alloc(ctx, lane, (size_t)k * k * 32);
+    Fr *zev = (Fr *)lane_alloc(ctx, lane, Mz * 32), *wpow = (Fr *)lane_alloc(ctx, lane, Mz * 32);
+    int *flag = (int *)lane_alloc(ctx, lane, 256);
+    if (!dx || !z0 || !den || !deni || !rows || !zev || !wpow || !flag) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(flag, 0, sizeof(int), st));
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(dx, xs, k * 32, hipMemcpyHostToDevice, st));
+    if (to_m) KZG_TRY(fr_convert(ctx, st, dx, k, 1));
+    // the point set: Z from its values on the M-th roots of unity (M = 2^m > k), Z'(x_i), their inverses, the basis matrix
+    KZG_TRY(pow_table(ctx, st, host_omega(log_M), Fr::one(), Mz, wpow));
+    KZG_LAUNCH(ctx, st, "k_prod_diff", k_prod_diff, (unsigned)Mz, 256, 0, wpow, dx, (uint32_t)k, 0, zev);
+    KZG_TRY(ntt_run(ctx, lane, zev, log_M, 1));
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(z0, zev, (k + 1) * 32, hipMemcpyDeviceToDevice, st));
+    KZG_LAUNCH(ctx, st, "k_prod_diff", k_prod_diff, (unsigned)k, 256, 0, dx, dx, (uint32_t)k, 1, den);
+    KZG_LAUNCH(ctx, st, "k_any_zero", k_any_zero, gridfor(k), 256, 0, den, k, flag);  // two equal x_i
+    int hflag = 0;
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(&hflag, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));  // before anything is written to `out`
+    if (hflag & 1) return fail(ctx, KZG_ERR_SHAPE, "duplicate interpolation points (reference: invert().unwrap() panic)");
+    KZG_LAUNCH(ctx, st, "k_inverse_each", k_inverse_each, gridfor(k), 256, 0, den, deni, k);
+    uint32_t CH = 1;
+    while ((uint64_t)CH * CH * 4 <= k) CH *= 2;
+    const uint32_t nch = (uint32_t)((k + 1 + CH - 1) / CH);
+    if (nch > 256) return fail(ctx, KZG_ERR_INTERNAL, "interpolation chunk count exceeds the kernel's LDS array (B[256])");
+    const unsigned bt = nch <= 64 ? 64 : (nch <= 128 ? 128 : 256);
+    KZG_LAUNCH(ctx, st, "k_bary_rows", k_bary_rows_chunked, (unsigned)k, bt, 0, dx, (const Fr *)nullptr, deni, z0, (uint32_t)k, CH, nch, rows);
+    for (size_t b = 0; b < batch; b++) {
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(dy, (const Fr *)ys + b * k, k * 32, hipMemcpyHostToDevice, st));
+        if (to_m) KZG_TRY(fr_convert(ctx, st, dy, k, 1));
+        Fr *dst = out_dev ? (Fr *)out + b * k : I;
+        KZG_LAUNCH(ctx, st, "k_bary_colsum", k_bary_colsum, (unsigned)k, 256, 0, rows, (uint32_t)k, dst, dy);  // sum_i y_i L_i
+        if (to_m) KZG_TRY(fr_convert(ctx, st, dst, k, 0));
+        if (!out_dev) KZG_HIP_CHECK(ctx, hipMemcpyAsync((Fr *)out + b * k, I, k * 32, hipMemcpyDeviceToHost, st));
+    }
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (ctx->prof) prof_collect(ctx);
+    return KZG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Opening-point sets.  Everything create_witness_batched derives from the opening POINTS alone -- Z = prod (X - x_i), the
 // barycentric weights 1 / Z'(x_i), the coset shift on which Z has no root, and 1 / Z on that coset (N values: the batch inversion of
