@@ -12,7 +12,7 @@
  *     <0 = runtime failure (HIP).  kzg_last_error(ctx) gives a human-readable string.
  *   - a kzg_ctx is bound to one GPU and is thread-safe.  The reference's blocking calls -- kzg_commit_coeff,
  *     kzg_commit_eval, kzg_msm_g1, kzg_witness_coeff, kzg_witness_coeff_batched, kzg_witness_eval, kzg_verify_poly_coeff /
- *     _eval, kzg_ntt_fr, kzg_coset_ntt_fr, kzg_poly_mul, kzg_poly_eval, kzg_poly_multi_eval, kzg_interpolate, kzg_quotient_linear / _eval,
+ *     _eval, kzg_ntt_fr, kzg_coset_ntt_fr, kzg_poly_mul, kzg_poly_divide, kzg_poly_eval, kzg_poly_multi_eval, kzg_interpolate, kzg_quotient_linear / _eval,
  *     kzg_fr_vec_mul / _sub, kzg_divide_by_z_on_coset (KZGProver / KZGProverEvalForm / KZGVerifier are Clone + &self, src/coeff_form.rs:37-124; an
  *     EvaluationDomain is the caller's own) -- run CONCURRENTLY on one ctx: each call leases one of the context's lanes
  *     (option "streams", default and maximum 16), submits its kernels there and waits for its own result only, so N host
@@ -82,6 +82,8 @@ extern "C" {
  *                                                                             fill the grid; the workspace is at most 17 MiB of partial sums
  *                                                                             beside one chunk's staged coefficients (host input: <= 256 MiB)
  *   kzg_interpolate                         k <= 16384 points                (the k x k basis matrix: 8.6 GB there); any batch
+ *   kzg_poly_divide                         na <= 2^27 (the product limit of kzg_poly_mul); any nb and batch: dividends go in chunks of
+ *                                                                             min(256, max(1, 2^20 / na)); the workspace does not grow with batch
  *   kzg_srs_lagrange_from_monomial_g1       d <= 2^24;  _g2: d <= 1024
  *   kzg_fk20_setup                          log_n <= 22                      (the plan holds 2N points of 224 B: 1.9 GB there)
  *   kzg_fk20_cosets_setup                   log_n <= 22, 1 <= log_l <= log_n (the plan holds 8 x 2N rows of 128 B: 8.6 GB there)
@@ -175,6 +177,8 @@ int kzg_sync(kzg_ctx *ctx);
  * "multi_eval_segment" (0 = planned from n, k and batch; a power of two >= 8: kzg_poly_multi_eval cuts the coefficients into segments of
  *  that length) and "multi_eval_points_chunk" (0 = default, 4096; n: at most min(n, 4096) points per pass); either one set also keeps the
  *  call on its own kernels where it would take one kzg_poly_eval scan per value (up to 7 values): the same bytes, for A/B and tests,
+ * "poly_divide_base" (0 = default, 64; a power of two in 1..64: the coefficients of the power-series inverse kzg_poly_divide's one-workgroup
+ *  base kernel produces before Newton doubling takes over; the same bytes, for A/B and for tests that drive several Newton levels at tiny shapes),
  * "host_pairing" (1 / 0: the one pairing check that ends kzg_verify_cosets_batch / kzg_verify_eval_batch runs on the calling thread -- the same tower code
  *  compiled for the host -- instead of in a one-thread kernel; the same verdict, default 1),
  * "fk20_cosets_combine" (0 = the shared-doubling Straus kernel, default; 1 = one mul256 per term: the same bytes, for comparison),
@@ -771,6 +775,26 @@ int kzg_quotient_eval(kzg_ctx *ctx, const void *evals, size_t d, size_t i, int s
  * NTTs of size next_pow2(na + nb) and a pointwise product (EvaluationDomain::mul_assign, src/ft.rs:220-244).
  * The product is unique, so it equals the reference's naive Mul (:473-487) as well.  Host or device buffers. */
 int kzg_poly_mul(kzg_ctx *ctx, const void *a, size_t na, const void *b, size_t nb, int sfmt, int flags, void *out);
+/* Polynomial::long_division (src/polynomial.rs:193-227) by a divisor of any degree, for `batch` dividends and ONE divisor:
+ * a_bi = q_bi b + r_bi with deg r_bi < deg b.  a: batch x na scalars in sfmt, stride na; b: nb scalars, b[0] the constant term
+ * (KZG_IN_DEVICE applies to both).  Coefficients may be any 256-bit value and count as their residue.  b[nb - 1] must be non-zero
+ * mod r (pass slice_coeffs(), as for kzg_commit_coeff): a zero top coefficient -- the zero divisor included, where the reference
+ * panics with "divisor must not be zero" -- is KZG_ERR_SHAPE; for a device-resident divisor the check is one 32-byte read.
+ * Dividends may have leading zero coefficients and may be zero.
+ * q_out: batch x (na - nb + 1) scalars, stride na - nb + 1; r_out: batch x (nb - 1) scalars, stride nb - 1; both in sfmt, every value
+ * the residue below r, zero-padded to these lengths, to the host or (KZG_OUT_DEVICE) the device.  Either may be NULL, not both
+ * unless both would be empty.  na < nb: q_out is not touched, r_out is the dividend zero-padded to nb - 1.  nb == 1: r_out is not
+ * touched, q = a / b[0].  exact (optional, batch ints, host): exact[bi] = 1 iff the remainder of dividend bi is zero (the
+ * reference's None); computed on the device, with or without r_out.  The quotient and the remainder are unique, so the bytes are the
+ * reference's.
+ * KZG_ERR_SHAPE, before any output is written: a NULL context, NULL a or b (batch > 0), both outputs NULL where one would not be
+ * empty, na == 0, nb == 0, an unknown format, a top coefficient that is 0 mod r, na > 2^27, batch x na x 32 beyond size_t.
+ * batch == 0: KZG_OK, nothing written.  Blocking, on one leased lane.  Cost: the power-series inverse of rev(b) to na - nb + 1 terms
+ * once per call (a one-workgroup schoolbook base, option "poly_divide_base", then Newton doubling through the NTT), per dividend
+ * one product of next_pow2(2 (na - nb) + 1) points against the once-transformed inverse and, for the remainder, two streaming
+ * folds and one product of next_pow2(nb - 1) points. */
+int kzg_poly_divide(kzg_ctx *ctx, const void *a, size_t na, size_t batch, const void *b, size_t nb, int sfmt, int flags, void *q_out,
+                    void *r_out, int *exact);
 
 /* ---- device memory + measurement ------------------------------------------------------------- */
 int kzg_dev_alloc(kzg_ctx *ctx, size_t bytes, void **out);

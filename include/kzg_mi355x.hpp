@@ -130,6 +130,15 @@ struct Polynomial {  // src/polynomial.rs:24-27
     std::vector<Scalar> multi_eval(const Engine &e, const std::vector<Scalar> &xs) const;
     // :266-293; one point: X + (y - x), as the reference returns it
     static Polynomial lagrange_interpolation(const Engine &e, const std::vector<Scalar> &xs, const std::vector<Scalar> &ys);
+    bool is_zero() const { return degree == 0 && coeffs[0].is_zero(); }  // :45-47
+    // :193-227: (quotient, Option<remainder>); the remainder is valid iff has_remainder (the reference's Some)
+    struct Division;
+    Division long_division(const Engine &e, const Polynomial &divisor) const;
+};
+struct Polynomial::Division {
+    Polynomial quotient;
+    bool has_remainder = false;
+    Polynomial remainder;
 };
 
 // kzg_poly_multi_eval: ys[b k + i] = p_b(xs[i]) for `batch` polynomials of n coefficients each (coeffs: batch x n scalars back to
@@ -153,6 +162,44 @@ inline std::vector<Scalar> interpolate(const Engine &e, const std::vector<Scalar
     Scalar none;
     e.check(kzg_interpolate(e.ctx(), xs.data(), ys.empty() ? &none : ys.data(), k, ys.size() / k, KZG_FR_CANONICAL_LE_32, 0, ys.empty() ? &none : out.data()));
     return out;
+}
+
+// kzg_poly_divide: `batch` dividends of na coefficients each (a: batch x na scalars back to back) by the one divisor b (b.back() != 0):
+// q receives batch x (na - nb + 1) and r batch x (nb - 1) scalars, zero-padded; exact[bi] = 1 iff remainder bi is zero.  na < nb: q is
+// empty and r holds the dividends.
+inline void poly_divide(const Engine &e, const std::vector<Scalar> &a, size_t na, size_t batch, const std::vector<Scalar> &b, std::vector<Scalar> &q,
+                        std::vector<Scalar> &r, std::vector<int> *exact = nullptr) {
+    static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+    const size_t nb = b.size();
+    if (na == 0 || nb == 0 || a.size() / na != batch || a.size() != batch * na) throw ReferencePanic("poly_divide: shape");
+    q.assign(na >= nb ? batch * (na - nb + 1) : 0, Scalar());
+    r.assign(batch * (nb - 1), Scalar());
+    if (exact) exact->assign(batch, 0);
+    Scalar none;
+    e.check(kzg_poly_divide(e.ctx(), a.data(), na, batch, b.data(), nb, KZG_FR_CANONICAL_LE_32, 0, q.empty() ? &none : q.data(),
+                            r.empty() ? &none : r.data(), exact && batch ? exact->data() : nullptr));
+}
+
+inline Polynomial::Division Polynomial::long_division(const Engine &e, const Polynomial &divisor) const {
+    Division d;
+    d.quotient = Polynomial::make({Scalar()});  // new_zero
+    if (is_zero()) return d;
+    if (divisor.is_zero()) throw ReferencePanic("divisor must not be zero!");
+    if (degree < divisor.degree) {
+        d.has_remainder = true;
+        d.remainder = *this;
+        return d;
+    }
+    std::vector<Scalar> a(coeffs.begin(), coeffs.begin() + num_coeffs()), b(divisor.coeffs.begin(), divisor.coeffs.begin() + divisor.num_coeffs());
+    std::vector<Scalar> q, r;
+    std::vector<int> exact;
+    poly_divide(e, a, a.size(), 1, b, q, r, &exact);
+    d.quotient = Polynomial::new_from_coeffs(std::move(q), degree - divisor.degree);
+    if (!exact[0]) {
+        d.has_remainder = true;
+        d.remainder = Polynomial::make(std::move(r));  // the degree fixed up, as shrink_degree leaves it
+    }
+    return d;
 }
 
 inline std::vector<Scalar> Polynomial::multi_eval(const Engine &e, const std::vector<Scalar> &xs) const {

@@ -160,6 +160,7 @@ def load(path=None):
         "kzg_multiopen_coeff_finish": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, vp, vp, i32, i32, vp, vp, i32]),
         "kzg_verify_multiopen": (i32, [vp, vp, vp, vp, vp, i32, vp, sz, ctypes.POINTER(u32), sz, vp, vp, vp, vp, i32, ctypes.POINTER(i32)]),
         "kzg_poly_mul": (i32, [vp, vp, sz, vp, sz, i32, i32, vp]),
+        "kzg_poly_divide": (i32, [vp, vp, sz, sz, vp, sz, i32, i32, vp, vp, ctypes.POINTER(i32)]),
         "kzg_dev_alloc": (i32, [vp, sz, c_void_pp]),
         "kzg_dev_free": (i32, [vp, vp]),
         "kzg_dev_upload": (i32, [vp, vp, vp, sz]),

@@ -319,6 +319,55 @@ class Engine:
             _raise(self, rc)
         return unpack_scalars(out.raw)
 
+    def poly_divide(self, a, b, batch=1, na=None, q_out=None, r_out=None):
+        """kzg_poly_divide: `batch` dividends of na coefficients each (a: ints, a canonical blob or a DeviceBuffer of batch x na
+        scalars back to back) by the one divisor b (lowest coefficient first, b[-1] != 0; ints, a blob, or a DeviceBuffer when a is
+        one).  Returns (q, r, exact): the quotients zero-padded to na - nb + 1 and the remainders zero-padded to nb - 1 coefficients
+        -- flat lists of ints for batch = 1, lists of `batch` lists otherwise, or the DeviceBuffers q_out / r_out (in the dividends'
+        format) when both are given -- and exact, a list of `batch` bools: the remainder is zero (the reference's None).  na < nb
+        leaves q empty and r the dividend."""
+        ptr, nn, sfmt, flags, _keep = self._scalars_arg(a)
+        if na is None:
+            if batch < 1 or nn % batch:
+                raise ReferencePanic("%d scalars are not %d dividends of equal length" % (nn, batch))
+            na = nn // batch
+        if nn < na * batch:  # the call would read past the buffer
+            raise ReferencePanic("%d scalars given, batch * na = %d" % (nn, batch * na))
+        tmp = None
+        if isinstance(b, DeviceBuffer):
+            if not flags or b.sfmt != sfmt:
+                raise ReferencePanic("poly_divide: a device-resident divisor needs device-resident dividends of the same format")
+            bptr, nb = b.ptr, b.n
+        else:
+            bptr = bytes(b) if isinstance(b, (bytes, bytearray)) else b"".join(self._host_scalar(int(x), sfmt) for x in b)
+            nb = len(bptr) // 32
+            if flags:  # KZG_IN_DEVICE covers both inputs
+                tmp = DeviceBuffer(self, max(nb, 1), sfmt).upload(bptr) if nb else None
+                bptr = tmp.ptr if tmp else None
+        m, nr = (na - nb + 1 if na >= nb else 0), max(nb - 1, 0)
+        ex = (ctypes.c_int * max(batch, 1))()
+        try:
+            if q_out is not None or r_out is not None:
+                if q_out is None or r_out is None or q_out.n < batch * m or r_out.n < batch * nr or q_out.sfmt != sfmt or r_out.sfmt != sfmt:
+                    raise ReferencePanic("poly_divide: q_out and r_out hold batch * (na - nb + 1) and batch * (nb - 1) scalars of the dividends' format")
+                rc = self.lib.kzg_poly_divide(self.ctx, ptr, na, batch, bptr, nb, sfmt, flags | L.OUT_DEVICE, q_out.ptr, r_out.ptr, ex)
+                if rc:
+                    _raise(self, rc)
+                return q_out, r_out, [bool(v) for v in ex[:batch]]
+            qb, rb = ctypes.create_string_buffer(32 * max(batch * m, 1)), ctypes.create_string_buffer(32 * max(batch * nr, 1))
+            rc = self.lib.kzg_poly_divide(self.ctx, ptr, na, batch, bptr, nb, sfmt, flags, qb, rb, ex)
+            if rc:
+                _raise(self, rc)
+        finally:
+            if tmp is not None:
+                tmp.free()
+        q = [self._scalar_from(qb.raw[32 * j:32 * j + 32], sfmt) for j in range(batch * m)]
+        r = [self._scalar_from(rb.raw[32 * j:32 * j + 32], sfmt) for j in range(batch * nr)]
+        exact = [bool(v) for v in ex[:batch]]
+        if batch == 1:
+            return q, r, exact
+        return [q[i * m:(i + 1) * m] for i in range(batch)], [r[i * nr:(i + 1) * nr] for i in range(batch)], exact
+
     def quotient_eval(self, evals, i):
         blob = pack_scalars(evals)
         d = len(blob) // 32
@@ -1217,6 +1266,25 @@ class Polynomial:
         return Polynomial(coeffs)  # From<EvaluationDomain> = Polynomial::new (src/ft.rs:27-31)
 
     best_mul = fft_mul
+
+    @staticmethod
+    def new_zero():  # :49-54
+        return Polynomial([0], 0)
+
+    def is_zero(self):  # :45-47
+        return self.degree == 0 and self.coeffs[0] == 0
+
+    def long_division(self, engine, divisor):  # :193-227 -> (quotient, remainder or None)
+        if self.is_zero():
+            return Polynomial.new_zero(), None
+        if divisor.is_zero():
+            raise ReferencePanic("divisor must not be zero!")
+        if self.degree < divisor.degree:
+            return Polynomial.new_zero(), Polynomial(list(self.coeffs), self.degree)
+        q, r, exact = engine.poly_divide(self.slice_coeffs(), divisor.slice_coeffs())
+        quotient = Polynomial.new_from_coeffs(q, self.degree - divisor.degree)
+        # the reference's remainder keeps the dividend's vector with its degree shrunk (:204-222): Polynomial() fixes the degree up
+        return quotient, (None if exact[0] else Polynomial(r))
 
     def __eq__(self, other):  # :29-40
         return self.degree == other.degree and all(a == b for a, b in zip(self.coeffs, other.coeffs))

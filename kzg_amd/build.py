@@ -18,7 +18,7 @@ OUT_HOOKS = os.path.join(HERE, "libkzg_mi355x_hooks.so")
 HOOK_SOURCES = ["capi.hip", "mgpu.hip", "g1ntt.hip", "verify_cosets.hip", "verify_cosets_batch.hip", "verify_eval_batch.hip"]  # the translation units that hold hooks (runtime.hip holds none)
 # translation units of the hooks library only (no product counterpart): kzg_test_arith, the device twin of tests/host_math.cpp
 HOOK_ONLY_SOURCES = ["arith_hooks.hip"]
-SOURCES = ["capi.hip", "runtime.hip", "msm.hip", "srs.hip", "ntt.hip", "poly.hip", "witness.hip", "pairing.hip", "msm_wide.hip", "msm_tail.hip", "mgpu.hip", "g1ntt.hip", "recover.hip", "verify_cosets.hip", "verify_cosets_batch.hip", "verify_eval_batch.hip", "open_eval.hip", "fold.hip", "multiopen.hip", "multi_eval.hip"]
+SOURCES = ["capi.hip", "runtime.hip", "msm.hip", "srs.hip", "ntt.hip", "poly.hip", "witness.hip", "pairing.hip", "msm_wide.hip", "msm_tail.hip", "mgpu.hip", "g1ntt.hip", "recover.hip", "verify_cosets.hip", "verify_cosets_batch.hip", "verify_eval_batch.hip", "open_eval.hip", "fold.hip", "multiopen.hip", "multi_eval.hip", "poly_divide.hip"]
 # per-file extra flags (none at present; out-of-line multiplies for the tail kernels were measured: no gain)
 EXTRA_FLAGS = {}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]

@@ -145,6 +145,7 @@ struct kzg_ctx {
     int opt_multiopen_points_chunk = 0;   // kzg_multiopen_eval_commit: at most this many distinct points per chunk (0 = min(16, 2^22 / d) alone)
     int opt_multi_eval_segment = 0;       // kzg_poly_multi_eval: forced segment length, a power of two >= 8 (0 = planned from n, k, batch)
     int opt_multi_eval_points_chunk = 0;  // kzg_poly_multi_eval: at most this many points per pass (0 = 4096 alone); either option takes the kernels at any k
+    int opt_poly_divide_base = 0;         // kzg_poly_divide: precision the base kernel of the series inverse produces, a power of two <= 64 (0 = 64)
     int opt_host_pairing = 1;          // kzg_verify_cosets_batch, kzg_verify_eval_batch: the one pairing check runs on the calling thread (vcb_finish.h); 0 = in a one-thread kernel
     int opt_fk20_cosets_combine = 0;   // the coset combination of kzg_witness_cosets_*: 0 = Straus (shared doublings), 1 = mul256 per term
     int opt_ntt_kernel = KZG_NTT_KERNEL_DEFAULT;  // 0: three-phase passes (k_ntt_pass1/2); 1: load/store fused into the first/last stage pair (k_ntt_tile); 2: 1 + two butterflies per thread
