@@ -76,6 +76,46 @@ enum {
     KZG_ARITH_FR29_QUOTIENT_THREAD = 22, KZG_ARITH_MULSHOUP29X2 = 23, KZG_ARITH_EMIT = 24,
     KZG_ARITH_NUM_OPS = 25
 };
+/* kzg_test_tower: the device twin of ht_tower_op of tests/host_tower.cpp (kzg_amd/csrc/tower_hooks.hip; both compile the record bodies
+ * of kzg_amd/csrc/tower_hooks.h).  One thread per record, 64 per block, runs the functions of kzg_amd/csrc/tower.h as the verifier
+ * kernels of pairing.hip do: out of line, operands in scratch memory.  Same shape as kzg_test_arith; n <= 4096.  An unknown op, n == 0,
+ * a record size that is not the op's, or a record whose alias / power / np / mask word is out of range returns KZG_ERR_SHAPE before
+ * anything is launched.  Encoding: canonical little-endian, Fq 48 B, Fq2 96 B (c0, c1), Fq12 576 B (the coefficients of w^0..w^5),
+ * G1 affine 96 B, G2 affine 192 B, all zero = the identity; the kernel converts to and from Montgomery form.
+ * `alias` (i32) selects how the call r = op(a, b) is made, on the objects themselves and without a copy:
+ *   0 r distinct, 1 r is a, 2 r is b, 3 a is b (r distinct; the record's b is unused), 4 r, a, b one object; unary ops take 0 or 1.
+ *
+ *  op                          in_rec  out_rec  record (in -> out)
+ *  F2_MUL                       196     96      a, b, alias -> a b
+ *  F2_SQR / F2_INV / F2_MUL_XI  100     96      a, alias -> a^2, 1/a (a != 0), a (1 + u)
+ *  F2_MUL_FQ                    148     96      a, k (Fq), alias -> a k
+ *  F12_MUL                      1156    576     a, b, alias -> a b
+ *  F12_SQR / F12_CYCLOTOMIC_SQR / F12_INV / F12_CONJ / F12_EXP_Z
+ *                               580     576     a, alias -> a^2, a^2 (a cyclotomic), 1/a, a^(q^6), a^z (a cyclotomic, z < 0)
+ *  F12_FROB                     584     576     a, i32 power (1 or 2), alias -> a^(q^power)
+ *  F12_IS_ONE                   576     4       a -> u32 (a == 1)
+ *  F12_MUL_LINE                 864     576     f, lam, cst, P (G1) -> f (cst - lam xP w^2 + yP w^3)
+ *  G2_ADD                       388     192     P, Q, alias -> P + Q (g2_add on Jacobian operands, Z = 1)
+ *  G2_DOUBLE                    196     192     P, alias -> 2 P (g2_dbl)
+ *  G2_MUL                       224     192     P, k (8 x u32) -> [k]P
+ *  G2_ON_CURVE                  192     4       P -> u32
+ *  G2_PRECOMPUTE_LINES          192     13056   Q -> the 68 (lam, cst) pairs of g2_precompute_lines (all zero for the identity)
+ *  MILLER_LOOP                  1160    576     u32 np (1..4), u32 mask (< 2^np), 4 x G1, 4 x G2 -> prod f_{z,Q_i}(P_i); pair i uses
+ *                                               stored lines (computed in the same thread from Q_i) when bit i of mask is set, else
+ *                                               lines on the fly; mask 0 passes no table at all, as k_pairing_check does
+ *  FINAL_EXPONENTIATION         576     576     f -> f^(3 (q^12 - 1)/r)
+ *  PAIRING_PRODUCT_IS_ONE       1160    4       as MILLER_LOOP -> u32 (prod e(P_i, Q_i) == 1)
+ */
+enum {
+    KZG_TOWER_F2_MUL = 0, KZG_TOWER_F2_SQR = 1, KZG_TOWER_F2_INV = 2, KZG_TOWER_F2_MUL_FQ = 3, KZG_TOWER_F2_MUL_XI = 4,
+    KZG_TOWER_F12_MUL = 5, KZG_TOWER_F12_SQR = 6, KZG_TOWER_F12_CYCLOTOMIC_SQR = 7, KZG_TOWER_F12_INV = 8, KZG_TOWER_F12_FROB = 9,
+    KZG_TOWER_F12_CONJ = 10, KZG_TOWER_F12_IS_ONE = 11, KZG_TOWER_F12_EXP_Z = 12, KZG_TOWER_F12_MUL_LINE = 13,
+    KZG_TOWER_G2_ADD = 14, KZG_TOWER_G2_DOUBLE = 15, KZG_TOWER_G2_MUL = 16, KZG_TOWER_G2_ON_CURVE = 17,
+    KZG_TOWER_G2_PRECOMPUTE_LINES = 18, KZG_TOWER_MILLER_LOOP = 19, KZG_TOWER_FINAL_EXPONENTIATION = 20,
+    KZG_TOWER_PAIRING_PRODUCT_IS_ONE = 21,
+    KZG_TOWER_NUM_OPS = 22
+};
+int kzg_test_tower(kzg_ctx *ctx, int op, const void *in, size_t in_rec, size_t n, void *out, size_t out_rec);
 /* the first two stages of kzg_verify_cosets alone (kzg_amd/csrc/verify_cosets.hip).  stage 0, interpolation: in = count x l cell values
  * (sfmt) of the cosets coset_ids -> out = count x l interpolant coefficients (sfmt).  stage 1, fixed-base sum: in = count x l scalars
  * (sfmt; coset_ids unused) -> out = count points sum_j in[k l + j] gs[j], affine Montgomery */

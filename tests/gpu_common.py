@@ -25,7 +25,8 @@ class HooksEngine:
                            "kzg_test_g1_mul": [vp, vp, vp, sz, vp], "kzg_ctx_create": [i32, ctypes.POINTER(vp)],
                            "kzg_ctx_destroy": [vp], "kzg_test_mctx_inject_failure": [vp, i32],
                            "kzg_test_mctx_inject_alloc_failure": [vp], "kzg_test_mctx_inject_stall": [vp, i32],
-                           "kzg_test_arith": [vp, i32, vp, sz, sz, vp, sz]}.items():
+                           "kzg_test_arith": [vp, i32, vp, sz, sz, vp, sz],
+                           "kzg_test_tower": [vp, i32, vp, sz, sz, vp, sz]}.items():
             f = getattr(self.lib, name)
             f.argtypes = args
             f.restype = None if name == "kzg_ctx_destroy" else i32

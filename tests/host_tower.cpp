@@ -1,6 +1,7 @@
 // Host build (g++) of kzg_amd/csrc/tower.h -- the same source hipcc compiles for gfx950 -- so tests/ can check
 // the tower fields, G2 and the pairing against the python oracle without a GPU.  Test infrastructure only.
 #include "../kzg_amd/csrc/tower.h"
+#include "../kzg_amd/csrc/tower_hooks.h"
 using namespace kzg;
 
 static Fq load_fq(const uint8_t *p) {  // canonical little-endian 48 B -> Montgomery
@@ -140,5 +141,38 @@ int ht_pairing_product_is_one(const uint8_t *ps, const uint8_t *qs, int np) {
         Q[i] = load_g2(qs + 192 * i);
     }
     return pairing_product_is_one(P, Q, T, np) ? 1 : 0;
+}
+}
+
+// ---- the host twin of kzg_test_tower (include/kzg_mi355x_test.h): record in, record out, every aliasing form.  The record bodies are
+// kzg_amd/csrc/tower_hooks.h, the very source kzg_amd/csrc/tower_hooks.hip compiles for the device.
+template <int OP>
+static int run_tower_op(int op, const uint32_t *in, uint32_t *out, Fq2 *tabs) {
+    if (op == OP) {
+        tower_record<OP>(in, out, tabs);
+        return 0;
+    }
+    if constexpr (OP + 1 < KZG_TOWER_NUM_OPS) return run_tower_op<OP + 1>(op, in, out, tabs);
+    return 3;
+}
+
+extern "C" {
+// the op's record sizes in bytes; 0 for a known op, 3 (KZG_ERR_SHAPE) otherwise
+int ht_tower_shape(int op, uint32_t *in_rec, uint32_t *out_rec) {
+    if (op < 0 || op >= KZG_TOWER_NUM_OPS) return 3;
+    *in_rec = kTowerShapes[op].in_rec;
+    *out_rec = kTowerShapes[op].out_rec;
+    return 0;
+}
+// one record of `op`; refuses what kzg_test_tower refuses (3 = KZG_ERR_SHAPE)
+int ht_tower_op(int op, const uint8_t *in, uint8_t *out) {
+    if (op < 0 || op >= KZG_TOWER_NUM_OPS) return 3;
+    static uint32_t w[290], o[TT_LINES_WORDS];  // the longest records: MILLER_LOOP in, G2_PRECOMPUTE_LINES out
+    static Fq2 tabs[TT_TABS_PER_RECORD];
+    memcpy(w, in, kTowerShapes[op].in_rec);
+    if (!tower_record_ok(op, w)) return 3;
+    int rc = run_tower_op<0>(op, w, o, tabs);
+    memcpy(out, o, kTowerShapes[op].out_rec);
+    return rc;
 }
 }

@@ -8,6 +8,7 @@ import subprocess
 import pytest
 
 from oracle import kzg_model as M, pairing_model as P
+from tests import tower_vectors as TV
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Q = M.Q
@@ -62,6 +63,32 @@ def rf2(rng):
 
 def rf12(rng):
     return tuple(rf2(rng) for _ in range(6))
+
+
+def test_tower_vector_shapes_match_the_c_table(L):
+    for name in TV.OPS:
+        i, o = ctypes.c_uint32(), ctypes.c_uint32()
+        assert L.ht_tower_shape(TV.OP[name], ctypes.byref(i), ctypes.byref(o)) == 0
+        assert (i.value, o.value) == TV.SHAPES[name], name
+    assert L.ht_tower_shape(len(TV.OPS), ctypes.byref(i), ctypes.byref(o)) == 3
+
+
+@pytest.mark.parametrize("name", TV.OPS)
+def test_tower_vectors_through_the_host_shim(L, name):
+    """The whole vector set of tests/tower_vectors.py, every aliasing form included, through ht_tower_op: the record bodies the GPU
+    test runs through kzg_test_tower, here with the portable multiply.  Validates the vectors and their expected values without a GPU."""
+    results = []
+    for rec, want, _ in TV.vectors(name):
+        o = ctypes.create_string_buffer(len(want))
+        assert L.ht_tower_op(TV.OP[name], rec, o) == 0
+        results.append(o.raw)
+    TV.check(name, results)
+
+
+def test_tower_shim_refuses_records_out_of_contract(L):
+    o = ctypes.create_string_buffer(13056)
+    for name, rec in TV.BAD_RECORDS:
+        assert L.ht_tower_op(TV.OP[name], rec, o) == 3, name
 
 
 def test_fq2_ops(L):
