@@ -335,7 +335,8 @@ int kzg_witness_eval_sharded(kzg_mctx *m, const kzg_msrs *lagrange, const void *
  * Returns KZG_ERR_DEGREE_TOO_LARGE if exp >= 32.  Host-only helper; omega written in sfmt. */
 int kzg_compute_omega(size_t d, size_t *m, uint32_t *exp, void *omega, int sfmt);
 /* In place, natural order in and out: out[i] = sum_j a[j] w^(ij); inverse uses w^-1 and scales by
- * d^-1.  The transform is linear, so data may be in either Fr format (it is preserved). */
+ * d^-1.  The transform is linear, so data may be in either Fr format (it is preserved).  There is no sfmt parameter: a word at or
+ * above r counts as its residue (canonical data under the rule above), and every output word is the residue below r. */
 int kzg_ntt_fr(kzg_ctx *ctx, void *data, uint32_t log_n, int inverse, int flags);
 /* coset_fft / icoset_fft (src/ft.rs:168-178): distribute_powers(g = 7) then fft; ifft then g^-i. */
 int kzg_coset_ntt_fr(kzg_ctx *ctx, void *data, uint32_t log_n, int inverse, int sfmt, int flags);

@@ -322,6 +322,10 @@ extern "C" int kzg_witness_coeff_many(kzg_ctx *ctx, const kzg_srs *srs, const vo
     if (count == 0) return KZG_OK;
     std::vector<Fr> xm(count);
     for (size_t j = 0; j < count; j++) KZG_TRY(host_scalar(ctx, (const uint8_t *)xs + 32 * j, sfmt, &xm[j]));
+    for (size_t j = 0; j < count; j++) {  // the ys are only compared with p(x_j) below; host scalars all the same: < r
+        Fr ym;
+        KZG_TRY(host_scalar(ctx, (const uint8_t *)ys + 32 * j, sfmt, &ym));
+    }
     BatchPipe bp;
     KZG_TRY(batch_begin(ctx, count, count * psz, out, flags, &bp));
     int rc = KZG_OK;
@@ -557,8 +561,9 @@ extern "C" int kzg_quotient_linear(kzg_ctx *ctx, const void *coeffs, size_t n, c
     const int lane = ls.lane;
     KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     KZG_TRY(check_sfmt(ctx, sfmt));
-    Fr xm;
+    Fr xm, ym;
     KZG_TRY(host_scalar(ctx, x, sfmt, &xm));
+    KZG_TRY(host_scalar(ctx, y, sfmt, &ym));  // only compared with p(x) below; a host scalar all the same: < r, before q_out is written
     KZG_TRY(lane_reserve(ctx, lane, stage_bytes(n * 32, flags) * 2 + (n / 2048 + 4) * 64 + 65536));
     hipStream_t st = ctx->lanes[lane].stream;
     const void *d = nullptr;
@@ -1539,8 +1544,9 @@ extern "C" int kzg_witness_coeff(kzg_ctx *ctx, const kzg_srs *srs, const void *c
     KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     KZG_TRY(check_sfmt(ctx, sfmt));
     if (n - 1 > srs->n) return fail(ctx, KZG_ERR_SHAPE, "quotient longer than the SRS (reference: slice index panic)");
-    Fr xm;
+    Fr xm, ym;
     KZG_TRY(host_scalar(ctx, x, sfmt, &xm));
+    KZG_TRY(host_scalar(ctx, y, sfmt, &ym));  // y is only compared with p(x) below, but the rule for host scalars holds for it too: < r
     size_t need = msm_workspace_bytes(srs, n - 1) + stage_bytes(n * 32, flags) + n * 32 + (n / 2048 + 4) * 64 + 65536;
     KZG_TRY(lane_reserve(ctx, lane, need));
     hipStream_t st = ctx->lanes[lane].stream;

@@ -17,11 +17,7 @@ namespace kzg {
 
 constexpr int FOLD_U = 4;  // vectors whose elements a lane has requested before it uses the first
 
-__device__ __forceinline__ Fr fold_residue(Fr f) {  // any value below 2^256 < 3r as a residue below r
-    reduce_once(f);
-    reduce_once(f);
-    return f;
-}
+__device__ __forceinline__ Fr fold_residue(Fr f) { return fr_residue(f); }  // any value below 2^256 < 3r as a residue below r (field.h)
 
 // grid (ceil(d / 256), groups); v: group g at v + g gstride, its vector i at + i d; gammas[g] Montgomery
 __global__ __launch_bounds__(256) void k_fr_fold(const Fr *v, size_t d, size_t t, size_t gstride, const Fr *gammas, int carry, Fr *out) {

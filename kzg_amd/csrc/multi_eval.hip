@@ -61,8 +61,7 @@ struct MeMont {
     static __device__ __forceinline__ Point point(const Fr *xs, const MePoint *, uint32_t i) { return xs[i]; }
     static __device__ __forceinline__ Acc zero() { return Fr::zero(); }
     static __device__ __forceinline__ void put(uint32_t *slot, Fr raw) {
-        reduce_once(raw);  // any value below 2^256 < 3r
-        reduce_once(raw);
+        raw = fr_residue(raw);  // any value below 2^256 < 3r (field.h)
 #pragma unroll
         for (int i = 0; i < W; i++) slot[i] = raw.v[i];
     }

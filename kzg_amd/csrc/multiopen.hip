@@ -20,11 +20,7 @@ namespace kzg {
 
 constexpr int FOLD_U = 4;  // terms whose elements a lane has requested before it uses the first (fold.hip)
 
-__device__ __forceinline__ Fr mo_residue(Fr f) {  // any value below 2^256 < 3r as a residue below r
-    reduce_once(f);
-    reduce_once(f);
-    return f;
-}
+__device__ __forceinline__ Fr mo_residue(Fr f) { return fr_residue(f); }  // any value below 2^256 < 3r as a residue below r (field.h)
 
 // sum_{k0 <= k < k1} weight[k] v[idx[k] d + j] for the lane's j (p = v + j)
 __device__ __forceinline__ Fr mo_terms(const Fr *p, size_t d, const uint32_t *idx, const Fr *weight, size_t k0, size_t k1, Fr acc) {

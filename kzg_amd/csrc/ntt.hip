@@ -773,7 +773,7 @@ __global__ __launch_bounds__(256) void k_ntt_outer(Fr *data, size_t B, const Fr 
     if (j2 >= B) return;
     Fr x[A];
 #pragma unroll
-    for (int j1 = 0; j1 < A; j1++) x[j1] = data[(size_t)j1 * B + j2];
+    for (int j1 = 0; j1 < A; j1++) x[j1] = fr_residue(data[(size_t)j1 * B + j2]);  // caller words >= r count as their residue
     // bit-reversal + DIT stages, twiddles w_A^(j << (LOGA - 1 - s)) by repeated multiplication
     Fr y[A];
 #pragma unroll

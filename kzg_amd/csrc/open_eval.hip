@@ -41,12 +41,7 @@ __global__ __launch_bounds__(256) void k_open_denoms(const Fr *tab, size_t d, Op
 }
 
 // a caller's scalar (any value below 2^256 < 3r in the canonical format) as a residue below r
-__device__ __forceinline__ Fr oe_load(const Fr *p) {
-    Fr f = *p;
-    reduce_once(f);
-    reduce_once(f);
-    return f;
-}
+__device__ __forceinline__ Fr oe_load(const Fr *p) { return fr_residue(*p); }
 
 // the sums of a and of b over the block (256 threads), in every thread
 __device__ __forceinline__ void block_sum2(Fr &a, Fr &b, Fr *sh) {
@@ -99,6 +94,11 @@ __global__ __launch_bounds__(256) void k_open_quotient(const Fr *evals, size_t d
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d) return;
     q[(size_t)b * d + i] = mul(sub(oe_load(evals + (size_t)b * d + i), y[b]), inv[(size_t)u * d + i]);
+}
+
+// y = f_m for a point of the domain: the caller's word taken to its residue (a plain copy would hand a word >= r back as the value)
+__global__ __launch_bounds__(64) void k_open_value_on_domain(const Fr *f_m, Fr *y) {
+    if (threadIdx.x == 0) *y = oe_load(f_m);
 }
 
 // The two evaluation kernels with an indirection (kzg_multiopen_eval_commit): claim b of the launch names its polynomial, vidx[b], and
@@ -212,8 +212,8 @@ int open_eval_fr_run(kzg_ctx *ctx, int lane, const Fr *d_evals, uint32_t log_d, 
     }
     for (size_t b = 0; b < B && rc == KZG_OK; b++) {
         if (!pts[b].on_domain) continue;
-        if (hipMemcpyAsync(d_y + b, d_evals + b * d + pts[b].m, 32, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = fail(ctx, KZG_ERR_HIP, "open_eval: copy of f_m");
-        if (rc == KZG_OK && d_q) rc = quotient_eval_run(ctx, lane, d_evals + b * d, log_d, pts[b].m, sfmt, d_q + b * d);
+        KZG_LAUNCH(ctx, st, "k_open_value_on_domain", k_open_value_on_domain, 1, 64, 0, d_evals + b * d + pts[b].m, d_y + b);
+        if (d_q) rc = quotient_eval_run(ctx, lane, d_evals + b * d, log_d, pts[b].m, sfmt, d_q + b * d);
     }
     ctx->lanes[lane].arena_used = mark;
     return rc;

@@ -300,15 +300,15 @@ __global__ __launch_bounds__(HT) void k_quotient_apply(const Fr *coeffs, size_t 
     Fr29 carry = (t + 1 < HT) ? sh_get<HT>(sh, t + 1) : Hb;
     __syncthreads();
     // the eight quotient coefficients of this thread go back through the tile: whole-line stores.  q_(8t+7) is the carry; each of the
-    // others is a coefficient (canonical: the caller's scalars are) plus a Shoup product made canonical -- one modular addition, and
-    // the next product starts from the sum's limbs.
+    // others is a coefficient (taken to its residue: a caller's canonical scalars may be any 256-bit word, and add wants operands
+    // below r) plus a Shoup product made canonical -- one modular addition, and the next product starts from the sum's limbs.
     Fr out = fr29_canonical(carry);
 #pragma unroll
     for (int k = HE - 1; k >= 0; k--) {
         h_lds[17 * t + 2 * k] = hchunk{out.v[0], out.v[1], out.v[2], out.v[3]};
         h_lds[17 * t + 2 * k + 1] = hchunk{out.v[4], out.v[5], out.v[6], out.v[7]};
         if (k) {
-            out = add(a[k], fr29_pack_canonical(mul_const(carry, c.x)));
+            out = add(fr_residue(a[k]), fr29_pack_canonical(mul_const(carry, c.x)));
             carry = fr29_unpack(out);
         }
     }
@@ -460,7 +460,10 @@ __global__ __launch_bounds__(256) void k_eval_quotient(const Fr *evals, size_t d
     size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     Fr contrib = Fr::zero();
     if (j < d && j != m) {
-        Fr y = evals[m];
+        // Canonical caller data may be any 256-bit word (Montgomery words are < r: a no-op there).  y goes to its residue; f_j may stay
+        // as it is: f_j - y with y < r is below 2^256 without a borrow and in (0, r) after one (sub adds r once), and the product with
+        // wm_inv < r takes any 256-bit operand to a residue below r -- so the element's own load costs no extra instruction.
+        Fr y = fr_residue(evals[m]);
         size_t t = (j + d - m) & (d - 1);
         // q_j = g_j / (w^t - 1) with g_j = (f_j - y) w^-m, and its term of q_m: q_j w^t = g_j (1 + 1 / (w^t - 1)) = g_j + q_j --
         // two products per element and no read of the w^t table (it used to be three and 128 B per element)

@@ -651,6 +651,13 @@ int kzg::witness_coeff_batched_run(kzg_ctx *ctx, const WitnessSink &sink, const 
     if (k == 0) return fail(ctx, KZG_ERR_SHAPE, "no opening points (the reference recurses without bound on an empty slice)");
     if (k > 16384) return fail(ctx, KZG_ERR_SHAPE, "create_witness_batched supports at most 16384 opening points (the interpolation works on a k x k matrix)");
     const int to_m = sfmt == KZG_FR_CANONICAL_LE_32;
+    if (to_m) {  // xs, ys are host scalars: each < r, before memory is touched (to_mont below would take a larger one mod r)
+        for (size_t i = 0; i < 2 * k; i++) {
+            Fr v;
+            memcpy(v.v, (const uint8_t *)(i < k ? xs : ys) + 32 * (i < k ? i : i - k), 32);
+            if (!is_canonical(v)) return fail(ctx, KZG_ERR_SHAPE, "scalar not canonical (>= r)");
+        }
+    }
     hipStream_t st = ctx->lanes[lane].stream;
 
     // ---- k == 1: the reference's interpolant is X + (y - x) (src/polynomial.rs:244-247) -----------
@@ -881,7 +888,8 @@ __global__ __launch_bounds__(256) void k_vec_op(Fr *a, const Fr *b, size_t n, in
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (op == 1) {
-        a[i] = sub(a[i], b[i]);
+        // canonical caller data may be any 256-bit word; sub wants both operands < r
+        a[i] = canonical ? sub(fr_residue(a[i]), fr_residue(b[i])) : sub(a[i], b[i]);
     } else {
         a[i] = canonical ? mul(a[i], to_mont(b[i])) : mul(a[i], b[i]);
     }

@@ -13,6 +13,10 @@ void hm_fr_sub(const uint32_t *a, const uint32_t *b, uint32_t *o) { Fr x, y; mem
 void hm_fr_inv(const uint32_t *a, uint32_t *o) { Fr x; memcpy(x.v, a, 32); Fr z = inv(x); memcpy(o, z.v, 32); }
 void hm_fr_to_mont(const uint32_t *a, uint32_t *o) { Fr x; memcpy(x.v, a, 32); Fr z = to_mont(x); memcpy(o, z.v, 32); }
 void hm_fr_from_mont(const uint32_t *a, uint32_t *o) { Fr x; memcpy(x.v, a, 32); Fr z = from_mont(x); memcpy(o, z.v, 32); }
+void hm_fr_residue(const uint32_t *a, uint32_t *o) { Fr x; memcpy(x.v, a, 32); Fr z = fr_residue(x); memcpy(o, z.v, 32); }
+// what k_vec_op's subtraction does with canonical caller data: any two 256-bit words -> the residue of their difference
+void hm_fr_residue_sub(const uint32_t *a, const uint32_t *b, uint32_t *o) { Fr x, y; memcpy(x.v, a, 32); memcpy(y.v, b, 32);
+    Fr z = sub(fr_residue(x), fr_residue(y)); memcpy(o, z.v, 32); }
 void hm_fr_root_of_unity(uint32_t *o) { Fr z = from_mont(fr_root_of_unity()); memcpy(o, z.v, 32); }
 void hm_g1_generator(uint32_t *o) { G1Affine g = g1_generator(); memcpy(o, &g, 96); }
 // acc(affine a) + b via madd, then via add(xyzz,xyzz), then dbl; all returned affine

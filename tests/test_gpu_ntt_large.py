@@ -10,6 +10,7 @@ import kzg_amd
 from kzg_amd import _lib as L
 from oracle import c_oracle as C
 from oracle import kzg_model as M
+from tests.residue_lift import lift_bytes
 
 pytestmark = pytest.mark.gpu
 R = M.R
@@ -173,7 +174,8 @@ def test_ntt_above_2_24(engine, log_n, full):
     """EvaluationDomain::fft beyond the two-pass range (the reference goes to 2^31, src/ft.rs:55-76): one more four-step level
     (A = 2, 4, 16 columns of 2^24) around the two-pass transform.  2^25 bit-exact against the oracle's FFT; every size: outputs
     against direct Horner evaluation (indices with k mod A != 0 and k / A large: both index components), round trip, and the
-    inverse on its own at a sampled index through the forward identity ifft(x)[i] = fft(x)[(n - i) mod n] / n."""
+    inverse on its own at a sampled index through the forward identity ifft(x)[i] = fft(x)[(n - i) mod n] / n.  2^25 also with every
+    7th input word replaced by another representative of its residue (v + r or v + 2r, tests/residue_lift.py): the same bytes."""
     n = 1 << log_n
     buf = engine.alloc_scalars(n).fill_random(700 + log_n)
     a0 = buf.download()
@@ -181,8 +183,9 @@ def test_ntt_above_2_24(engine, log_n, full):
     _, _, omega = kzg_amd.compute_omega(n)
     idx = [1, (n >> 1) + 3, n - 2] if log_n < 28 else [n - 5]
     got = {i: int.from_bytes(buf.download(1, offset=i), "little") for i in idx}
+    want = C.fft_bytes(a0, log_n) if full else None
     if full:
-        assert buf.download() == C.fft_bytes(a0, log_n)
+        assert buf.download() == want
     for i in idx:
         assert got[i] == C.poly_eval_bytes(a0, n, pow(omega, i, R)), i
     engine.ntt(buf, log_n, inverse=True)
@@ -191,6 +194,11 @@ def test_ntt_above_2_24(engine, log_n, full):
     i = idx[0]
     inv_n = pow(n, -1, R)
     assert int.from_bytes(buf.download(1, offset=(n - i) % n), "little") == got[i] * inv_n % R
+    if full:    # words >= r count as their residue: the outer level's loads (k_ntt_outer) meet caller data before any reduction
+        buf.upload(lift_bytes(a0, "sparse"))
+        engine.ntt(buf, log_n)
+        same = buf.download() == want       # (compared outside the assert: a failure must not render a diff of a gigabyte)
+        assert same, "2^25 with words >= r gives other bytes than their residues"
     buf.free()
 
 

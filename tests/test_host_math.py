@@ -85,6 +85,27 @@ def test_field_ops(L):
     assert call(L.hm_fr_root_of_unity, n=32) == M.FR_ROOT_OF_UNITY
 
 
+def test_fr_residue_any_256_bit_word(L):
+    """fr_residue (field.h): any 256-bit word -> its residue below r by two conditional subtractions (2^256 < 3r), over the edge
+    words of tests/residue_lift.py and random ones; and the subtraction k_vec_op runs on canonical caller data, over every
+    pairing of canonical and lifted operands with a mod r below, above and equal to b mod r (equal: the bytes of 0, not of r)."""
+    from tests import residue_lift as RL
+    rng = random.Random(11)
+    R, TOP = M.R, 1 << 256
+    assert 2 * R < TOP < 3 * R
+    edges = [0, 1, R - 1, R, R + 1, 2 * R - 1, 2 * R, 2 * R + 1, TOP - 1, TOP - 2, RL.T, RL.T + R, 3 * R - TOP, (1 << 255), (1 << 255) - 1]
+    words = edges + [rng.getrandbits(256) for _ in range(300)] + RL.lift(RL.base(rng, 40), "all")
+    for w in words:
+        assert call(L.hm_fr_residue, b(w, 32), n=32) == w % R, hex(w)
+    reps = lambda v: [v + k * R for k in range(3) if v + k * R < TOP]  # noqa: E731
+    pairs = [(0, 0), (5, 3), (3, 5), (0, 5), (R - 1, 0), (0, R - 1), (R - 1, R - 1), (RL.T, RL.T), (1, RL.T), (RL.T, 1)]
+    pairs += [(rng.randrange(R), rng.randrange(R)) for _ in range(40)]
+    for x, y in pairs:
+        for a in reps(x):
+            for c in reps(y):
+                assert call(L.hm_fr_residue_sub, b(a, 32), b(c, 32), n=32) == (x - y) % R, (hex(a), hex(c))
+
+
 def test_g1_ops(L):
     rng = random.Random(4)
     assert pt(L.hm_g1_generator) == C.g1_generator()
