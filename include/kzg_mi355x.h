@@ -13,7 +13,7 @@
  *   - a kzg_ctx is bound to one GPU and is thread-safe.  The reference's blocking calls -- kzg_commit_coeff,
  *     kzg_commit_eval, kzg_msm_g1, kzg_witness_coeff, kzg_witness_coeff_batched, kzg_witness_eval, kzg_verify_poly_coeff /
  *     _eval, kzg_ntt_fr, kzg_coset_ntt_fr, kzg_poly_mul, kzg_poly_divide, kzg_poly_eval, kzg_poly_multi_eval, kzg_interpolate, kzg_quotient_linear / _eval,
- *     kzg_fr_vec_mul / _sub, kzg_divide_by_z_on_coset (KZGProver / KZGProverEvalForm / KZGVerifier are Clone + &self, src/coeff_form.rs:37-124; an
+ *     kzg_point_tree_product, kzg_point_tree_eval, kzg_point_tree_combine, kzg_point_tree_interpolate, kzg_fr_vec_mul / _sub, kzg_divide_by_z_on_coset (KZGProver / KZGProverEvalForm / KZGVerifier are Clone + &self, src/coeff_form.rs:37-124; an
  *     EvaluationDomain is the caller's own) -- run CONCURRENTLY on one ctx: each call leases one of the context's lanes
  *     (option "streams", default and maximum 16), submits its kernels there and waits for its own result only, so N host
  *     threads calling commit() / create_witness_batched() against one resident SRS fill the GPU like kzg_msm_g1_batch does.
@@ -84,6 +84,9 @@ extern "C" {
  *   kzg_interpolate                         k <= 16384 points                (the k x k basis matrix: 8.6 GB there); any batch
  *   kzg_poly_divide                         na <= 2^27 (the product limit of kzg_poly_mul); any nb and batch: dividends go in chunks of
  *                                                                             min(256, max(1, 2^20 / na)); the workspace does not grow with batch
+ *   kzg_point_tree_setup                    1 <= k <= 2^22 points             (the plan holds 32 x (3 log2 K + 1) bytes per point of the padded
+ *                                                                             size K: 9.0 GB at 2^22); kzg_point_tree_eval: n <= 2^28; any batch:
+ *                                                                             chunks of max(1, 2^21 / K) blocks, the workspace does not grow with it
  *   kzg_srs_lagrange_from_monomial_g1       d <= 2^24;  _g2: d <= 1024
  *   kzg_fk20_setup                          log_n <= 22                      (the plan holds 2N points of 224 B: 1.9 GB there)
  *   kzg_fk20_cosets_setup                   log_n <= 22, 1 <= log_l <= log_n (the plan holds 8 x 2N rows of 128 B: 8.6 GB there)
@@ -179,6 +182,8 @@ int kzg_sync(kzg_ctx *ctx);
  *  call on its own kernels where it would take one kzg_poly_eval scan per value (up to 7 values): the same bytes, for A/B and tests,
  * "poly_divide_base" (0 = default, 64; a power of two in 1..64: the coefficients of the power-series inverse kzg_poly_divide's one-workgroup
  *  base kernel produces before Newton doubling takes over; the same bytes, for A/B and for tests that drive several Newton levels at tiny shapes),
+ * "point_tree_leaf" (0 = default, 16; a power of two in 1..16: kzg_point_tree_setup multiplies nodes of up to that many points by its schoolbook
+ *  kernels and the levels above through transforms; read at setup and kept by the plan; the same bytes, for tests that reach many levels at tiny k),
  * "host_pairing" (1 / 0: the one pairing check that ends kzg_verify_cosets_batch / kzg_verify_eval_batch runs on the calling thread -- the same tower code
  *  compiled for the host -- instead of in a one-thread kernel; the same verdict, default 1),
  * "fk20_cosets_combine" (0 = the shared-doubling Straus kernel, default; 1 = one mul256 per term: the same bytes, for comparison),
@@ -765,6 +770,36 @@ int kzg_poly_multi_eval(kzg_ctx *ctx, const void *coeffs, size_t n, size_t batch
  * mirror).  Also KZG_ERR_SHAPE, before `out` is written: k == 0, k > 16384, an x >= r, an unknown format, a NULL context or buffer.
  * batch == 0: KZG_OK.  The basis matrix is built once per call, each value vector costs one k x k matrix-vector product. */
 int kzg_interpolate(kzg_ctx *ctx, const void *xs, const void *ys, size_t k, size_t batch, int sfmt, int flags, void *out);
+/* SubProductTree (src/polynomial.rs:303-365) as a device-resident plan the caller keeps: the sub-product tree of an arbitrary point
+ * set, and on it Polynomial::multi_eval (:229-233), SubProductTree::linear_mod_combination (:347-365), lagrange_interpolation_with_tree
+ * (:237-293) and the product polynomial, each in O(k log^2 k) field products where kzg_poly_multi_eval and kzg_interpolate take
+ * n k and k^2 (which of the two to call: DESIGN.md section 3.4g; nothing is rerouted).
+ * kzg_point_tree_setup: xs = k host scalars in sfmt, each below r (else KZG_ERR_SHAPE), 1 <= k <= 2^22; repeated points are allowed.
+ * Exclusive, like the other *_setup calls.  The plan is immutable afterwards and, like a kzg_srs, usable from any thread and from every
+ * context on the same device.  It holds the tree padded to next_pow2(k) points with dummy points 0, the transforms of its nodes above
+ * the leaf size (option "point_tree_leaf"), the power-series inverse of the reversed root and 1 / M'(x_i).
+ * kzg_point_tree_shape: k, the padded size, the bytes the plan holds in HBM, and distinct = 0 if two points coincide.
+ * kzg_point_tree_product: the k + 1 coefficients of M = prod (X - x_i) (tree.product).
+ * kzg_point_tree_eval: ys_out[b * k + i] = p_b(xs[i]); coeffs is batch x n scalars, stride n; any n >= 1 (n <= 2^28): there is no
+ * xs.len() > degree assertion, polynomials longer than the padded size go through in blocks.  The bytes are those of
+ * kzg_poly_multi_eval on the same inputs.  Where SubProductTree::eval panics on a zero remainder (:342-343: a polynomial that
+ * vanishes on a whole subtree) this call returns the values.
+ * kzg_point_tree_combine: out[b * k + j] = coefficient j of sum_i cs[b * k + i] M / (X - x_i); k coefficients, zero-padded.
+ * kzg_point_tree_interpolate: the bytes of kzg_interpolate: combine of ys[b * k + i] / M'(x_i).  A plan with repeated points gives
+ * KZG_ERR_SHAPE before `out` is written.  k == 1 gives the constant y (the reference's X + (y - x) there is the caller's to mirror).
+ * All four: coefficients, cs and ys may be any 256-bit value and count as their residue; outputs are residues below r in sfmt;
+ * KZG_IN_DEVICE (coeffs / cs / ys) and KZG_OUT_DEVICE as for kzg_poly_multi_eval; batch == 0: KZG_OK, nothing written; a NULL context,
+ * plan or buffer or an unknown format: KZG_ERR_SHAPE before memory is touched.  Blocking, on one leased lane; polynomials / vectors go
+ * in chunks of max(1, 2^21 / padded size) blocks, so the workspace (96 bytes per point of a chunk) does not grow with batch. */
+typedef struct kzg_point_tree kzg_point_tree;
+int kzg_point_tree_setup(kzg_ctx *ctx, const void *xs, size_t k, int sfmt, kzg_point_tree **out);
+void kzg_point_tree_free(kzg_ctx *ctx, kzg_point_tree *plan);
+int kzg_point_tree_shape(const kzg_point_tree *plan, size_t *k, size_t *padded, size_t *bytes, int *distinct);
+int kzg_point_tree_product(kzg_ctx *ctx, const kzg_point_tree *plan, int sfmt, int flags, void *out);
+int kzg_point_tree_eval(kzg_ctx *ctx, const kzg_point_tree *plan, const void *coeffs, size_t n, size_t batch, int sfmt, int flags,
+                        void *ys_out);
+int kzg_point_tree_combine(kzg_ctx *ctx, const kzg_point_tree *plan, const void *cs, size_t batch, int sfmt, int flags, void *out);
+int kzg_point_tree_interpolate(kzg_ctx *ctx, const kzg_point_tree *plan, const void *ys, size_t batch, int sfmt, int flags, void *out);
 /* quotient of create_witness without the MSM: q = (p - y)/(X - x), n-1 scalars, in place allowed.
  * Returns KZG_ERR_POINT_NOT_ON_POLY if the remainder is non-zero. */
 int kzg_quotient_linear(kzg_ctx *ctx, const void *coeffs, size_t n, const void *x, const void *y, int sfmt,

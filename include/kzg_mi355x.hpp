@@ -100,6 +100,7 @@ inline KZGParams setup(const Engine &e, const Scalar &s, size_t num_coeffs, size
     return p;
 }
 
+class PointTree;
 struct Polynomial {  // src/polynomial.rs:24-27
     size_t degree = 0;
     std::vector<Scalar> coeffs;
@@ -130,6 +131,8 @@ struct Polynomial {  // src/polynomial.rs:24-27
     std::vector<Scalar> multi_eval(const Engine &e, const std::vector<Scalar> &xs) const;
     // :266-293; one point: X + (y - x), as the reference returns it
     static Polynomial lagrange_interpolation(const Engine &e, const std::vector<Scalar> &xs, const std::vector<Scalar> &ys);
+    // :237-264 on a PointTree built from xs (below); one point: X + (y - x), as the reference returns it
+    static Polynomial lagrange_interpolation_with_tree(const Engine &e, const std::vector<Scalar> &xs, const std::vector<Scalar> &ys, const PointTree &tree);
     bool is_zero() const { return degree == 0 && coeffs[0].is_zero(); }  // :45-47
     // :193-227: (quotient, Option<remainder>); the remainder is valid iff has_remainder (the reference's Some)
     struct Division;
@@ -212,6 +215,83 @@ inline Polynomial Polynomial::lagrange_interpolation(const Engine &e, const std:
     if (xs.size() != ys.size()) throw ReferencePanic("assert_eq!(xs.len(), ys.len())");
     std::vector<Scalar> c = interpolate(e, xs, ys);
     if (xs.size() != 1) return Polynomial::make(std::move(c));
+    Scalar d = ys[0];  // X + (y - x): the subtraction is the engine's, on one element
+    e.check(kzg_fr_vec_sub(e.ctx(), d.le.data(), xs[0].le.data(), 1, KZG_FR_CANONICAL_LE_32, 0));
+    return Polynomial::new_from_coeffs({d, Scalar::from_u64(1)}, 1);
+}
+
+// SubProductTree (src/polynomial.rs:303-365) as a device-resident plan (kzg_point_tree): built once from a point set, kept by the
+// caller, every method O(k log^2 k).  The engine must outlive the tree.
+class PointTree {
+  public:
+    PointTree(const Engine &e, const std::vector<Scalar> &xs) : e_(&e), k_(xs.size()) {  // new_from_points, :310-327
+        static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+        Scalar none;
+        e.check(kzg_point_tree_setup(e.ctx(), xs.empty() ? &none : xs.data(), xs.size(), KZG_FR_CANONICAL_LE_32, &h_));
+    }
+    static PointTree new_from_points(const Engine &e, const std::vector<Scalar> &xs) { return PointTree(e, xs); }
+    ~PointTree() {
+        if (h_) kzg_point_tree_free(e_->ctx(), h_);
+    }
+    PointTree(const PointTree &) = delete;
+    PointTree &operator=(const PointTree &) = delete;
+    PointTree(PointTree &&o) noexcept : e_(o.e_), h_(o.h_), k_(o.k_) { o.h_ = nullptr; }
+    const kzg_point_tree *handle() const { return h_; }
+    size_t len() const { return k_; }
+    size_t bytes() const {
+        size_t b = 0;
+        kzg_point_tree_shape(h_, nullptr, nullptr, &b, nullptr);
+        return b;
+    }
+    bool distinct() const {
+        int d = 0;
+        kzg_point_tree_shape(h_, nullptr, nullptr, nullptr, &d);
+        return d != 0;
+    }
+    Polynomial product() const {  // tree.product: prod (X - x_i)
+        std::vector<Scalar> c(k_ + 1);
+        e_->check(kzg_point_tree_product(e_->ctx(), h_, KZG_FR_CANONICAL_LE_32, 0, c.data()));
+        return Polynomial::new_from_coeffs(std::move(c), k_);
+    }
+    // ys[b k + i] = p_b(xs[i]) for `batch` polynomials of n coefficients each (coeffs: batch x n scalars back to back)
+    std::vector<Scalar> eval_batch(const std::vector<Scalar> &coeffs, size_t n, size_t batch) const {
+        if (n == 0 || coeffs.size() / n != batch || coeffs.size() != batch * n) throw ReferencePanic("PointTree::eval_batch: shape");
+        std::vector<Scalar> ys(batch * k_);
+        Scalar none;
+        e_->check(kzg_point_tree_eval(e_->ctx(), h_, coeffs.data(), n, batch, KZG_FR_CANONICAL_LE_32, 0, ys.empty() ? &none : ys.data()));
+        return ys;
+    }
+    std::vector<Scalar> eval(const Polynomial &f) const {  // :329-348, without its panic on a zero remainder
+        std::vector<Scalar> c(f.coeffs.begin(), f.coeffs.begin() + f.num_coeffs());
+        return eval_batch(c, c.size(), 1);
+    }
+    Polynomial linear_mod_combination(const std::vector<Scalar> &cs) const {  // :350-364
+        if (cs.size() != k_) throw ReferencePanic("PointTree::linear_mod_combination: one scalar per point");
+        std::vector<Scalar> out(k_);
+        e_->check(kzg_point_tree_combine(e_->ctx(), h_, cs.data(), 1, KZG_FR_CANONICAL_LE_32, 0, out.data()));
+        return Polynomial::make(std::move(out));
+    }
+    // out[b k + j] = coefficient j of the polynomial of degree < k through (xs[i], ys[b k + i]); one point gives the constant
+    std::vector<Scalar> interpolate(const std::vector<Scalar> &ys) const {
+        if (ys.size() % k_) throw ReferencePanic("PointTree::interpolate: shape");
+        std::vector<Scalar> out(ys.size());
+        Scalar none;
+        e_->check(kzg_point_tree_interpolate(e_->ctx(), h_, ys.empty() ? &none : ys.data(), ys.size() / k_, KZG_FR_CANONICAL_LE_32, 0,
+                                             ys.empty() ? &none : out.data()));
+        return out;
+    }
+
+  private:
+    const Engine *e_;
+    kzg_point_tree *h_ = nullptr;
+    size_t k_;
+};
+
+inline Polynomial Polynomial::lagrange_interpolation_with_tree(const Engine &e, const std::vector<Scalar> &xs, const std::vector<Scalar> &ys,
+                                                               const PointTree &tree) {
+    if (xs.size() != ys.size()) throw ReferencePanic("assert_eq!(xs.len(), ys.len())");
+    if (tree.len() != xs.size()) throw ReferencePanic("lagrange_interpolation_with_tree: the tree was built from another point set");
+    if (xs.size() != 1) return Polynomial::make(tree.interpolate(ys));
     Scalar d = ys[0];  // X + (y - x): the subtraction is the engine's, on one element
     e.check(kzg_fr_vec_sub(e.ctx(), d.le.data(), xs[0].le.data(), 1, KZG_FR_CANONICAL_LE_32, 0));
     return Polynomial::new_from_coeffs({d, Scalar::from_u64(1)}, 1);

@@ -161,6 +161,13 @@ def load(path=None):
         "kzg_verify_multiopen": (i32, [vp, vp, vp, vp, vp, i32, vp, sz, ctypes.POINTER(u32), sz, vp, vp, vp, vp, i32, ctypes.POINTER(i32)]),
         "kzg_poly_mul": (i32, [vp, vp, sz, vp, sz, i32, i32, vp]),
         "kzg_poly_divide": (i32, [vp, vp, sz, sz, vp, sz, i32, i32, vp, vp, ctypes.POINTER(i32)]),
+        "kzg_point_tree_setup": (i32, [vp, vp, sz, i32, c_void_pp]),
+        "kzg_point_tree_free": (None, [vp, vp]),
+        "kzg_point_tree_shape": (i32, [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(i32)]),
+        "kzg_point_tree_product": (i32, [vp, vp, i32, i32, vp]),
+        "kzg_point_tree_eval": (i32, [vp, vp, vp, sz, sz, i32, i32, vp]),
+        "kzg_point_tree_combine": (i32, [vp, vp, vp, sz, i32, i32, vp]),
+        "kzg_point_tree_interpolate": (i32, [vp, vp, vp, sz, i32, i32, vp]),
         "kzg_dev_alloc": (i32, [vp, sz, c_void_pp]),
         "kzg_dev_free": (i32, [vp, vp]),
         "kzg_dev_upload": (i32, [vp, vp, vp, sz]),

@@ -299,6 +299,10 @@ class Engine:
         cs = unpack_scalars(out.raw[: 32 * len(rows) * k])
         return [cs[b * k:(b + 1) * k] for b in range(len(rows))] if many else cs
 
+    def point_tree(self, xs):
+        """kzg_point_tree_setup: the reusable sub-product tree of the points xs (ints below R, 1 <= len(xs) <= 2^22) as a PointTree."""
+        return PointTree(self, xs)
+
     def quotient_linear(self, coeffs, x, y):
         blob = pack_scalars(coeffs)
         n = len(blob) // 32
@@ -674,6 +678,115 @@ class Srs:
         if rc:
             _raise(engine, rc)
         return Srs(engine, h)
+
+
+class PointTree:
+    """SubProductTree (src/polynomial.rs:303-365) as a device-resident plan (kzg_point_tree): the sub-product tree of a point set,
+    kept between calls.  Evaluation of polynomials at all its points, linear_mod_combination, interpolation and the product
+    polynomial each take O(k log^2 k) field products."""
+
+    def __init__(self, engine, xs):
+        self.engine, self.handle = engine, None
+        self.xs = [int(x) for x in xs]
+        xb = b"".join(x.to_bytes(32, "little") if 0 <= x < (1 << 256) else pack_scalars([x]) for x in self.xs)
+        h = ctypes.c_void_p()
+        rc = engine.lib.kzg_point_tree_setup(engine.ctx, xb, len(self.xs), L.FR_CANONICAL, ctypes.byref(h))
+        if rc:
+            _raise(engine, rc)
+        self.handle = h
+
+    @staticmethod
+    def new_from_points(engine, xs):  # :310-327
+        return PointTree(engine, xs)
+
+    def shape(self):
+        """(k, padded size, bytes the plan holds in HBM, distinct)."""
+        k, padded, nbytes, distinct = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_int()
+        rc = self.engine.lib.kzg_point_tree_shape(self.handle, ctypes.byref(k), ctypes.byref(padded), ctypes.byref(nbytes), ctypes.byref(distinct))
+        if rc:
+            _raise(self.engine, rc)
+        return k.value, padded.value, nbytes.value, bool(distinct.value)
+
+    def __len__(self):
+        return len(self.xs)
+
+    @property
+    def product(self):
+        """tree.product: M = prod (X - x_i), a Polynomial of degree k."""
+        k = len(self.xs)
+        out = ctypes.create_string_buffer(32 * (k + 1))
+        rc = self.engine.lib.kzg_point_tree_product(self.engine.ctx, self.handle, L.FR_CANONICAL, 0, out)
+        if rc:
+            _raise(self.engine, rc)
+        return Polynomial.new_from_coeffs(unpack_scalars(out.raw), k)
+
+    def eval_batch(self, coeffs, n=None, batch=1, out=None):
+        """kzg_point_tree_eval: the values p_b(xs[i]) of `batch` polynomials of n coefficients each (coeffs: ints, a canonical blob or
+        a DeviceBuffer of batch x n scalars back to back).  Returns a list of `batch` lists of k ints -- one flat list for
+        batch = 1 -- or `out` (a DeviceBuffer of batch x k scalars in the coefficients' format) when one is given."""
+        e = self.engine
+        ptr, nn, sfmt, flags, _keep = e._scalars_arg(coeffs)
+        if n is None:
+            if batch < 1 or nn % batch:
+                raise ReferencePanic("%d scalars are not %d polynomials of equal length" % (nn, batch))
+            n = nn // batch
+        if nn < n * batch:  # the call would read past the buffer
+            raise ReferencePanic("%d scalars given, batch * n = %d" % (nn, batch * n))
+        k = len(self.xs)
+        if out is not None:
+            if out.n < batch * k or out.sfmt != sfmt:
+                raise ReferencePanic("PointTree.eval_batch: out holds %d scalars, batch * k = %d (and has the coefficients' format)" % (out.n, batch * k))
+            rc = e.lib.kzg_point_tree_eval(e.ctx, self.handle, ptr, n, batch, sfmt, flags | L.OUT_DEVICE, out.ptr)
+            if rc:
+                _raise(e, rc)
+            return out
+        buf = ctypes.create_string_buffer(32 * max(batch * k, 1))
+        rc = e.lib.kzg_point_tree_eval(e.ctx, self.handle, ptr, n, batch, sfmt, flags, buf)
+        if rc:
+            _raise(e, rc)
+        ys = [e._scalar_from(buf.raw[32 * j:32 * j + 32], sfmt) for j in range(batch * k)]
+        return ys if batch == 1 else [ys[b * k:(b + 1) * k] for b in range(batch)]
+
+    def eval(self, f):  # :329-348, without its panic on a zero remainder
+        """The values of the Polynomial (or coefficient list) f at the tree's points."""
+        return self.eval_batch(f.slice_coeffs() if isinstance(f, Polynomial) else f)
+
+    def _vectors(self, fn, vs):
+        k = len(self.xs)
+        many = len(vs) > 0 and isinstance(vs[0], (list, tuple))
+        rows = [list(v) for v in vs] if many else [list(vs)]
+        if any(len(v) != k for v in rows):
+            raise ReferencePanic("assert_eq!(xs.len(), ys.len())")
+        out = ctypes.create_string_buffer(32 * max(len(rows) * k, 1))
+        rc = fn(self.engine.ctx, self.handle, pack_scalars([c for v in rows for c in v]), len(rows), L.FR_CANONICAL, 0, out)
+        if rc:
+            _raise(self.engine, rc)
+        cs = unpack_scalars(out.raw[: 32 * len(rows) * k])
+        return [cs[b * k:(b + 1) * k] for b in range(len(rows))] if many else cs
+
+    def linear_mod_combination(self, cs):  # :350-364
+        """sum_i cs[i] M / (X - x_i) as a Polynomial (a list of value vectors gives a list of Polynomials)."""
+        res = self._vectors(self.engine.lib.kzg_point_tree_combine, cs)
+        return [Polynomial(r) for r in res] if res and isinstance(res[0], list) else Polynomial(res)
+
+    def interpolate(self, ys):
+        """kzg_point_tree_interpolate: the k coefficients (lowest first) of the polynomial of degree < k through (xs[i], ys[i]); a list
+        of value vectors gives a list of coefficient lists.  One point gives the constant."""
+        return self._vectors(self.engine.lib.kzg_point_tree_interpolate, ys)
+
+    def close(self):
+        if self.handle:
+            self.engine.lib.kzg_point_tree_free(self.engine.ctx, self.handle)
+            self.handle = None
+
+    free = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 class _Fk20Handle:
@@ -1260,6 +1373,16 @@ class Polynomial:
         if len(xs) == 1:  # :269-272: the reference returns X + (y - x) for one point
             return Polynomial.new_from_coeffs([(int(ys[0]) - int(xs[0])) % R_MODULUS, 1], 1)
         return Polynomial(engine.interpolate(xs, ys))
+
+    @staticmethod
+    def lagrange_interpolation_with_tree(engine, xs, ys, tree):  # :237-264; tree = PointTree.new_from_points(engine, xs)
+        if len(xs) != len(ys):
+            raise ReferencePanic("assert_eq!(xs.len(), ys.len())")
+        if len(xs) == 1:  # :244-247: X + (y - x) for one point
+            return Polynomial.new_from_coeffs([(int(ys[0]) - int(xs[0])) % R_MODULUS, 1], 1)
+        if len(tree) != len(xs):
+            raise ReferencePanic("lagrange_interpolation_with_tree: the tree was built from another point set")
+        return Polynomial(tree.interpolate(ys))
 
     def fft_mul(self, engine, other):  # :167-183 (and best_mul :185-191: the product is the same polynomial)
         coeffs = engine.poly_mul(self.slice_coeffs(), other.slice_coeffs())

@@ -146,7 +146,8 @@ struct kzg_ctx {
     int opt_multi_eval_segment = 0;       // kzg_poly_multi_eval: forced segment length, a power of two >= 8 (0 = planned from n, k, batch)
     int opt_multi_eval_points_chunk = 0;  // kzg_poly_multi_eval: at most this many points per pass (0 = 4096 alone); either option takes the kernels at any k
     int opt_poly_divide_base = 0;         // kzg_poly_divide: precision the base kernel of the series inverse produces, a power of two <= 64 (0 = 64)
-    int opt_host_pairing = 1;          // kzg_verify_cosets_batch, kzg_verify_eval_batch: the one pairing check runs on the calling thread (vcb_finish.h); 0 = in a one-thread kernel
+    int opt_point_tree_leaf = 0;          // kzg_point_tree_setup: nodes of up to this many points are multiplied by the schoolbook kernels, a power of two <= 16 (0 = 16)
+    int opt_host_pairing = 1;         // kzg_verify_cosets_batch, kzg_verify_eval_batch: the one pairing check runs on the calling thread (vcb_finish.h); 0 = in a one-thread kernel
     int opt_fk20_cosets_combine = 0;   // the coset combination of kzg_witness_cosets_*: 0 = Straus (shared doublings), 1 = mul256 per term
     int opt_ntt_kernel = KZG_NTT_KERNEL_DEFAULT;  // 0: three-phase passes (k_ntt_pass1/2); 1: load/store fused into the first/last stage pair (k_ntt_tile); 2: 1 + two butterflies per thread
     int opt_ntt_three_from = 23;       // NTT sizes from 2^this on take three passes of <= 2^8 points (ntt_run3); 0 = never
@@ -479,6 +480,16 @@ int multiopen_gather_run(kzg_ctx *ctx, hipStream_t st, const Fr *d_v, size_t d, 
 // d_g[j] += sum_u (sum_{k in u} d_w[k] d_v[d_idx[k] d + j] - d_Y[u]) d_inv[u d + j]; the claims of point u are [d_pstart[u], d_pstart[u + 1])
 int multiopen_accum_run(kzg_ctx *ctx, hipStream_t st, const Fr *d_v, size_t d, const uint32_t *d_idx, const Fr *d_w, const uint32_t *d_pstart,
                         int nz, const Fr *d_y, Fr *d_Y, const Fr *d_inv, Fr *d_g);
+
+// poly_divide.hip: d_g[0, m) = 1 / f mod X^m (f: fl_all <= m Montgomery coefficients, f[0] != 0) by a schoolbook base of
+// min(base, 64, m) coefficients and Newton doubling through ntt_run.  d_A, d_G: scratch of 2^ilog2_ceil(2 m - 1) elements each; the
+// lane's arena must have ntt_workspace_bytes(ilog2_ceil(2 m - 1)) left.  Behind kzg_poly_divide and kzg_point_tree_setup.
+int series_inverse_run(kzg_ctx *ctx, int lane, const Fr *d_f, size_t fl_all, size_t m, size_t base, Fr *d_g, Fr *d_A, Fr *d_G);
+
+// point_tree.hip: batched transforms of 2^log_t points over `total` contiguous elements (total a multiple of 2^log_t), in place.
+// dit = 0: natural order in, bit-reversed spectrum out (decimation in frequency); dit = 1: bit-reversed in, natural out.  tw is
+// the table w^j, j < 2^(log_tw - 1), of a 2^log_tw-th root w (or of 1 / w), log_tw >= log_t: no scaling is applied.
+int pt_ntt_run(kzg_ctx *ctx, hipStream_t st, Fr *d, size_t total, uint32_t log_t, int dit, const Fr *tw, uint32_t log_tw);
 
 
 }  // namespace kzg

@@ -176,6 +176,29 @@ static int pd_fold_run(kzg_ctx *ctx, hipStream_t st, const Fr *src, size_t len, 
 // transform size of the Newton level k -> hi for a divisor with fl coefficients below X^hi
 static inline size_t pd_newton_size(size_t k, size_t hi, size_t fl) { return pd_pow2(std::max(hi, fl + k - 2)); }
 
+// g[0, m) = 1 / f mod X^m for f of fl_all <= m coefficients, f[0] != 0 (f, g Montgomery): the first min(base, m) coefficients by
+// k_pd_inv_base (base <= PD_BASE), then Newton doubling.  d_A, d_G: scratch of pow2(2 m - 1) elements each; the lane's arena must
+// have ntt_workspace_bytes(ilog2_ceil(2 m - 1)) left.  Shared by kzg_poly_divide and kzg_point_tree_setup.
+int series_inverse_run(kzg_ctx *ctx, int lane, const Fr *d_f, size_t fl_all, size_t m, size_t base, Fr *d_g, Fr *d_A, Fr *d_G) {
+    hipStream_t st = ctx->lanes[lane].stream;
+    size_t k = std::min(std::min(base, (size_t)PD_BASE), m);
+    KZG_LAUNCH(ctx, st, "k_pd_inv_base", k_pd_inv_base, 1, PD_BASE, 0, d_f, (uint32_t)std::min<size_t>(fl_all, PD_BASE), (uint32_t)k, d_g);
+    while (k < m) {  // Newton: F in d_A, G in d_G
+        const size_t hi = std::min(2 * k, m), fl = std::min(hi, fl_all), T = pd_newton_size(k, hi, fl);
+        const uint32_t log_T = (uint32_t)ilog2_ceil(T);
+        const bool sf = ntt_short_input_ok(log_T, fl);
+        KZG_LAUNCH(ctx, st, "k_pd_load", k_pd_load, pd_grid(sf ? fl : T), PD_T, 0, d_f, 0, 0, fl, d_A, sf ? fl : T, 0);
+        KZG_LAUNCH(ctx, st, "k_pd_load", k_pd_load, pd_grid(T), PD_T, 0, d_g, 0, 0, k, d_G, T, 0);
+        KZG_TRY(pd_ntt(ctx, lane, d_A, log_T, 0, sf ? fl : (size_t)-1));
+        KZG_TRY(pd_ntt(ctx, lane, d_G, log_T, 0));
+        KZG_LAUNCH(ctx, st, "k_pd_newton", k_pd_newton, pd_grid(T), PD_T, 0, d_A, d_G, T);
+        KZG_TRY(pd_ntt(ctx, lane, d_G, log_T, 1));
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_g + k, d_G + k, (hi - k) * 32, hipMemcpyDeviceToDevice, st));  // the truncation to hi
+        k = hi;
+    }
+    return KZG_OK;
+}
+
 }  // namespace kzg
 
 using namespace kzg;
@@ -267,21 +290,7 @@ extern "C" int kzg_poly_divide(kzg_ctx *ctx, const void *a, size_t na, size_t ba
         KZG_LAUNCH(ctx, st, "k_pd_inv_base", k_pd_inv_base, 1, PD_BASE, 0, d_f, 1u, 1u, d_f);  // d_f[0] = 1 / b[0]
     } else if (general) {
         const size_t base = ctx->opt_poly_divide_base ? (size_t)ctx->opt_poly_divide_base : (size_t)PD_BASE;
-        size_t k = std::min(base, m);
-        KZG_LAUNCH(ctx, st, "k_pd_inv_base", k_pd_inv_base, 1, PD_BASE, 0, d_f, (uint32_t)std::min<size_t>(fl_all, PD_BASE), (uint32_t)k, d_g);
-        while (k < m) {  // Newton: F in d_A, G in d_G (both free until the quotient stage)
-            const size_t hi = std::min(2 * k, m), fl = std::min(hi, nb), T = pd_newton_size(k, hi, fl);
-            const uint32_t log_T = (uint32_t)ilog2_ceil(T);
-            const bool sf = ntt_short_input_ok(log_T, fl);
-            KZG_LAUNCH(ctx, st, "k_pd_load", k_pd_load, pd_grid(sf ? fl : T), PD_T, 0, d_f, 0, 0, fl, d_A, sf ? fl : T, 0);
-            KZG_LAUNCH(ctx, st, "k_pd_load", k_pd_load, pd_grid(T), PD_T, 0, d_g, 0, 0, k, d_G, T, 0);
-            KZG_TRY(pd_ntt(ctx, lane, d_A, log_T, 0, sf ? fl : (size_t)-1));
-            KZG_TRY(pd_ntt(ctx, lane, d_G, log_T, 0));
-            KZG_LAUNCH(ctx, st, "k_pd_newton", k_pd_newton, pd_grid(T), PD_T, 0, d_A, d_G, T);
-            KZG_TRY(pd_ntt(ctx, lane, d_G, log_T, 1));
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_g + k, d_G + k, (hi - k) * 32, hipMemcpyDeviceToDevice, st));  // the truncation to hi
-            k = hi;
-        }
+        KZG_TRY(series_inverse_run(ctx, lane, d_f, fl_all, m, base, d_g, d_A, d_G));  // (d_A, d_G: free until the quotient stage)
         KZG_LAUNCH(ctx, st, "k_pd_load", k_pd_load, pd_grid(Tq), PD_T, 0, d_g, 0, 0, m, d_G, Tq, 0);
         KZG_TRY(pd_ntt(ctx, lane, d_G, log_tq, 0));
         if (want_r) {

@@ -433,6 +433,9 @@ extern "C" int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value) 
     } else if (k == "poly_divide_base") {
         if (value != 0 && (value < 1 || value > 64 || (value & (value - 1)))) return fail(ctx, KZG_ERR_SHAPE, "poly_divide_base must be 0 (64) or a power of two in 1..64");
         ctx->opt_poly_divide_base = (int)value;
+    } else if (k == "point_tree_leaf") {
+        if (value != 0 && (value < 1 || value > 16 || (value & (value - 1)))) return fail(ctx, KZG_ERR_SHAPE, "point_tree_leaf must be 0 (16) or a power of two in 1..16");
+        ctx->opt_point_tree_leaf = (int)value;
     } else if (k == "ntt_vec_log") {
         if (value < 0 || value > 2) return fail(ctx, KZG_ERR_SHAPE, "ntt_vec_log must be 0..2");
         ctx->opt_ntt_vec_log = (int)value;
