@@ -145,7 +145,13 @@ const char *kzg_version(void);
  * GPU_MAX_HW_QUEUES (>= 18) itself or calls kzg_init_hw_queues(n) (n = 0: 24) BEFORE its first HIP call -- it sets the
  * variable unless the host already did -- or starts with KZG_SET_HW_QUEUES=1 in the environment (the library's load-time
  * constructor then makes that call).  Otherwise the engine measures the queues it has and narrows the pipeline to fit
- * (4 queues: 3 lanes + 1 accumulation stream; loss: INTEGRATION.md section 6). */
+ * (4 queues: 3 lanes + 1 accumulation stream; loss: INTEGRATION.md section 6).  kzg_msm_g1_batch with 17-bit windows and 4-byte
+ * sort records (2^17 .. 2^21 points) does not run as lanes: the MSMs of a batch travel in groups of sixteen (option "group_msms":
+ * 1..16, 0 = lanes), every sort and tail kernel is launched once per group, and one sort stream, one tail stream and two
+ * accumulation streams need four queues only.  Measured at 2^20: 467.7 commitments/s on four queues against 448.3 for the narrowed
+ * lanes and 461.2 for 13 + 4 lanes on 24 queues; the other sizes measured are in profiles/grouped_pipeline_ab.txt (same bytes).
+ * Other sizes and window widths, kzg_witness_*_many, the device group and concurrent blocking callers run
+ * as lanes and do want the queues.  kzg_ctx_info reports the group size (group_msms=<g>, 0 = lanes only). */
 int kzg_init_hw_queues(int queues);
 int kzg_device_count(void);  /* usable HIP devices (0 if none) */
 /* "hip=<file of the HIP runtime this library is bound to> runtime_version=<n> driver_version=<n>": a process may hold two HIP
@@ -165,6 +171,9 @@ int kzg_sync(kzg_ctx *ctx);
  * thread -- the same field code compiled for the host -- instead of one GPU lane; same bytes, ~90 us less latency),
  * "sort_single_pass" (0 / 1: 17-bit windows sorted in one pass instead of two levels; A/B only),
  * "defer_tail" (1 / 0: kzg_msm_g1_batch enqueues a lane's tail kernels after the sort of the lane's next MSM; default 1),
+ * "group_msms" (0..16, default 16: MSMs per sort / tail launch of the grouped shape of kzg_msm_g1_batch, see kzg_init_hw_queues;
+ *  0 = never grouped: lanes; the context's workspace grows to min(batch, 2 x group_msms) MSM workspaces of ~0.3 GB at 2^20 and
+ *  ~0.5 GB at 2^21 -- 9.5 GB / 15.5 GB for a batch of 32 or more at the default, kept until the context is destroyed),
  * "accum_blocks_small" / "accum_streams_small" / "small_entries" (MSMs of at most small_entries sorted entries -- windows x terms,
  *  default 2^21: up to 2^17 points -- inside a pipeline take a 160-block accumulation grid and are spread over 4 accumulation
  *  streams instead of 480 blocks on 2: +20 % at 2^16, +50 % at 2^14; accum_blocks_small = 0 switches the rule off),

@@ -246,11 +246,109 @@ static int batch_end(kzg_ctx *ctx, const BatchPipe &bp, int rc, void *out, size_
     return rc;
 }
 
+// ---- the grouped shape of the batched pipeline (four streams whatever the process' hardware-queue pool: plan_pipeline) ----
+// A lane is a stream and a stream is in order, so 3 lanes hold 3 MSMs in their latency-bound sort and tail kernels -- too few to
+// keep the accumulation queue fed.  Here the MSMs travel in groups of G (option group_msms): every sort kernel and every tail
+// kernel is launched ONCE per group (grid.y = the MSM's slot, msm.hip / msm_wide.hip / msm_tail.hip k_*_g), k_accum_affine stays
+// one launch per MSM, and four streams carry the whole pipeline:
+//     sort stream:  sort(g)  ->  ev sorted     two accumulation FIFO streams (MSMs alternate):  accum(g, i)  ->  ev accumulated
+//     tail stream:  tail(g) + results  ->  ev done;     sort(g + 2) waits for it: group g + 2 re-uses group g's half of the arena.
+// Two groups are in flight.  Ordering is by events only.  Oversized sort bins: a group is sorted with one block per bin (never in
+// slices); a slot that meets one says so in its word of d_lane_heavy, the pick-up at the end of the call notes it in heavy_last, and
+// the following calls keep the per-lane path, slices included, for as long as that note holds (common.h, KZG_HEAVY_WINDOW).
+static bool batch_wants_group(kzg_ctx *ctx, const kzg_srs *srs, size_t n, size_t batch) {
+    if (ctx->plan_group <= 0 || batch < 2 || !msm_group_covers(ctx, srs, n)) return false;
+    // (2^17 points with three or more accumulation streams planned are small MSMs, common.h msm_small: as lanes they take a 160-block
+    // accumulation grid on four streams.  Grouped, with the batch grid on two, they measured 3043 against 2801 commitments/s on 24
+    // queues, profiles/grouped_pipeline_ab.txt (h): no exception for them.)
+    if (ctx->opt_heavy_bins == 1) return false;
+    const uint64_t now = ctx->msm_count.load(std::memory_order_relaxed) + 1, last = ctx->heavy_last.load(std::memory_order_relaxed);
+    return !(ctx->opt_heavy_bins == 0 && last != 0 && now - last <= (uint64_t)KZG_HEAVY_WINDOW);
+}
+
+static int msm_batch_grouped(kzg_ctx *ctx, const BatchPipe &bp, const kzg_srs *srs, size_t offset, const void *scalars, size_t n,
+                             size_t batch, size_t stride_bytes, int sfmt, int flags, size_t psz, int ofmt) {
+    const size_t G = (size_t)ctx->plan_group, ngroups = (batch + G - 1) / G;
+    const size_t ws = align_up(msm_workspace_bytes(srs, n), 256);
+    const size_t per = align_up(ws + stage_bytes(n * 32, flags) + 8192, 4096);
+    const size_t D = KZG_GROUP_DEPTH, nslots = std::min(batch, D * G);  // groups in flight = parts of the group arena
+    hipStream_t s_sort = ctx->lanes[0].stream, s_tail = ctx->lanes[1].stream;
+    hipStream_t s_acc[2] = {ctx->accum_streams[0], bp.nas >= 2 ? ctx->accum_streams[1] : ctx->lanes[2].stream};
+    while (ctx->group_events.size() < 4 * D) {
+        hipEvent_t e = nullptr;
+        KZG_HIP_CHECK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        ctx->group_events.push_back(e);
+    }
+    // per arena half h: [4 h] sorted, [4 h + 1 + a] accumulated on FIFO stream a, [4 h + 3] tail done
+    hipEvent_t *ev = ctx->group_events.data();
+    if (ctx->group_tab_count < batch) {
+        if (ctx->group_tab) hipFree(ctx->group_tab);
+        ctx->group_tab = nullptr;
+        ctx->group_tab_count = 0;
+        KZG_HIP_CHECK(ctx, hipMalloc((void **)&ctx->group_tab, batch * sizeof(GroupSlot)));
+        ctx->group_tab_count = batch;
+    }
+    KZG_TRY(lane_reserve(ctx, 0, nslots * per + 4096));
+    ctx->lanes[0].arena_limit = 0;
+    char *arena = (char *)lane_alloc(ctx, 0, nslots * per);
+    if (!arena) return fail(ctx, KZG_ERR_ALLOC, "group arena not reserved");
+    // the slots' table: MSM b is slot b % G of group b / G, in arena half (b / G) % D
+    std::vector<GroupSlot> tab(batch);
+    for (size_t b = 0; b < batch; b++) {
+        const size_t slot = ((b / G) % D) * G + b % G;
+        GroupSlot &t = tab[b];
+        t.base = arena + slot * per;
+        t.scalars = (flags & KZG_IN_DEVICE) ? (const void *)((const uint8_t *)scalars + b * stride_bytes) : (const void *)(t.base + ws);
+        t.out = bp.d_out + b * psz;
+        t.heavy = ctx->d_lane_heavy + KZG_MAX_LANES + slot;
+    }
+    KZG_HIP_CHECK(ctx, hipMemcpy(ctx->group_tab, tab.data(), batch * sizeof(GroupSlot), hipMemcpyHostToDevice));  // (nothing of the call is in flight yet)
+    const uint32_t seq = ++ctx->group_heavy_seq;
+    ctx->msm_count.fetch_add(batch, std::memory_order_relaxed);
+    auto enqueue = [&]() -> int {
+    for (size_t g = 0; g < ngroups; g++) {
+        const size_t b0 = g * G, cnt = std::min(G, batch - b0), h = g % D;
+        const GroupSlot *d_tab = ctx->group_tab + b0;
+        if (g >= D) KZG_HIP_CHECK(ctx, hipStreamWaitEvent(s_sort, ev[4 * h + 3], 0));  // the half's previous group has left it
+        if (!(flags & KZG_IN_DEVICE))
+            for (size_t i = 0; i < cnt; i++)
+                KZG_HIP_CHECK(ctx, hipMemcpyAsync(tab[b0 + i].base + ws, (const uint8_t *)scalars + (b0 + i) * stride_bytes, n * 32,
+                                                  hipMemcpyHostToDevice, s_sort));
+        KZG_TRY(msm_group_sort(ctx, s_sort, srs, offset, n, sfmt, d_tab, (int)cnt, seq));
+        KZG_HIP_CHECK(ctx, hipEventRecord(ev[4 * h], s_sort));
+        const int na = cnt > 1 ? 2 : 1;
+        for (int a = 0; a < na; a++) KZG_HIP_CHECK(ctx, hipStreamWaitEvent(s_acc[a], ev[4 * h], 0));
+        for (size_t i = 0; i < cnt; i++) KZG_TRY(msm_group_accum(ctx, s_acc[i & 1], srs, n, tab[b0 + i].base));
+        for (int a = 0; a < na; a++) {
+            KZG_HIP_CHECK(ctx, hipEventRecord(ev[4 * h + 1 + a], s_acc[a]));
+            KZG_HIP_CHECK(ctx, hipStreamWaitEvent(s_tail, ev[4 * h + 1 + a], 0));
+        }
+        KZG_TRY(msm_group_tail(ctx, s_tail, srs, n, d_tab, (int)cnt, ofmt));
+        KZG_HIP_CHECK(ctx, hipEventRecord(ev[4 * h + 3], s_tail));
+    }
+    return KZG_OK;
+    };
+    const int rc = enqueue();
+    if (rc != KZG_OK) {  // nothing of a failed call stays queued: batch_end waits for the lanes' streams only
+        for (hipStream_t st : {s_sort, s_acc[0], s_acc[1], s_tail}) hipStreamSynchronize(st);
+        return rc;
+    }
+#if !defined(KZG_TIMING_NO_PICKUP)
+    // the slots' last sorts (common.h heavy_last), as batch_end does for the lanes'.  The tail stream has waited for everything else.
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(s_tail));
+    uint32_t hv[KZG_GROUP_DEPTH * KZG_MAX_GROUP];
+    KZG_HIP_CHECK(ctx, hipMemcpy(hv, ctx->d_lane_heavy + KZG_MAX_LANES, sizeof hv, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < nslots; k++)
+        if (hv[k] == seq) ctx->heavy_last.store(ctx->msm_count.load(std::memory_order_relaxed), std::memory_order_relaxed);
+#endif
+    return KZG_OK;
+}
+
 namespace kzg {
 // kzg_msm_g1_batch with an explicit distance between consecutive scalar vectors (the sharded commit hands every device the
 // slice [lo, hi) of each polynomial: stride = whole-polynomial bytes, n = hi - lo)
 int msm_batch_strided(kzg_ctx *ctx, const kzg_srs *srs, size_t offset, const void *scalars, size_t n, size_t batch,
-                      size_t stride_bytes, int sfmt, int flags, void *out, int ofmt) {
+                      size_t stride_bytes, int sfmt, int flags, void *out, int ofmt, bool may_group) {
     Guard g(ctx);
     KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     KZG_TRY(check_sfmt(ctx, sfmt));
@@ -260,6 +358,8 @@ int msm_batch_strided(kzg_ctx *ctx, const kzg_srs *srs, size_t offset, const voi
     if (batch == 0) return KZG_OK;
     BatchPipe bp;
     KZG_TRY(batch_begin(ctx, batch, batch * psz, out, flags, &bp));
+    if (may_group && batch_wants_group(ctx, srs, n, batch))
+        return batch_end(ctx, bp, msm_batch_grouped(ctx, bp, srs, offset, scalars, n, batch, stride_bytes, sfmt, flags, psz, ofmt), out, batch * psz);
     size_t per = align_up(msm_workspace_bytes(srs, n) + stage_bytes(n * 32, flags) + 8192, 4096);
     int rc = KZG_OK;
     // Software pipelining inside a lane (deep batches on FIFO accumulation streams): MSM b's tail is enqueued AFTER the sort of the
@@ -305,7 +405,7 @@ extern "C" int kzg_msm_g1_batch(kzg_ctx *ctx, const kzg_srs *srs, size_t offset,
                                 size_t batch, int sfmt, int flags, void *out, int ofmt) {
     if (!ctx || !srs || !out || (!scalars && n && batch)) return KZG_ERR_SHAPE;
     if (n > SIZE_MAX / 32) return KZG_ERR_SHAPE;
-    return msm_batch_strided(ctx, srs, offset, scalars, n, batch, n * 32, sfmt, flags, out, ofmt);
+    return msm_batch_strided(ctx, srs, offset, scalars, n, batch, n * 32, sfmt, flags, out, ofmt, true);
 }
 
 extern "C" int kzg_witness_coeff_many(kzg_ctx *ctx, const kzg_srs *srs, const void *coeffs, size_t n, const void *xs,

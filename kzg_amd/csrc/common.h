@@ -99,6 +99,9 @@ struct CtxGate {
 };
 constexpr int KZG_HEAVY_WINDOW = 64;  // MSMs for which one oversized sort bin keeps the slice kernels enqueued (kzg_ctx::heavy_last)
 constexpr int KZG_MAX_LANES = 24;  // lanes.reserve(): leased lanes are indexed while other threads append
+constexpr int KZG_MAX_GROUP = 16;  // MSMs per sort / tail launch of the grouped pipeline, at most (option group_msms)
+constexpr int KZG_GROUP_DEPTH = 2;  // groups in flight = halves of the group arena (three measured no faster at 16 MSMs per group)
+struct GroupSlot;
 
 }  // namespace kzg
 
@@ -184,7 +187,7 @@ struct kzg_ctx {
     int accum_blocks_single() const { return opt_accum_blocks ? opt_accum_blocks : 256 * KZG_ACCUM_WAVES; }
     int accum_blocks_batch() const { return opt_accum_blocks_batch ? opt_accum_blocks_batch : 240 * KZG_ACCUM_WAVES; }
     int num_cus = 256;
-    std::atomic<bool> attr_msm_set{false}, attr_ntt_set{false}, attr_wide_set{false}, attr_sort20_set{false}, attr_horner_set{false};  // > 64 KiB dynamic-LDS opt-in done for this device
+    std::atomic<bool> attr_msm_set{false}, attr_ntt_set{false}, attr_wide_set{false}, attr_sort20_set{false}, attr_horner_set{false}, attr_group_set{false};  // > 64 KiB dynamic-LDS opt-in done for this device
     // profiling
     bool prof = false;
     bool prof_only_accum = false;  // events around k_accum_affine only (bench.py's timed region: two events per kernel launch cost 1.4 % there)
@@ -208,7 +211,15 @@ struct kzg_ctx {
     // the next KZG_HEAVY_WINDOW MSMs after such a pick-up (or option heavy_bins = 1): enqueued for nothing they cost uniform
     // scalars 0.8 % of the batched rate.  Setting the option clears the history.
     std::atomic<uint64_t> msm_count{0}, heavy_last{0};
-    uint32_t *d_lane_heavy = nullptr;
+    uint32_t *d_lane_heavy = nullptr;  // KZG_MAX_LANES words, then one per slot of the grouped pipeline (KZG_GROUP_DEPTH x KZG_MAX_GROUP)
+    // The grouped shape of the batched pipeline (capi.hip, msm_batch_grouped): four streams carry a batch of the MSMs it covers,
+    // whatever the hardware-queue pool of the process.  MSMs per sort / tail launch (option group_msms, 0 = never grouped: lanes).
+    int opt_group_msms = 16;
+    int plan_group = 0;  // group size of the current plan (plan_pipeline), 0 = the plan runs as lanes
+    kzg::GroupSlot *group_tab = nullptr;  // device table, one entry per MSM of the call (grow-only)
+    size_t group_tab_count = 0;
+    std::vector<hipEvent_t> group_events;  // per arena half: sorted, accumulated on either FIFO stream, tail done
+    uint32_t group_heavy_seq = 0;          // calls that took the grouped shape (what their slots' words are compared with)
     void *batch_out = nullptr;  // device staging of kzg_msm_g1_batch results (grow-only)
     size_t batch_out_bytes = 0;
 };
@@ -360,6 +371,20 @@ int msm_run(kzg_ctx *ctx, int lane, const kzg_srs *srs, size_t offset, const voi
             MsmPoint **d_result, hipStream_t accum_stream = nullptr, hipEvent_t sorted_ev = nullptr, hipEvent_t accum_ev = nullptr,
             MsmPending *defer = nullptr);
 int msm_finish(kzg_ctx *ctx, MsmPending &pd, MsmPoint **d_result);  // the deferred part of an MSM (its result if it was not deferred)
+// The grouped shape of the batched pipeline (capi.hip, msm_batch_grouped): the sort kernels of up to KZG_MAX_GROUP MSMs of a batch
+// are ONE launch each, and so are their tail kernels; only k_accum_affine stays one launch per MSM.  A device table with one
+// GroupSlot per MSM, written once per call, tells the kernels where each slot's scalars, workspace and result are.
+struct GroupSlot {
+    const void *scalars;  // the n scalars of the slot's MSM (device)
+    char *base;           // the slot's workspace (msm_workspace_bytes; every intermediate array at its usual offset inside)
+    void *out;            // where the slot's result goes (device)
+    uint32_t *heavy;      // the slot's oversized-bin word (kzg_ctx::d_lane_heavy, behind the lanes' words)
+};
+bool msm_group_covers(const kzg_ctx *ctx, const kzg_srs *srs, size_t n);  // c = 17 window tables, 4-byte sort records, 2^17 points and more
+int msm_group_sort(kzg_ctx *ctx, hipStream_t st, const kzg_srs *srs, size_t offset, size_t n, int sfmt, const GroupSlot *d_tab, int cnt,
+                   uint32_t heavy_seq);
+int msm_group_accum(kzg_ctx *ctx, hipStream_t st, const kzg_srs *srs, size_t n, char *base);  // one slot's k_accum_affine
+int msm_group_tail(kzg_ctx *ctx, hipStream_t st, const kzg_srs *srs, size_t n, const GroupSlot *d_tab, int cnt, int ofmt);  // tail + results
 // runtime.hip: one MSM on a leased lane (its accumulation kernel on the lease's FIFO stream when other calls are in flight)
 int lease_msm(kzg_ctx *ctx, const Lease &ls, const kzg_srs *srs, size_t offset, const void *d_sc, size_t n, int sfmt, MsmPoint **res);
 // d_points: count points -> one point (plain sum)
@@ -378,7 +403,7 @@ int sum_groups_emit(kzg_ctx *ctx, int lane, const MsmPoint *d_pts, size_t count,
 
 // capi.hip
 int msm_batch_strided(kzg_ctx *ctx, const kzg_srs *srs, size_t offset, const void *scalars, size_t n, size_t batch,
-                      size_t stride_bytes, int sfmt, int flags, void *out, int ofmt);
+                      size_t stride_bytes, int sfmt, int flags, void *out, int ofmt, bool may_group = false);  // may_group: kzg_msm_g1_batch (the device group keeps its lanes)
 // out[g] = sum_i points[g * gstride + i * istride] (strides in points); points in pfmt, host or device per flags
 int g1_sum_batch_strided(kzg_ctx *ctx, const void *points, size_t count, size_t groups, size_t gstride, size_t istride, int pfmt,
                          int flags, void *out, int ofmt, int level = POINTS_ON_CURVE);

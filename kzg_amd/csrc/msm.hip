@@ -211,8 +211,10 @@ __global__ __launch_bounds__(1024) void k_scatter(const Fr *scalars, size_t n, i
 // 64th bucket, so k_scan_b needs no cross-block pass for the starts.
 constexpr int BIN_SHIFT = 6, BIN_BUCKETS = 1 << BIN_SHIFT;  // NBINS = 1024 bins (msm_internal.h)
 
-__global__ __launch_bounds__(1024) void k_bin_hist(const Fr *scalars, size_t n, int sfmt, size_t per_block, uint32_t *blk_bins,
-                                                   int w_lo, int w_hi) {
+// (the bodies of the sort kernels are functions of their own: each is a kernel per MSM and, with grid.y = the MSM's slot, a kernel
+// per group of MSMs -- msm_internal.h, GroupSlot)
+__device__ __forceinline__ void bin_hist_body(const Fr *scalars, size_t n, int sfmt, size_t per_block, uint32_t *blk_bins, int w_lo,
+                                              int w_hi) {
     KZG_SIDE_PRIO_STMT;
     __shared__ uint32_t h[NBINS];
     for (int b = threadIdx.x; b < NBINS; b += blockDim.x) h[b] = 0;
@@ -230,12 +232,21 @@ __global__ __launch_bounds__(1024) void k_bin_hist(const Fr *scalars, size_t n, 
     __syncthreads();
     for (int b = threadIdx.x; b < NBINS; b += blockDim.x) blk_bins[(size_t)blockIdx.x * NBINS + b] = h[b];
 }
+__global__ __launch_bounds__(1024) void k_bin_hist(const Fr *scalars, size_t n, int sfmt, size_t per_block, uint32_t *blk_bins,
+                                                   int w_lo, int w_hi) {
+    bin_hist_body(scalars, n, sfmt, per_block, blk_bins, w_lo, w_hi);
+}
+__global__ __launch_bounds__(1024) void k_bin_hist_g(const GroupSlot *tab, GroupSortOff o, size_t n, int sfmt, size_t per_block, int w_lo,
+                                                     int w_hi) {
+    const GroupSlot s = tab[blockIdx.y];
+    bin_hist_body((const Fr *)s.scalars, n, sfmt, per_block, (uint32_t *)(s.base + o.bins), w_lo, w_hi);
+}
 
 // per bin: exclusive scan over the sort blocks' counts (in place) and the bin size.  Block q owns bins [64 q, 64 q + 64); its 16
 // waves each take a slice of the sort blocks (<= 32 counters per thread, loaded in one batch), the slices are chained through LDS.
 constexpr int BIN_SCAN_SLICES = 16, BIN_SCAN_MAXG = 32;
 constexpr int SORT2_MAX_BLOCKS = BIN_SCAN_SLICES * BIN_SCAN_MAXG;  // level-1 sort blocks k_bin_scan can chain (512)
-__global__ __launch_bounds__(1024) void k_bin_scan(uint32_t *blk_bins, int G, uint32_t *bin_total, uint32_t *ready) {
+__device__ __forceinline__ void bin_scan_body(uint32_t *blk_bins, int G, uint32_t *bin_total, uint32_t *ready) {
     KZG_SIDE_PRIO_STMT;
     __shared__ uint32_t part[BIN_SCAN_SLICES][64];
     if (blockIdx.x == 0 && threadIdx.x < SCAN_SEG) ready[threadIdx.x] = 0;  // k_scan_b's chained flag counts
@@ -267,6 +278,13 @@ __global__ __launch_bounds__(1024) void k_bin_scan(uint32_t *blk_bins, int G, ui
         if (k < gs && g0 + k < G) blk_bins[(size_t)(g0 + k) * NBINS + bin] = pre + v[k];
     if (slice == 0) bin_total[bin] = tot;
 }
+__global__ __launch_bounds__(1024) void k_bin_scan(uint32_t *blk_bins, int G, uint32_t *bin_total, uint32_t *ready) {
+    bin_scan_body(blk_bins, G, bin_total, ready);
+}
+__global__ __launch_bounds__(1024) void k_bin_scan_g(const GroupSlot *tab, GroupSortOff o, int G) {
+    char *base = tab[blockIdx.y].base;
+    bin_scan_body((uint32_t *)(base + o.bins), G, (uint32_t *)(base + o.bin_base) + NBINS + 1, (uint32_t *)(base + o.agg) + SCAN_SEG);
+}
 
 
 // Level 1.  A block takes its scalars in chunks of 1024 (one per thread).  Per chunk the <= 15 K records are first sorted by bin
@@ -275,9 +293,9 @@ __global__ __launch_bounds__(1024) void k_bin_scan(uint32_t *blk_bins, int G, ui
 // packed word: bin (10) | low 6 bucket bits (6) | sign (1) | window - w_lo (4) | thread = scalar index in the chunk (10)
 constexpr int BIN_SCATTER_LDS = (3 * NBINS + 16 + 15 * 1024) * 4;
 template <class REC>
-__global__ __launch_bounds__(1024) void k_bin_scatter(const Fr *scalars, size_t n, int sfmt, size_t per_block, const uint32_t *blk_off,
-                                                      const uint32_t *bin_total, uint32_t *bin_base, uint32_t row_stride,
-                                                      uint32_t idx_base, typename REC::T *rec, int w_lo, int w_hi) {
+__device__ __forceinline__ void bin_scatter_body(const Fr *scalars, size_t n, int sfmt, size_t per_block, const uint32_t *blk_off,
+                                                 const uint32_t *bin_total, uint32_t *bin_base, uint32_t row_stride, uint32_t idx_base,
+                                                 typename REC::T *rec, int w_lo, int w_hi) {
     KZG_SIDE_PRIO_STMT;
     uint32_t *cur = lds_u32, *cnt = cur + NBINS, *off = cnt + NBINS, *wsum = off + NBINS, *stage = wsum + 16;
     const uint32_t tid = threadIdx.x;
@@ -325,6 +343,20 @@ __global__ __launch_bounds__(1024) void k_bin_scatter(const Fr *scalars, size_t 
         __syncthreads();
         cur[tid] += cnt[tid];
     }
+}
+template <class REC>
+__global__ __launch_bounds__(1024) void k_bin_scatter(const Fr *scalars, size_t n, int sfmt, size_t per_block, const uint32_t *blk_off,
+                                                      const uint32_t *bin_total, uint32_t *bin_base, uint32_t row_stride,
+                                                      uint32_t idx_base, typename REC::T *rec, int w_lo, int w_hi) {
+    bin_scatter_body<REC>(scalars, n, sfmt, per_block, blk_off, bin_total, bin_base, row_stride, idx_base, rec, w_lo, w_hi);
+}
+template <class REC>
+__global__ __launch_bounds__(1024) void k_bin_scatter_g(const GroupSlot *tab, GroupSortOff o, size_t n, int sfmt, size_t per_block,
+                                                        uint32_t row_stride, uint32_t idx_base, int w_lo, int w_hi) {
+    const GroupSlot s = tab[blockIdx.y];
+    uint32_t *bin_base = (uint32_t *)(s.base + o.bin_base);
+    bin_scatter_body<REC>((const Fr *)s.scalars, n, sfmt, per_block, (const uint32_t *)(s.base + o.bins), bin_base + NBINS + 1, bin_base,
+                          row_stride, idx_base, (typename REC::T *)(s.base + o.rec), w_lo, w_hi);
 }
 
 // ---- positional tables: width-18 NAF digits (kzg_srs::naf) ----------------------------------------------------------------
@@ -431,9 +463,8 @@ __global__ __launch_bounds__(1024) void k_bin_scatter_naf(const uint32_t *recs, 
 // each bucket's share of a chunk is one run of stores) lives in msm_wide.hip with the handling of oversized bins: sort2_level2.
 
 // k_scan_b for the two-level sort: block j's first bucket starts at bin_base[4 j], M = bin_base[NBINS]
-__global__ __launch_bounds__(SCAN_SEG) void k_scan_b_bins(const uint32_t *total, const uint32_t *bin_base, int B, int NB,
-                                                          uint32_t *bucket_start, uint32_t *s1, MsmState *st, uint32_t slots,
-                                                          uint32_t *ready) {
+__device__ __forceinline__ void scan_b_bins_body(const uint32_t *total, const uint32_t *bin_base, int B, int NB, uint32_t *bucket_start,
+                                                 uint32_t *s1, MsmState *st, uint32_t slots, uint32_t *ready) {
     KZG_SIDE_PRIO_STMT;
     __shared__ uint32_t lds[4];
     const uint32_t M = bin_base[NBINS];
@@ -469,6 +500,17 @@ __global__ __launch_bounds__(SCAN_SEG) void k_scan_b_bins(const uint32_t *total,
         st->ntasks = (M + E - 1) / E;
         st->ovf_tasks = 0;
     }
+}
+__global__ __launch_bounds__(SCAN_SEG) void k_scan_b_bins(const uint32_t *total, const uint32_t *bin_base, int B, int NB,
+                                                          uint32_t *bucket_start, uint32_t *s1, MsmState *st, uint32_t slots,
+                                                          uint32_t *ready) {
+    scan_b_bins_body(total, bin_base, B, NB, bucket_start, s1, st, slots, ready);
+}
+// (a block waits for the flags of the blocks before it in ITS slot's row of the grid only: they were dispatched earlier)
+__global__ __launch_bounds__(SCAN_SEG) void k_scan_b_bins_g(const GroupSlot *tab, GroupSortOff o, int B, int NB, uint32_t slots) {
+    char *base = tab[blockIdx.y].base;
+    scan_b_bins_body((const uint32_t *)(base + o.total), (const uint32_t *)(base + o.bin_base), B, NB, (uint32_t *)(base + o.bucket_start),
+                     (uint32_t *)(base + o.s1), (MsmState *)(base + o.state), slots, (uint32_t *)(base + o.agg) + SCAN_SEG);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -614,6 +656,14 @@ __global__ __launch_bounds__(64) void k_emit_points(const MsmPoint *pts, size_t 
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     emit_one(pts[i * stride_pts], out + i * format_bytes_dev(fmt), fmt);
+}
+
+// the results of a group of MSMs: thread i takes slot i (one lane each: the Fq inversion of to_affine is a chain)
+__global__ __launch_bounds__(64) void k_emit_points_g(const GroupSlot *tab, int cnt, size_t off_result, int fmt) {
+    KZG_SIDE_PRIO_STMT;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    emit_one(*(const MsmPoint *)(tab[i].base + off_result), (uint8_t *)tab[i].out, fmt);
 }
 
 // out[g] = sum_{i < count} pts[g * gstride + i * istride]   (count is small: one partial per GPU)
@@ -1088,6 +1138,59 @@ int msm_run(kzg_ctx *ctx, int lane, const kzg_srs *srs, size_t offset, const voi
         return fail(ctx, KZG_ERR_SHAPE, "SRS too large for the 31-bit entry index (table rows * points < 2^31)");
     if (srs->naf && offset + n > srs->npad) return fail(ctx, KZG_ERR_SHAPE, "MSM range exceeds the SRS");
     return msm_run_narrow(ctx, lane, srs, offset, d_scalars, n, sfmt, d_result, accum_stream, sorted_ev, accum_ev, defer);
+}
+
+// ---- the grouped shape (common.h, GroupSlot): msm_run_narrow's c = 17 / Rec4 branch for `cnt` MSMs of one size at once ----------
+bool msm_group_covers(const kzg_ctx *ctx, const kzg_srs *srs, size_t n) {
+    return srs->device == ctx->device && srs->narrow17 && !srs->naf && !srs->sort20 && !ctx->opt_sort_single && srs->rows == srs->W &&
+           (uint64_t)srs->rows * srs->npad < REC4_MAX_INDEX && n >= ((size_t)1 << 17) && n <= srs->n;
+}
+
+// the shape every grouped MSM runs in: batch-sized accumulation grid, lane-time tail (set_lane_mode(pipelined, deep))
+static uint32_t group_slots(const kzg_ctx *ctx) { return (uint32_t)ctx->accum_blocks_batch() * 256u; }
+
+int msm_group_sort(kzg_ctx *ctx, hipStream_t st, const kzg_srs *srs, size_t offset, size_t n, int sfmt, const GroupSlot *d_tab, int cnt,
+                   uint32_t heavy_seq) {
+    if (cnt < 1 || cnt > KZG_MAX_GROUP || !msm_group_covers(ctx, srs, n) || offset > srs->n - n)
+        return fail(ctx, KZG_ERR_INTERNAL, "grouped MSM outside its scope");
+    if (!ctx->attr_group_set) {
+        KZG_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)k_bin_scatter_g<Rec4>, hipFuncAttributeMaxDynamicSharedMemorySize, BIN_SCATTER_LDS));
+        ctx->attr_group_set = true;
+    }
+    const MsmLayout L = msm_layout(srs, n);
+    const GroupSortOff o = {L.off_bins, L.off_bin_base, L.off_blk_hist, L.off_agg, L.off_total, L.off_bucket_start, L.off_s1, L.off_state,
+                            L.off_entries};
+    const int G2 = L.G2, W = srs->W;
+    const size_t per2 = (n + G2 - 1) / G2;
+    const uint32_t slots = group_slots(ctx);
+    KZG_LAUNCH(ctx, st, "k_bin_hist", k_bin_hist_g, dim3(G2, cnt), 1024, 0, d_tab, o, n, sfmt, per2, 0, W);
+    KZG_LAUNCH(ctx, st, "k_bin_scan", k_bin_scan_g, dim3(NBINS / 64, cnt), 1024, 0, d_tab, o, G2);
+    KZG_LAUNCH(ctx, st, "k_bin_scatter", k_bin_scatter_g<Rec4>, dim3(G2, cnt), 1024, BIN_SCATTER_LDS, d_tab, o, n, sfmt, per2,
+               (uint32_t)srs->npad, (uint32_t)offset, 0, W);
+    KZG_TRY(sort2_level2_group(ctx, st, d_tab, cnt, o, slots, heavy_seq));
+    KZG_LAUNCH(ctx, st, "k_scan_b_bins", k_scan_b_bins_g, dim3(L.B / SCAN_SEG, cnt), SCAN_SEG, 0, d_tab, o, L.B, L.B / SCAN_SEG, slots);
+    return KZG_OK;
+}
+
+int msm_group_accum(kzg_ctx *ctx, hipStream_t st, const kzg_srs *srs, size_t n, char *base) {
+    const MsmLayout L = msm_layout(srs, n);
+    const uint32_t slots = group_slots(ctx);
+    const size_t thr1 = L.M_max / KZG_ACCUM_MIN_CHUNK + 1 < (size_t)slots ? L.M_max / KZG_ACCUM_MIN_CHUNK + 1 : (size_t)slots;
+    KZG_LAUNCH(ctx, st, "k_accum_affine", k_accum_affine, (unsigned)((thr1 + 255) / 256), 256, 0, (const uint32_t *)(base + L.off_entries),
+               (const uint32_t *)(base + L.off_bucket_start), (const uint32_t *)(base + L.off_s1), L.B, (const uint4 *)srs->table30,
+               (MsmPoint *)(base + L.off_bufA), (MsmState *)(base + L.off_state));
+    return KZG_OK;
+}
+
+int msm_group_tail(kzg_ctx *ctx, hipStream_t st, const kzg_srs *srs, size_t n, const GroupSlot *d_tab, int cnt, int ofmt) {
+    if (!point_format_bytes(ofmt)) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 output format");
+    const MsmLayout L = msm_layout(srs, n);
+    const GroupTailOff o = {L.off_bufA, L.off_bufB, L.off_s1, L.off_state, L.off_tail + L.tail.off_dense, L.off_tail + L.tail.off_rows,
+                            L.off_tail + L.tail.off_cols, L.off_tail + L.tail.off_Q, L.off_tail + L.tail.off_tasks,
+                            L.off_tail + L.tail.off_arrive, L.off_tail + L.tail.off_result};
+    KZG_TRY(msm_tail_run_group(ctx, st, d_tab, cnt, o, L.B, expected_partials(L.M_max, group_slots(ctx), L.B)));
+    KZG_LAUNCH(ctx, st, "k_emit_points", k_emit_points_g, (cnt + 63) / 64, 64, 0, d_tab, cnt, o.result, ofmt);
+    return KZG_OK;
 }
 
 }  // namespace kzg

@@ -85,6 +85,24 @@ struct TailLayout {
     size_t off_dense, off_rows, off_cols, off_Q, off_tasks, off_arrive, off_result, bytes;
 };
 TailLayout tail_layout(int B, size_t T1_max);
+
+// ---- grouped launches (the grouped shape of the batched pipeline: capi.hip, msm_batch_grouped) -------------------------------
+// The sort and tail kernels of up to KZG_MAX_GROUP MSMs of one batch (same SRS, same n, hence the same workspace layout) go out as
+// ONE launch each: grid.y = the MSM's slot in its group, and the kernel (k_*_g: the same body as its per-MSM twin) takes the slot's
+// pointers from a device table of GroupSlot that the host writes once per call.  Every intermediate array keeps its place in the
+// slot's own workspace, so the arrays get their leading group-slot dimension through GroupSlot::base (common.h).
+struct GroupSortOff {  // MsmLayout offsets the sort kernels use
+    size_t bins, bin_base, rec, agg, total, bucket_start, s1, state, entries;
+};
+struct GroupTailOff {  // partial lists, equal-split layout and state, then the TailLayout arrays
+    size_t part, scratch, s1, state, dense, rows, cols, Q, tasks, arrive, result;
+};
+// msm_wide.hip: level 2 of the c = 17 / Rec4 sort for `cnt` slots, every bin by its own block (the slice kernels are not enqueued)
+int sort2_level2_group(kzg_ctx *ctx, hipStream_t st, const GroupSlot *d_tab, int cnt, const GroupSortOff &o, uint32_t slots,
+                       uint32_t heavy_seq);
+// msm_tail.hip: msm_tail_run (throughput form) for `cnt` slots; the results stay in the slots' workspaces (GroupTailOff::result)
+int msm_tail_run_group(kzg_ctx *ctx, hipStream_t st, const GroupSlot *d_tab, int cnt, const GroupTailOff &o, int B,
+                       size_t expected_partials);
 int msm_tail_run(kzg_ctx *ctx, hipStream_t st, const MsmMode &mode, const MsmPoint *part, MsmPoint *scratch, const uint32_t *s1, int B,
                  size_t expected_partials, MsmState *state, char *tail_base, const TailLayout &L, MsmPoint **d_result,
                  bool odd_weights = false);

@@ -74,9 +74,11 @@ __device__ __forceinline__ MsmPoint wave_sum(const MsmPoint *p, uint32_t lo, uin
     return butterfly_sum<64>(acc);
 }
 
+// (every kernel of the throughput form is a body function with two kernels around it: one per MSM, and one per group of MSMs with
+// grid.y = the MSM's slot -- msm_internal.h, GroupSlot / GroupTailOff)
 template <int G>
-__global__ KZG_TAIL_LB void k_fold_dense(const MsmPoint *part, const uint32_t *s1, int B, MsmPoint *dense, MsmState *st,
-                                                    uint32_t *tasks, uint32_t *arrive) {
+__device__ __forceinline__ void fold_dense_body(const MsmPoint *part, const uint32_t *s1, int B, MsmPoint *dense, MsmState *st,
+                                                uint32_t *tasks, uint32_t *arrive) {
     KZG_SIDE_PRIO_STMT;
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t b = gid / G, g = gid % G;
@@ -96,9 +98,20 @@ __global__ KZG_TAIL_LB void k_fold_dense(const MsmPoint *part, const uint32_t *s
     acc = butterfly_sum<G>(acc);
     if (g == 0) dense[b] = acc;
 }
+template <int G>
+__global__ KZG_TAIL_LB void k_fold_dense(const MsmPoint *part, const uint32_t *s1, int B, MsmPoint *dense, MsmState *st,
+                                                    uint32_t *tasks, uint32_t *arrive) {
+    fold_dense_body<G>(part, s1, B, dense, st, tasks, arrive);
+}
+template <int G>
+__global__ KZG_TAIL_LB void k_fold_dense_g(const GroupSlot *tab, GroupTailOff o, int B) {
+    char *base = tab[blockIdx.y].base;
+    fold_dense_body<G>((const MsmPoint *)(base + o.part), (const uint32_t *)(base + o.s1), B, (MsmPoint *)(base + o.dense),
+                       (MsmState *)(base + o.state), (uint32_t *)(base + o.tasks), (uint32_t *)(base + o.arrive));
+}
 
-__global__ KZG_TAIL_LB void k_fold_overflow(const MsmPoint *part, MsmPoint *scratch, const uint32_t *s1, MsmPoint *dense,
-                                                       const MsmState *st, const uint32_t *tasks, uint32_t *arrive) {
+__device__ __forceinline__ void fold_overflow_body(const MsmPoint *part, MsmPoint *scratch, const uint32_t *s1, MsmPoint *dense,
+                                                   const MsmState *st, const uint32_t *tasks, uint32_t *arrive) {
     KZG_SIDE_PRIO_STMT;
     const uint32_t T = st->ovf_tasks;
     if (T == 0) return;
@@ -126,6 +139,16 @@ __global__ KZG_TAIL_LB void k_fold_overflow(const MsmPoint *part, MsmPoint *scra
         }
     }
 }
+__global__ KZG_TAIL_LB void k_fold_overflow(const MsmPoint *part, MsmPoint *scratch, const uint32_t *s1, MsmPoint *dense,
+                                                       const MsmState *st, const uint32_t *tasks, uint32_t *arrive) {
+    fold_overflow_body(part, scratch, s1, dense, st, tasks, arrive);
+}
+__global__ KZG_TAIL_LB void k_fold_overflow_g(const GroupSlot *tab, GroupTailOff o) {
+    char *base = tab[blockIdx.y].base;
+    fold_overflow_body((const MsmPoint *)(base + o.part), (MsmPoint *)(base + o.scratch), (const uint32_t *)(base + o.s1),
+                       (MsmPoint *)(base + o.dense), (const MsmState *)(base + o.state), (const uint32_t *)(base + o.tasks),
+                       (uint32_t *)(base + o.arrive));
+}
 
 __global__ KZG_TAIL_LB void k_rc_sums(const MsmPoint *dense, int Rn, int Cn, MsmPoint *rows, MsmPoint *cols) {
     KZG_SIDE_PRIO_STMT;
@@ -148,7 +171,7 @@ __global__ KZG_TAIL_LB void k_rc_sums(const MsmPoint *dense, int Rn, int Cn, Msm
 // column sum, each adding Cn / RC_LANES points in sequence before a log2(RC_LANES)-level butterfly -- 35 wave-additions per 8
 // sums instead of 72 (a butterfly level costs a full addition for half the useful work of the level before).
 constexpr int RC_LANES = 8;
-__global__ KZG_TAIL_LB void k_rc_sums_t(const MsmPoint *dense, int Rn, int Cn, MsmPoint *rows, MsmPoint *cols) {
+__device__ __forceinline__ void rc_sums_t_body(const MsmPoint *dense, int Rn, int Cn, MsmPoint *rows, MsmPoint *cols) {
     KZG_SIDE_PRIO_STMT;
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
     const int sum = gid / RC_LANES, l = gid % RC_LANES;
@@ -166,9 +189,16 @@ __global__ KZG_TAIL_LB void k_rc_sums_t(const MsmPoint *dense, int Rn, int Cn, M
     acc = butterfly_sum<RC_LANES>(acc);
     if (l == 0) (sum < Rn ? rows[sum] : cols[sum - Rn]) = acc;
 }
+__global__ KZG_TAIL_LB void k_rc_sums_t(const MsmPoint *dense, int Rn, int Cn, MsmPoint *rows, MsmPoint *cols) {
+    rc_sums_t_body(dense, Rn, Cn, rows, cols);
+}
+__global__ KZG_TAIL_LB void k_rc_sums_t_g(const GroupSlot *tab, GroupTailOff o, int Rn, int Cn) {
+    char *base = tab[blockIdx.y].base;
+    rc_sums_t_body((const MsmPoint *)(base + o.dense), Rn, Cn, (MsmPoint *)(base + o.rows), (MsmPoint *)(base + o.cols));
+}
 
 // Q[j] (j < lr): sum of rows whose index has bit j set; Q[lr + j] (j < lc): the same for the columns; Q[lr + lc]: all columns
-__global__ KZG_TAIL_LB void k_weighted_bits(const MsmPoint *rows, const MsmPoint *cols, int lr, int lc, MsmPoint *Q) {
+__device__ __forceinline__ void weighted_bits_body(const MsmPoint *rows, const MsmPoint *cols, int lr, int lc, MsmPoint *Q) {
     KZG_SIDE_PRIO_STMT;
     const int lane = threadIdx.x & 63;
     const int wv = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
@@ -188,12 +218,19 @@ __global__ KZG_TAIL_LB void k_weighted_bits(const MsmPoint *rows, const MsmPoint
     acc = butterfly_sum<64>(acc);
     if (lane == 0) Q[wv] = acc;
 }
+__global__ KZG_TAIL_LB void k_weighted_bits(const MsmPoint *rows, const MsmPoint *cols, int lr, int lc, MsmPoint *Q) {
+    weighted_bits_body(rows, cols, lr, lc, Q);
+}
+__global__ KZG_TAIL_LB void k_weighted_bits_g(const GroupSlot *tab, GroupTailOff o, int lr, int lc) {
+    char *base = tab[blockIdx.y].base;
+    weighted_bits_body((const MsmPoint *)(base + o.rows), (const MsmPoint *)(base + o.cols), lr, lc, (MsmPoint *)(base + o.Q));
+}
 
 // result = sum_{j < lr} 2^(j + lc) Q[j] + sum_{j < lc} 2^j Q[lr + j] + Q[lr + lc]        (lr + lc + 1 <= 32 lanes)
 //        = sum_b b B_b + sum_b B_b = sum_b (b + 1) B_b.
 // odd (positional tables: bucket b holds the digits of magnitude 2 b + 1): 2 sum_b b B_b + sum_b B_b -- every bit slice one
 // doubling more, the plain total as it is.
-__global__ __launch_bounds__(64) void k_reduce_final(const MsmPoint *Q, int lr, int lc, MsmPoint *result, int odd) {
+__device__ __forceinline__ void reduce_final_body(const MsmPoint *Q, int lr, int lc, MsmPoint *result, int odd) {
     KZG_SIDE_PRIO_STMT;
     const int lane = threadIdx.x;
     const int cnt = lr + lc + 1;
@@ -204,6 +241,13 @@ __global__ __launch_bounds__(64) void k_reduce_final(const MsmPoint *Q, int lr, 
         if (k < shift && lane < cnt) p = g1_dbl30(p);
     p = butterfly_sum<32>(p);
     if (lane == 0) *result = p;
+}
+__global__ __launch_bounds__(64) void k_reduce_final(const MsmPoint *Q, int lr, int lc, MsmPoint *result, int odd) {
+    reduce_final_body(Q, lr, lc, result, odd);
+}
+__global__ __launch_bounds__(64) void k_reduce_final_g(const GroupSlot *tab, GroupTailOff o, int lr, int lc) {
+    char *base = tab[blockIdx.y].base;
+    reduce_final_body((const MsmPoint *)(base + o.Q), lr, lc, (MsmPoint *)(base + o.result), 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -441,6 +485,32 @@ int msm_tail_run(kzg_ctx *ctx, hipStream_t st, const MsmMode &mode, const MsmPoi
         KZG_LAUNCH(ctx, st, "k_reduce_final", k_reduce_final, 1, 64, 0, Q, lr, lc, result, odd_weights ? 1 : 0);
     }
     *d_result = result;
+    return KZG_OK;
+}
+
+// msm_tail_run with mode.tail_wide for the `cnt` slots of a group (c = 17: 256 x 256 buckets, window tables: no odd weights)
+int msm_tail_run_group(kzg_ctx *ctx, hipStream_t st, const GroupSlot *d_tab, int cnt, const GroupTailOff &o, int B,
+                       size_t expected_partials) {
+    int Rn, Cn, lr, lc;
+    tail_shape(B, &Rn, &Cn, &lr, &lc);
+    if (Rn < RC_LANES || Cn < RC_LANES) return fail(ctx, KZG_ERR_INTERNAL, "grouped tail: bucket count");
+    const size_t avg = expected_partials / (size_t)B + 1;
+    int G = 1;
+    while (G < 64 && (size_t)G * (FOLD_SEQ / 2) < avg) G *= 2;
+    const int wpb = TAIL_THREADS / 64;
+    const unsigned grid = (unsigned)(((size_t)B * G + TAIL_THREADS - 1) / TAIL_THREADS);
+#define KZG_FOLD(GG)                                                                                              \
+    case GG:                                                                                                      \
+        KZG_LAUNCH(ctx, st, "k_fold_dense", k_fold_dense_g<GG>, dim3(grid, cnt), TAIL_THREADS, 0, d_tab, o, B); \
+        break;
+    switch (G) {
+        KZG_FOLD(1) KZG_FOLD(2) KZG_FOLD(4) KZG_FOLD(8) KZG_FOLD(16) KZG_FOLD(32) KZG_FOLD(64)
+    }
+#undef KZG_FOLD
+    KZG_LAUNCH(ctx, st, "k_fold_overflow", k_fold_overflow_g, dim3(256, cnt), TAIL_THREADS, 0, d_tab, o);
+    KZG_LAUNCH(ctx, st, "k_rc_sums", k_rc_sums_t_g, dim3(((Rn + Cn) * RC_LANES + 255) / 256, cnt), 256, 0, d_tab, o, Rn, Cn);
+    KZG_LAUNCH(ctx, st, "k_weighted_bits", k_weighted_bits_g, dim3((lr + lc + 1 + wpb - 1) / wpb, cnt), TAIL_THREADS, 0, d_tab, o, lr, lc);
+    KZG_LAUNCH(ctx, st, "k_reduce_final", k_reduce_final_g, dim3(1, cnt), 64, 0, d_tab, o, lr, lc);
     return KZG_OK;
 }
 

@@ -436,9 +436,9 @@ __device__ __forceinline__ uint32_t heavy_slice_len(uint32_t M) {
 __device__ __forceinline__ uint32_t heavy_slices(uint32_t size, uint32_t SL) { return size > 4 * SL ? (size + SL - 1) / SL : 0u; }
 
 template <class REC, int NB>
-__global__ __launch_bounds__(SORT2_THREADS) void k_bin_sort2(const typename REC::T *rec, const uint32_t *bin_base, uint32_t *entries,
-                                                             uint32_t *total, uint32_t *bucket_start, MsmState *st, uint32_t slots,
-                                                             int sliced, uint32_t *lane_heavy, uint32_t heavy_seq) {
+__device__ __forceinline__ void bin_sort2_body(const typename REC::T *rec, const uint32_t *bin_base, uint32_t *entries, uint32_t *total,
+                                               uint32_t *bucket_start, MsmState *st, uint32_t slots, int sliced, uint32_t *lane_heavy,
+                                               uint32_t heavy_seq) {
     typedef typename REC::T RT;
     __shared__ uint32_t h[NB], cur[NB], off[NB], sc[4];
     __shared__ RT stage[SORT2_CHUNK];
@@ -468,6 +468,19 @@ __global__ __launch_bounds__(SORT2_THREADS) void k_bin_sort2(const typename REC:
         if (bucket_start) bucket_start[(size_t)blockIdx.x * NB + k] = start;
     }
     sort2_place_range<REC, NB>(rec, r0, r1, entries, h, cur, off, sc, stage);
+}
+template <class REC, int NB>
+__global__ __launch_bounds__(SORT2_THREADS) void k_bin_sort2(const typename REC::T *rec, const uint32_t *bin_base, uint32_t *entries,
+                                                             uint32_t *total, uint32_t *bucket_start, MsmState *st, uint32_t slots,
+                                                             int sliced, uint32_t *lane_heavy, uint32_t heavy_seq) {
+    bin_sort2_body<REC, NB>(rec, bin_base, entries, total, bucket_start, st, slots, sliced, lane_heavy, heavy_seq);
+}
+// a group of MSMs (msm_internal.h, GroupSlot): grid.y = the slot; c = 17 only (sizes -> total[]), never sliced
+template <class REC, int NB>
+__global__ __launch_bounds__(SORT2_THREADS) void k_bin_sort2_g(const GroupSlot *tab, GroupSortOff o, uint32_t slots, uint32_t heavy_seq) {
+    const GroupSlot s = tab[blockIdx.y];
+    bin_sort2_body<REC, NB>((const typename REC::T *)(s.base + o.rec), (const uint32_t *)(s.base + o.bin_base),
+                            (uint32_t *)(s.base + o.entries), (uint32_t *)(s.base + o.total), nullptr, nullptr, slots, 0, s.heavy, heavy_seq);
 }
 
 // the heavy bin that owns slice `id` (< hv[0]): the last bin whose first slice is <= id (bins that are not heavy share their
@@ -633,6 +646,12 @@ int sort2_level2(kzg_ctx *ctx, hipStream_t st, int kind, const void *rec, const 
     if (kind == 4) return sort2_level2_t<Rec4, 64>(ctx, st, rec, bin_base, hv, entries, total, bucket_start, nullptr, slots, sliced, lane_heavy, heavy_seq);
     if (kind == 8) return sort2_level2_t<Rec8, 64>(ctx, st, rec, bin_base, hv, entries, total, bucket_start, nullptr, slots, sliced, lane_heavy, heavy_seq);
     return sort2_level2_t<Rec20, SORT20_BUCKETS>(ctx, st, rec, bin_base, hv, entries, nullptr, bucket_start, state, slots, sliced, lane_heavy, heavy_seq);
+}
+
+int sort2_level2_group(kzg_ctx *ctx, hipStream_t st, const GroupSlot *d_tab, int cnt, const GroupSortOff &o, uint32_t slots,
+                       uint32_t heavy_seq) {
+    KZG_LAUNCH(ctx, st, "k_bin_sort", (k_bin_sort2_g<Rec4, 64>), dim3(NBINS, cnt), SORT2_THREADS, 0, d_tab, o, slots, heavy_seq);
+    return KZG_OK;
 }
 
 int sort20_place(kzg_ctx *ctx, hipStream_t st, const void *d_scalars, size_t n, int sfmt, int G2, const uint32_t *bins,

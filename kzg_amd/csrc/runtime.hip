@@ -121,7 +121,8 @@ extern "C" const char *kzg_version(void) { return "kzg-mi355x 0.1.0 (gfx950)"; }
 // touch the host's environment on its own: the host either exports GPU_MAX_HW_QUEUES itself, or calls kzg_init_hw_queues()
 // before its first HIP call, or sets KZG_SET_HW_QUEUES=<n> to let the load-time constructor below do it.  Without any of these
 // the pipeline measures the queues it has (probe_queues) and narrows itself (4 queues: 3 lanes + 1 accumulation stream; loss
-// in INTEGRATION.md section 6, profiles/r03_hw_queues.txt).
+// in INTEGRATION.md section 6, profiles/r03_hw_queues.txt).  Batches the grouped shape covers (plan_pipeline below) need four queues
+// only and run grouped either way (profiles/grouped_pipeline_ab.txt).
 extern "C" int kzg_init_hw_queues(int queues) {
     if (queues < 0 || queues > 64) return KZG_ERR_SHAPE;
     char buf[16];
@@ -148,17 +149,17 @@ extern "C" int kzg_runtime_info(char *buf, size_t buflen) {
     return KZG_OK;
 }
 
-// "device=<d> lanes=<n> accum_streams=<m> hw_queues_found=<q> narrowed_from=<L>+<A>|none witness_cache_slots=<s>": the batched
-// pipeline's current plan (all zero before the first batched / concurrent call) and whether the process' hardware-queue pool forced
-// it below what was asked for.
+// "device=<d> lanes=<n> accum_streams=<m> hw_queues_found=<q> narrowed_from=<L>+<A>|none witness_cache_slots=<s> group_msms=<g>": the
+// batched pipeline's current plan (all zero before the first batched / concurrent call), whether the process' hardware-queue pool
+// forced it below what was asked for, and the group size batches the grouped shape covers run with instead of the lanes (0: none do).
 extern "C" int kzg_ctx_info(kzg_ctx *ctx, char *buf, size_t buflen) {
     if (!ctx || !buf || !buflen) return KZG_ERR_SHAPE;
     Guard g(ctx);
     char nf[32] = "none";
     if (ctx->plan_lanes < ctx->plan_want_lanes || ctx->plan_accum < ctx->plan_want_accum)
         snprintf(nf, sizeof nf, "%d+%d", ctx->plan_want_lanes, ctx->plan_want_accum);
-    snprintf(buf, buflen, "device=%d lanes=%d accum_streams=%d hw_queues_found=%d narrowed_from=%s witness_cache_slots=%d", ctx->device,
-             ctx->plan_lanes, ctx->plan_accum, ctx->plan_queues, nf, ctx->opt_witness_cache_slots);
+    snprintf(buf, buflen, "device=%d lanes=%d accum_streams=%d hw_queues_found=%d narrowed_from=%s witness_cache_slots=%d group_msms=%d", ctx->device,
+             ctx->plan_lanes, ctx->plan_accum, ctx->plan_queues, nf, ctx->opt_witness_cache_slots, ctx->plan_group);
     return KZG_OK;
 }
 
@@ -264,8 +265,8 @@ extern "C" int kzg_ctx_create(int device, kzg_ctx **out) {
         delete ctx;
         return KZG_ERR_HIP;
     }
-    if (hipMalloc((void **)&ctx->d_lane_heavy, KZG_MAX_LANES * 4) != hipSuccess ||
-        hipMemset(ctx->d_lane_heavy, 0, KZG_MAX_LANES * 4) != hipSuccess) {
+    const size_t heavy_bytes = (KZG_MAX_LANES + KZG_GROUP_DEPTH * KZG_MAX_GROUP) * 4;  // the lanes' words, then the grouped pipeline's slots'
+    if (hipMalloc((void **)&ctx->d_lane_heavy, heavy_bytes) != hipSuccess || hipMemset(ctx->d_lane_heavy, 0, heavy_bytes) != hipSuccess) {
         if (ctx->d_lane_heavy) hipFree(ctx->d_lane_heavy);
         pool_unref(ctx->pool);
         delete ctx;
@@ -297,6 +298,8 @@ extern "C" void kzg_ctx_destroy(kzg_ctx *ctx) {
     for (auto e : ctx->event_pool) hipEventDestroy(e);
     for (auto e : ctx->sorted_events) hipEventDestroy(e);
     for (auto e : ctx->accum_events) hipEventDestroy(e);
+    for (auto e : ctx->group_events) hipEventDestroy(e);
+    if (ctx->group_tab) hipFree(ctx->group_tab);
     if (ctx->batch_out) hipFree(ctx->batch_out);
     if (ctx->d_lane_heavy) hipFree(ctx->d_lane_heavy);
     for (auto &ct : ctx->coset_tabs)
@@ -388,6 +391,9 @@ extern "C" int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value) 
         if (value < 0 || value > 64) return fail(ctx, KZG_ERR_SHAPE, "hw_queues must be 0 (GPU_MAX_HW_QUEUES or the ROCm default of 4) or 1..64");
         ctx->opt_hw_queues = (int)value;
         ctx->pipe_planned = false;
+    } else if (k == "group_msms") {
+        if (value < 0 || value > KZG_MAX_GROUP) return fail(ctx, KZG_ERR_SHAPE, "group_msms must be 0 (never grouped) or 1..16 MSMs per sort / tail launch");
+        ctx->opt_group_msms = (int)value;
     } else if (k == "window_rows") {
         if (value < 0 || value > 64) return fail(ctx, KZG_ERR_SHAPE, "window_rows must be 0 (one table row per window) or 1..64");
         ctx->opt_window_rows = (int)value;
@@ -779,7 +785,19 @@ int kzg::plan_pipeline(kzg_ctx *ctx, int want, int *nl_out, int *nas_out) {
             ctx->pipe_planned = false;  // the lease plan (below) re-derives itself from the new order
         }
     }
-    if (getenv("KZG_DEBUG")) fprintf(stderr, "kzg: pipeline plan: %d lanes + %d accumulation streams\n", nl, nas);
+    // A batch of MSMs the grouped shape covers does not run as `nl` lanes at all: its MSMs travel in groups of opt_group_msms
+    // through ONE sort stream and ONE tail stream (every sort / tail kernel launched once per group) beside two accumulation FIFO
+    // streams, so four hardware queues suffice (capi.hip, msm_batch_grouped; which batches: batch_wants_group).  Measured against the
+    // lanes at 2^20: +4.3 % on four queues (3 lanes + 1 accumulation stream), +2.1 % on 24 (13 + 4); other sizes:
+    // profiles/grouped_pipeline_ab.txt.  It takes four of the streams planned above: two lanes and two accumulation streams, or three
+    // lanes and the one accumulation stream.
+    const int plan_group = nl >= 2 && (nas >= 2 || (nas == 1 && nl >= 3)) ? ctx->opt_group_msms : 0;
+    if (getenv("KZG_DEBUG")) {
+        if (plan_group)
+            fprintf(stderr, "kzg: pipeline plan: %d lanes + %d accumulation streams; batches the grouped shape covers: groups of %d on 4 streams\n", nl, nas, plan_group);
+        else
+            fprintf(stderr, "kzg: pipeline plan: %d lanes + %d accumulation streams\n", nl, nas);
+    }
     if (want > 1) {
         ctx->plan_want_lanes = want_nl, ctx->plan_want_accum = want_nas, ctx->plan_lanes = nl, ctx->plan_accum = nas, ctx->plan_queues = found_queues;
         if ((nl < want_nl || nas < want_nas) && !ctx->plan_warned) {
@@ -787,10 +805,13 @@ int kzg::plan_pipeline(kzg_ctx *ctx, int want, int *nl_out, int *nas_out) {
             ctx->plan_warned = true;
             fprintf(stderr, "kzg: device %d: this context's %d + %d streams found only %d hardware queues of their own (other streams of the "
                             "process hold the rest: another context, an RCCL communicator, the host's); the batched pipeline is narrowed to %d "
-                            "lanes + %d accumulation streams -- expect 10-25 %% less batched throughput from THIS context.  Create contexts before "
+                            "lanes + %d accumulation streams -- expect 10-25 %% less throughput from THIS context for concurrent blocking callers, "
+                            "the *_many calls and batches outside the grouped shape%s.  Create contexts before "
                             "communicators, give the process more queues (kzg_init_hw_queues / GPU_MAX_HW_QUEUES before the first HIP call) or set "
                             "option \"streams\" explicitly; kzg_ctx_info reports the plan.\n",
-                    ctx->device, want_nl, want_nas, found_queues, nl, nas);
+                    ctx->device, want_nl, want_nas, found_queues, nl, nas,
+                    plan_group ? " (kzg_msm_g1_batch with 17-bit windows from 2^17 points on runs grouped on four streams and does not need the queues)"
+                               : "");
         }
     }
     KZG_TRY(ensure_lanes(ctx, nl));
@@ -802,6 +823,7 @@ int kzg::plan_pipeline(kzg_ctx *ctx, int want, int *nl_out, int *nas_out) {
         ctx->accum_events.push_back(e2);
     }
     ctx->planned_accum = nas;
+    ctx->plan_group = plan_group;
     *nl_out = nl;
     *nas_out = nas;
     return KZG_OK;
