@@ -96,7 +96,11 @@ extern "C" {
  *                                                                             beside one chunk's buffers and 32 B per commitment
  *   kzg_verify_eval_batch                   any count: the same three bucket sets beside one chunk's buffers (16,384 openings), and
  *                                                                             32 B per commitment when indices are given
- *   MSM                                     table rows x points < 2^31       (the sorted entry is a 31-bit table index + sign);
+ *   kzg_witness_coeff_tree                  the plan's 1 <= k <= 2^22, n <= 2^27 (the division's), n - k <= the SRS; any batch: chunks of
+ *                                                                             min(16, max(1, 2^24 / max(n, K))) polynomials, the workspace does not grow with it
+ *   kzg_msm_g2_bucket                       any n the SRS holds: the workspace is 16 x 32 x 128 buckets of 288 B (18.9 MB) beside the
+ *                                                                             staged scalars (32 B per term)
+ *   MSM                                     table rows x points < 2^31      (the sorted entry is a 31-bit table index + sign);
  *                                           window_bits 18, 19 (option), and 20 with option sort_single_pass: windows x points < 2^27
  *   kzg_g1_sum_batch                        count <= 2^20, groups <= 2^24
  *   kzg_commit_coeff_sharded_batch          batch <= 2^20
@@ -193,6 +197,9 @@ int kzg_sync(kzg_ctx *ctx);
  *  base kernel produces before Newton doubling takes over; the same bytes, for A/B and for tests that drive several Newton levels at tiny shapes),
  * "point_tree_leaf" (0 = default, 16; a power of two in 1..16: kzg_point_tree_setup multiplies nodes of up to that many points by its schoolbook
  *  kernels and the levels above through transforms; read at setup and kept by the plan; the same bytes, for tests that reach many levels at tiny k),
+ * "g2_msm_slice" (0 = default, 2048; a power of two in 1..2048: the points one workgroup of kzg_msm_g2_bucket sorts by digit) and
+ *  "g2_msm_slots" (0 = default, 16; 1..16: the slice slots of its bucket arena, so a chunk is slots x slice points); read per call; the same
+ *  bytes, for tests that put slice and chunk boundaries at single-digit n,
  * "host_pairing" (1 / 0: the one pairing check that ends kzg_verify_cosets_batch / kzg_verify_eval_batch runs on the calling thread -- the same tower code
  *  compiled for the host -- instead of in a one-thread kernel; the same verdict, default 1),
  * "fk20_cosets_combine" (0 = the shared-doubling Straus kernel, default; 1 = one mul256 per term: the same bytes, for comparison),
@@ -616,6 +623,17 @@ void kzg_srs_g2_free(kzg_ctx *ctx, kzg_srs_g2 *srs);
  * verifier's small n (one thread per term). */
 int kzg_msm_g2(kzg_ctx *ctx, const kzg_srs_g2 *srs, size_t offset, const void *scalars, size_t n, int sfmt, void *out,
                int ofmt);
+/* The same sum by the bucket method, for large n (not a reference method; the G2 counterpart of the variable-base sum behind
+ * kzg_verify_cosets_batch): signed 8-bit windows, slices of S points (option "g2_msm_slice") sorted by |digit| in LDS, one owner
+ * thread per (slice slot, window, bucket) adding its list with mixed additions, chunk after chunk of "g2_msm_slots" x S points into
+ * one arena of fixed size; then the slots are folded, every window reduced by a suffix scan and a tree sum, and one Horner chain over
+ * the 32 windows ends in an affine point on the device.  A term costs 32 mixed additions instead of ~380 point operations.  The
+ * result is a group element, so `out` holds the bytes kzg_msm_g2 writes for the same inputs, in any KZG_G2_* format.  scalars: host,
+ * or device with KZG_IN_DEVICE, in either format; a canonical value >= r counts as its residue.  n == 0 gives the identity.
+ * KZG_ERR_SHAPE before `out` is touched: the range exceeds the SRS, an unknown format, a NULL argument, an SRS of another GPU.  Takes
+ * the context exclusively, like the other verifier-side calls.  DESIGN.md section 3.6b says from which n on it is the faster call. */
+int kzg_msm_g2_bucket(kzg_ctx *ctx, const kzg_srs_g2 *srs, size_t offset, const void *scalars, size_t n, int sfmt, int flags,
+                      void *out, int ofmt);
 /* ok[c] = (prod_{i < pairs_per_check} e(g1[c*ppc + i], g2[c*ppc + i]) == 1), 1 <= pairs_per_check <= 4. */
 int kzg_pairing_check(kzg_ctx *ctx, const void *g1_points, int pfmt1, const void *g2_points, int pfmt2,
                       size_t pairs_per_check, size_t checks, uint8_t *ok);
@@ -630,6 +648,35 @@ int kzg_verify_eval(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const
 int kzg_verify_eval_batched(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *xs, size_t k,
                             const void *r_coeffs, size_t r_len, int sfmt, const void *commitment, const void *witness,
                             int pfmt, int *ok);
+struct kzg_point_tree; /* (the typedef is with kzg_point_tree_setup below) */
+/* KZGProver::create_witness_batched (src/coeff_form.rs:83-111) for callers who hold a kzg_point_tree of the opening points, without that
+ * call's bound of 16384 points: `batch` polynomials (coeffs: batch x n scalars, stride n) opened at the plan's k points.  With M the
+ * plan's product and p_b = q_b M + r_b, deg r_b < k:  out_w[b] = [q_b]_1 in ofmt;  out_r[b k + j] (optional) = coefficient j of r_b, the
+ * interpolant through (x_i, p_b(x_i)), zero-padded to k scalars in sfmt.  KZG_IN_DEVICE applies to coeffs and ys, KZG_OUT_DEVICE to out_w
+ * and out_r.  M stays on the device; quotient and remainder come from the division stages of kzg_poly_divide with the power-series
+ * inverse of rev(M) computed once per call; the quotients of a chunk of min(16, max(1, 2^24 / max(n, K))) polynomials go to the batched
+ * MSM pipeline without leaving HBM, so the workspace (allocated and freed by the call) does not grow with batch.
+ * ys (optional, batch x k claimed values): the claim of polynomial b holds iff r_b equals the tree interpolation of ys_b, compared on
+ * the device; status (optional, batch ints) receives 0 or KZG_ERR_POINT_NOT_ON_POLY per polynomial and the call returns KZG_OK; without
+ * status the call returns KZG_ERR_POINT_NOT_ON_POLY if any claim fails.  Every witness and every remainder is still written (the rule
+ * of kzg_witness_coeff_many).  n <= k: the witness is the identity and r is p zero-padded.  k == 1: r is the constant p(x_0) (the
+ * reference's X + (y - x) is for the mirrors, as for kzg_point_tree_interpolate).
+ * KZG_ERR_SHAPE before any output is written: n == 0, n > 2^27, n - k > kzg_srs_len(srs), a plan with repeated points, a plan or an
+ * SRS of another GPU, a NULL srs, plan, coeffs or out_w, an unknown format.  batch == 0: KZG_OK.  out_w and out_r hold the bytes of
+ * kzg_witness_coeff_batched for every (p, xs) that call accepts with k >= 2.  The Fr stage of a chunk takes the context exclusively. */
+int kzg_witness_coeff_tree(kzg_ctx *ctx, const kzg_srs *srs, const struct kzg_point_tree *plan, const void *coeffs, size_t n, size_t batch,
+                           const void *ys, int sfmt, int flags, void *out_w, int ofmt, void *out_r, int *status);
+/* The check of kzg_verify_eval_batched for callers who hold a kzg_point_tree of the opening points (kzg_point_tree_setup), without that
+ * call's bound of 16384 points: `count` openings at ONE point set, tuple c = (commitments[c], witnesses[c], r_c) with r_c =
+ * r_coeffs[c k .. c k + k), the remainder zero-padded to the plan's k coefficients.  hz = [M(tau)]_2 = MSM(hs[0 .. k], M) from the plan's
+ * product by the bucket method of kzg_msm_g2_bucket, ONCE per call and on the device; gr_c = MSM(gs[0 .. k), r_c), the `count` sums one
+ * after the other on one stream, each remainder staged from host memory (the pairing checks then run side by side);
+ * ok[c] = e(w_c, hz) == e(C_c - gr_c, hs[0]), one GPU thread per check.  All inputs in host memory; points are validated as in
+ * kzg_verify_eval (KZG_ERR_BAD_POINT, ok untouched).  KZG_ERR_SHAPE: k + 1 > len(hs), k > len(gs), a NULL buffer (also at count == 0), a
+ * Jacobian point format, an unknown format, a plan with repeated points, a plan or an SRS of another GPU.  For k <= 16384 the verdicts are
+ * those of kzg_verify_eval_batched on the same inputs.  Takes the context exclusively. */
+int kzg_verify_eval_tree(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const struct kzg_point_tree *plan, const void *r_coeffs, int sfmt,
+                         const void *commitments, const void *witnesses, int pfmt, size_t count, uint8_t *ok);
 /* KZGVerifierEvalForm::verify_eval_all (src/eval_form.rs:192-217) exactly as written there. */
 int kzg_verify_eval_all(kzg_ctx *ctx, const kzg_srs *lagrange_g, const kzg_srs_g2 *lagrange_h, const kzg_srs_g2 *hs,
                         const void *ys, size_t ys_len, int sfmt, const void *commitment, const void *witness, int pfmt,

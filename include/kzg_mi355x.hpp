@@ -100,6 +100,20 @@ inline KZGParams setup(const Engine &e, const Scalar &s, size_t num_coeffs, size
     return p;
 }
 
+// sum scalars[i] * hs[offset + i] by the bucket method (kzg_msm_g2_bucket): the affine Montgomery bytes kzg_msm_g2 gives
+struct G2Affine {
+    std::array<uint8_t, 192> bytes{};  // blst_p2_affine; identity = all zero
+    bool operator==(const G2Affine &o) const { return bytes == o.bytes; }
+};
+inline G2Affine msm_g2_bucket(const Engine &e, const kzg_srs_g2 *hs, const std::vector<Scalar> &scalars, size_t offset = 0) {
+    if (!hs) throw ReferencePanic("KZGParams.hs is empty (index out of bounds)");
+    G2Affine out;
+    Scalar none;
+    e.check(kzg_msm_g2_bucket(e.ctx(), hs, offset, scalars.empty() ? &none : scalars.data(), scalars.size(), KZG_FR_CANONICAL_LE_32, 0,
+                              out.bytes.data(), KZG_G2_AFFINE_MONT_192));
+    return out;
+}
+
 class PointTree;
 struct Polynomial {  // src/polynomial.rs:24-27
     size_t degree = 0;
@@ -279,6 +293,30 @@ class PointTree {
         e_->check(kzg_point_tree_interpolate(e_->ctx(), h_, ys.empty() ? &none : ys.data(), ys.size() / k_, KZG_FR_CANONICAL_LE_32, 0,
                                              ys.empty() ? &none : out.data()));
         return out;
+    }
+    // create_witness_batched (src/coeff_form.rs:83-111) at the tree's points, any number of them (kzg_witness_coeff_tree): returns w =
+    // [p / M]_1 and, through r, p mod M -- the two halves of a KZGBatchWitness.  ys: the claimed values (KZGError if one is wrong), or
+    // empty for no claim.  One point gives r as the constant; the reference's X + (y - x) is the caller's to form.
+    KZGWitness create_witness(const KZGParams &params, const Polynomial &p, const std::vector<Scalar> &ys, Polynomial *r) const {
+        if (!ys.empty() && ys.size() != k_) throw ReferencePanic("assert_eq!(xs.len(), ys.len())");
+        G1Affine w;
+        std::vector<Scalar> rc(k_);
+        e_->check(kzg_witness_coeff_tree(e_->ctx(), params.gs, h_, p.coeffs.data(), p.num_coeffs(), 1, ys.empty() ? nullptr : ys.data(),
+                                         KZG_FR_CANONICAL_LE_32, 0, w.bytes.data(), KZG_G1_AFFINE_MONT_96, rc.data(), nullptr));
+        if (r) *r = Polynomial::make(std::move(rc));
+        return w;
+    }
+    // verify_eval_batched (src/coeff_form.rs:144-182) at the tree's points, any number of them (kzg_verify_eval_tree): r and w are
+    // the two halves of a KZGBatchWitness
+    bool verify(const KZGParams &params, const KZGCommitment &c, const Polynomial &r, const KZGWitness &w) const {
+        if (!params.hs) throw ReferencePanic("KZGParams.hs is empty (index out of bounds)");
+        if (r.num_coeffs() > k_) throw ReferencePanic("PointTree::verify: witness.r has more coefficients than the tree has points");
+        std::vector<Scalar> rc(r.coeffs.begin(), r.coeffs.begin() + r.num_coeffs());
+        rc.resize(k_);
+        uint8_t ok = 0;
+        e_->check(kzg_verify_eval_tree(e_->ctx(), params.gs, params.hs, h_, rc.data(), KZG_FR_CANONICAL_LE_32, c.bytes.data(), w.bytes.data(),
+                                       KZG_G1_AFFINE_MONT_96, 1, &ok));
+        return ok != 0;
     }
 
   private:

@@ -138,6 +138,10 @@ int kzg_test_verify_eval_batch_parts(kzg_ctx *ctx, const struct kzg_srs *gs, con
                                      const void *witnesses, int pfmt, size_t count, const void *r, int *ok, void *out_yagg, void *out_cw,
                                      void *out_points);
 int kzg_test_arith(kzg_ctx *ctx, int op, const void *in, size_t in_rec, size_t n, void *out, size_t out_rec);
+/* g2_madd of kzg_amd/csrc/tower.h alone (the mixed addition kzg_msm_g2_bucket accumulates with; kzg_amd/csrc/g2_msm.hip), one thread per
+ * record, 64 per block: out[i] = acc[i] + pts[i].  acc: Jacobian Montgomery 288 B (any Z; Z = 0 the identity), pts and out: affine
+ * Montgomery 192 B (all zero the identity).  1 <= n <= 4096 */
+int kzg_test_g2_madd(kzg_ctx *ctx, const void *acc_jacobian, const void *pts_affine, size_t n, void *out_affine);
 /* pretend `srs` is resident on GPU `device` (the "SRS of another GPU" error of every MSM entry point, on a one-GPU box) */
 int kzg_test_srs_set_device(struct kzg_srs *srs, int device);
 /* the same for the G2 points and for a kzg_cosets_verifier (kzg_amd/csrc/verify_cosets.hip) */

@@ -130,6 +130,9 @@ def load(path=None):
         "kzg_srs_g2_len": (sz, [vp]),
         "kzg_srs_g2_free": (None, [vp, vp]),
         "kzg_msm_g2": (i32, [vp, vp, sz, vp, sz, i32, vp, i32]),
+        "kzg_msm_g2_bucket": (i32, [vp, vp, sz, vp, sz, i32, i32, vp, i32]),
+        "kzg_verify_eval_tree": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, i32, sz, vp]),
+        "kzg_witness_coeff_tree": (i32, [vp, vp, vp, vp, sz, sz, vp, i32, i32, vp, i32, vp, ctypes.POINTER(i32)]),
         "kzg_pairing_check": (i32, [vp, vp, i32, vp, i32, sz, sz, vp]),
         "kzg_verify_eval": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, i32, sz, vp]),
         "kzg_verify_eval_batched": (i32, [vp, vp, vp, vp, sz, vp, sz, i32, vp, vp, i32, ctypes.POINTER(i32)]),

@@ -774,6 +774,42 @@ class PointTree:
         of value vectors gives a list of coefficient lists.  One point gives the constant."""
         return self._vectors(self.engine.lib.kzg_point_tree_interpolate, ys)
 
+    def create_witness_batch(self, srs, coeffs, n=None, batch=1, ys=None, ofmt=L.G1_AFFINE_MONT, with_status=False):
+        """kzg_witness_coeff_tree: `batch` polynomials of n coefficients each (coeffs: ints, a canonical blob or a DeviceBuffer of
+        batch x n scalars back to back) opened at the tree's points against the SRS `srs`.  Returns (witnesses, remainders): `batch`
+        point blobs in ofmt and `batch` lists of k ints, r_b = p_b mod M zero-padded (the interpolant through the values).  ys
+        (optional: batch x k claimed values, flat, of the coefficients' kind): a claim that fails raises KZGError, or with
+        with_status=True a third element is returned, the list of `batch` status words (0 or KZG_ERR_POINT_NOT_ON_POLY)."""
+        e = self.engine
+        ptr, nn, sfmt, flags, _keep = e._scalars_arg(coeffs)
+        if n is None:
+            if batch < 1 or nn % batch:
+                raise ReferencePanic("%d scalars are not %d polynomials of equal length" % (nn, batch))
+            n = nn // batch
+        if nn < n * batch:  # the call would read past the buffer
+            raise ReferencePanic("%d scalars given, batch * n = %d" % (nn, batch * n))
+        k = len(self.xs)
+        yptr = None
+        if ys is not None:
+            yptr, yn, ysf, yfl, _ykeep = e._scalars_arg(ys)
+            if yn < batch * k or (yfl, ysf) != (flags, sfmt):
+                raise ReferencePanic("create_witness_batch: ys must be batch x k scalars of the coefficients' kind")
+        psz = L.POINT_BYTES[ofmt]
+        out_w, out_r = ctypes.create_string_buffer(psz * max(batch, 1)), ctypes.create_string_buffer(32 * max(batch * k, 1))
+        st = (ctypes.c_int * max(batch, 1))()
+        rc = e.lib.kzg_witness_coeff_tree(e.ctx, srs.handle, self.handle, ptr, n, batch, yptr, sfmt, flags, out_w, ofmt, out_r,
+                                          st if with_status else None)
+        if rc:
+            _raise(e, rc)
+        ws = [out_w.raw[i * psz:(i + 1) * psz] for i in range(batch)]
+        rs = [[e._scalar_from(out_r.raw[32 * (b * k + j):32 * (b * k + j) + 32], sfmt) for j in range(k)] for b in range(batch)]
+        return (ws, rs, list(st[:batch])) if with_status else (ws, rs)
+
+    def create_witness(self, srs, polynomial, ys=None, ofmt=L.G1_AFFINE_MONT):
+        """One polynomial opened at the tree's points: a KZGBatchWitness (r = p mod M, w = [p / M]_1); ys: its claimed values."""
+        ws, rs = self.create_witness_batch(srs, polynomial.slice_coeffs(), ys=ys, ofmt=ofmt)
+        return KZGBatchWitness(Polynomial(rs[0]), ws[0])
+
     def close(self):
         if self.handle:
             self.engine.lib.kzg_point_tree_free(self.engine.ctx, self.handle)
@@ -1000,6 +1036,17 @@ class SrsG2:
         blob = pack_scalars(scalars)
         out = ctypes.create_string_buffer(L.G2_POINT_BYTES[ofmt])
         rc = self.engine.lib.kzg_msm_g2(self.engine.ctx, self.handle, offset, blob, len(blob) // 32, L.FR_CANONICAL, out, ofmt)
+        if rc:
+            _raise(self.engine, rc)
+        return out.raw
+
+    def msm_bucket(self, scalars, offset=0, n=None, ofmt=L.G2_AFFINE_MONT):
+        """kzg_msm_g2_bucket: the same group element (the same bytes) by the bucket method, for large n; scalars: a list of ints, a blob
+        of canonical scalars or a DeviceBuffer in either format."""
+        ptr, nn, sfmt, flags, _keep = self.engine._scalars_arg(scalars)
+        n = nn if n is None else n
+        out = ctypes.create_string_buffer(L.G2_POINT_BYTES[ofmt])
+        rc = self.engine.lib.kzg_msm_g2_bucket(self.engine.ctx, self.handle, offset, ptr, n, sfmt, flags, out, ofmt)
         if rc:
             _raise(self.engine, rc)
         return out.raw
@@ -1594,6 +1641,16 @@ class KZGProver:
         ys = self.engine.poly_multi_eval(polynomial.slice_coeffs(), xs)
         return ys, self.create_witness_batched(polynomial, xs, ys, ofmt)
 
+    def create_witness_batched_with_tree(self, polynomial, tree, ys, ofmt=L.G1_AFFINE_MONT):
+        """create_witness_batched at the points of a PointTree (kzg_witness_coeff_tree): any number of points up to the plan's 2^22.
+        One point gives the reference's r = X + (y - x) (src/polynomial.rs:244-247) and the witness that goes with it, through
+        create_witness_batched: kzg_witness_coeff_tree itself returns the constant and [(p - y) / (X - x)]_1."""
+        if len(ys) != len(tree):
+            raise ReferencePanic("assert_eq!(xs.len(), ys.len())")
+        if len(tree) == 1:  # the reference interpolates one point as X + (y - x), so its witness is [(p - y) / (X - x) - 1]_1: the
+            return self.create_witness_batched(polynomial, tree.xs, ys, ofmt)  # reference-shaped call reproduces both halves
+        return tree.create_witness(self.parameters.gs, polynomial, ys=[int(y) % R_MODULUS for y in ys], ofmt=ofmt)
+
     def create_witness_batched(self, polynomial, xs, ys, ofmt=L.G1_AFFINE_MONT):  # :83-111
         e = self.engine
         assert len(xs) == len(ys)
@@ -1732,6 +1789,28 @@ class KZGVerifier:
         if rc:
             _raise(e, rc)
         return bool(ok.value)
+
+    def verify_eval_batched_with_tree(self, tree, commitment, witness, pfmt=L.G1_AFFINE_MONT):
+        """verify_eval_batched at the points of a PointTree (kzg_verify_eval_tree): any number of points up to the plan's 2^22."""
+        return self.verify_eval_batched_with_tree_many(tree, [commitment], [witness], pfmt)[0]
+
+    def verify_eval_batched_with_tree_many(self, tree, commitments, witnesses, pfmt=L.G1_AFFINE_MONT):
+        """`count` openings at the tree's points in one call (hz is computed once) -> list of bool"""
+        e = self.engine
+        k, n = len(tree), len(commitments)
+        assert len(witnesses) == n
+        rs = []
+        for w in witnesses:
+            c = list(w.r.slice_coeffs())
+            if len(c) > k:
+                raise ReferencePanic("verify_eval_batched_with_tree: witness.r has more coefficients than the tree has points")
+            rs.append(pack_scalars(c + [0] * (k - len(c))))
+        ok = ctypes.create_string_buffer(max(n, 1))
+        rc = e.lib.kzg_verify_eval_tree(e.ctx, self.parameters.gs.handle, self._hs().handle, tree.handle, b"".join(rs) or bytes(32),
+                                        L.FR_CANONICAL, b"".join(commitments) or bytes(96), b"".join(w.w for w in witnesses) or bytes(96), pfmt, n, ok)
+        if rc:
+            _raise(e, rc)
+        return [bool(b) for b in ok.raw[:n]]
 
     def verify_cosets(self, verifier, commitment, coset_ids, cells, proofs, pfmt=L.G1_AFFINE_MONT):
         """kzg_verify_cosets for the cells of ONE commitment: cells[k] (l values) and proofs[k] open coset coset_ids[k] of the

@@ -150,6 +150,8 @@ struct kzg_ctx {
     int opt_multi_eval_points_chunk = 0;  // kzg_poly_multi_eval: at most this many points per pass (0 = 4096 alone); either option takes the kernels at any k
     int opt_poly_divide_base = 0;         // kzg_poly_divide: precision the base kernel of the series inverse produces, a power of two <= 64 (0 = 64)
     int opt_point_tree_leaf = 0;          // kzg_point_tree_setup: nodes of up to this many points are multiplied by the schoolbook kernels, a power of two <= 16 (0 = 16)
+    int opt_g2_msm_slice = 0;             // kzg_msm_g2_bucket: points one workgroup sorts by digit, a power of two <= 2048 (0 = 2048)
+    int opt_g2_msm_slots = 0;             // kzg_msm_g2_bucket: slice slots of the bucket arena = slices per chunk, 1..16 (0 = 16)
     int opt_host_pairing = 1;         // kzg_verify_cosets_batch, kzg_verify_eval_batch: the one pairing check runs on the calling thread (vcb_finish.h); 0 = in a one-thread kernel
     int opt_fk20_cosets_combine = 0;   // the coset combination of kzg_witness_cosets_*: 0 = Straus (shared doublings), 1 = mul256 per term
     int opt_ntt_kernel = KZG_NTT_KERNEL_DEFAULT;  // 0: three-phase passes (k_ntt_pass1/2); 1: load/store fused into the first/last stage pair (k_ntt_tile); 2: 1 + two butterflies per thread
@@ -510,11 +512,38 @@ int multiopen_accum_run(kzg_ctx *ctx, hipStream_t st, const Fr *d_v, size_t d, c
 // min(base, 64, m) coefficients and Newton doubling through ntt_run.  d_A, d_G: scratch of 2^ilog2_ceil(2 m - 1) elements each; the
 // lane's arena must have ntt_workspace_bytes(ilog2_ceil(2 m - 1)) left.  Behind kzg_poly_divide and kzg_point_tree_setup.
 int series_inverse_run(kzg_ctx *ctx, int lane, const Fr *d_f, size_t fl_all, size_t m, size_t base, Fr *d_g, Fr *d_A, Fr *d_G);
+// The division by ONE divisor b (nb >= 2 coefficients) as stages on device memory, behind kzg_poly_divide and kzg_witness_coeff_tree:
+// poly_divisor_shape fills the sizes for dividends of na coefficients; the caller provides the buffers (elements): f fl_all, g m,
+// G and A Tq each and, for remainders, B, af, qf N each, tmp0 t0, tmp1 t1; the lane's arena must have
+// ntt_workspace_bytes(max(log_tq, log_N)) left.  poly_divisor_run (m >= 1) once per divisor -- bd on the device, converted to
+// Montgomery form if to_m --, poly_dividend_run per dividend: q and r keep the dividend's form, *flag is cleared at a non-zero
+// remainder coefficient.  poly_pad_run: a dividend shorter than the divisor, reduced and zero-padded, is its own remainder.
+struct PolyDivisor {
+    size_t na, nb, m, nr, Tq, N, fl_all, t0, t1;
+    uint32_t log_tq, log_N;
+    Fr *f, *g, *G, *A, *B, *af, *qf, *tmp0, *tmp1;
+};
+void poly_divisor_shape(size_t na, size_t nb, PolyDivisor *d);
+int poly_divisor_run(kzg_ctx *ctx, int lane, const Fr *bd, int to_m, bool want_r, const PolyDivisor &d);
+int poly_dividend_run(kzg_ctx *ctx, int lane, const PolyDivisor &d, const Fr *ai, Fr *qi, bool want_r, Fr *ri, int *flag);
+int poly_pad_run(kzg_ctx *ctx, hipStream_t st, const Fr *src, size_t cnt, Fr *dst, size_t total);
 
 // point_tree.hip: batched transforms of 2^log_t points over `total` contiguous elements (total a multiple of 2^log_t), in place.
 // dit = 0: natural order in, bit-reversed spectrum out (decimation in frequency); dit = 1: bit-reversed in, natural out.  tw is
 // the table w^j, j < 2^(log_tw - 1), of a 2^log_tw-th root w (or of 1 / w), log_tw >= log_t: no scaling is applied.
 int pt_ntt_run(kzg_ctx *ctx, hipStream_t st, Fr *d, size_t total, uint32_t log_t, int dit, const Fr *tw, uint32_t log_tw);
+// a kzg_point_tree as the prover and the verifier on a plan (witness_tree.hip) read it: product = M, k + 1 Montgomery coefficients
+// resident on `device`; K: the padded size; distinct = 0: two points coincide
+struct PointTreeView {
+    int device;
+    size_t k, K;
+    int distinct;
+    const Fr *product;
+};
+void point_tree_view(const kzg_point_tree *plan, PointTreeView *v);
+// the interpolation of kzg_point_tree_interpolate on device memory: d_out[u k + j] = coefficient j of the polynomial through
+// (x_i, d_ys[u k + i]) for `units` vectors, in the values' form; d_R: units x 2K, d_A: units x K elements of scratch (distinct plans only)
+int point_tree_interpolate_run(kzg_ctx *ctx, hipStream_t st, const kzg_point_tree *plan, const Fr *d_ys, size_t units, Fr *d_R, Fr *d_A, Fr *d_out);
 
 
 }  // namespace kzg

@@ -388,6 +388,13 @@ int kzg::fetch_ok(kzg_ctx *ctx, int lane, const uint8_t *d_ok, const int *d_bad,
     return KZG_OK;
 }
 
+// the G2 encoders for the other translation units (pairing_shared.h)
+size_t kzg::g2_point_bytes(int fmt) { return g2_format_bytes(fmt); }
+int kzg::g2_encode_run(kzg_ctx *ctx, hipStream_t st, const G2Affine *d_in, size_t n, int fmt, uint8_t *d_out) {
+    if (n) KZG_LAUNCH(ctx, st, "k_g2_encode", k_g2_encode, (unsigned)((n + 63) / 64), 64, 0, d_in, n, fmt, d_out, g2_format_bytes(fmt));
+    return KZG_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // C ABI: G2 SRS
 // ------------------------------------------------------------------------------------------------

@@ -21,4 +21,11 @@ namespace kzg {
 int g1_inputs(kzg_ctx *ctx, int lane, const void *host, size_t count, int pfmt, G1Xyzz **d_out, int *d_bad);
 // the verdicts and the decode flag of one launch: KZG_ERR_BAD_POINT if the flag is set (ok is then not written); synchronises the lane
 int fetch_ok(kzg_ctx *ctx, int lane, const uint8_t *d_ok, const int *d_bad, size_t count, uint8_t *ok);
+// bytes of one G2 point in a KZG_G2_* format (0: unknown format); k_g2_encode: n affine points -> d_out, one after the other
+size_t g2_point_bytes(int fmt);
+int g2_encode_run(kzg_ctx *ctx, hipStream_t st, const G2Affine *d_in, size_t n, int fmt, uint8_t *d_out);
+// g2_msm.hip, the bucket method behind kzg_msm_g2_bucket: sum_i d_sc[i] srs[offset + i] -> d_out (affine) on lane 0's stream; d_sc
+// canonical and reduced (vcb_canon); takes g2_msm_bucket_workspace_bytes from lane 0's arena
+size_t g2_msm_bucket_workspace_bytes(const kzg_ctx *ctx);
+int g2_msm_bucket_device(kzg_ctx *ctx, const kzg_srs_g2 *srs, size_t offset, const Fr *d_sc, size_t n, G2Affine *d_out);
 }  // namespace kzg

@@ -519,6 +519,18 @@ static int pt_combine(kzg_ctx *ctx, const kzg_point_tree *pl, const void *cs, si
     return KZG_OK;
 }
 
+// what the callers of other translation units read of a plan (common.h)
+void point_tree_view(const kzg_point_tree *pl, PointTreeView *v) {
+    v->device = pl->device;
+    v->k = pl->k;
+    v->K = pl->K;
+    v->distinct = pl->distinct;
+    v->product = pl->mtrue;
+}
+int point_tree_interpolate_run(kzg_ctx *ctx, hipStream_t st, const kzg_point_tree *pl, const Fr *d_ys, size_t units, Fr *d_R, Fr *d_A, Fr *d_out) {
+    return pt_combine_core(ctx, st, pl, d_ys, units, pl->dinv, d_R, d_A, d_out);
+}
+
 }  // namespace kzg
 
 extern "C" int kzg_point_tree_setup(kzg_ctx *ctx, const void *xs, size_t k, int sfmt, kzg_point_tree **out) {

@@ -199,6 +199,61 @@ int series_inverse_run(kzg_ctx *ctx, int lane, const Fr *d_f, size_t fl_all, siz
     return KZG_OK;
 }
 
+// ---- the division by ONE divisor as device-level stages (common.h, PolyDivisor): behind kzg_poly_divide and kzg_witness_coeff_tree ----
+void poly_divisor_shape(size_t na, size_t nb, PolyDivisor *d) {
+    d->na = na;
+    d->nb = nb;
+    d->m = na >= nb ? na - nb + 1 : 0;
+    d->nr = nb - 1;
+    d->log_tq = d->m ? (uint32_t)ilog2_ceil(2 * d->m - 1) : 0;
+    d->log_N = d->nr ? (uint32_t)ilog2_ceil(d->nr) : 0;
+    d->Tq = (size_t)1 << d->log_tq;
+    d->N = (size_t)1 << d->log_N;
+    d->fl_all = std::min(nb, std::max<size_t>(d->m, 1));
+    d->t0 = pd_fold_tmp0(std::max(na, d->m), d->N);
+    d->t1 = pd_fold_tmp1(std::max(na, d->m), d->N);
+}
+
+// what depends on the divisor alone (m >= 1, nb >= 2): f = rev(b) mod X^m, g = 1 / f, the transform of g and, with want_r, of b folded
+int poly_divisor_run(kzg_ctx *ctx, int lane, const Fr *bd, int to_m, bool want_r, const PolyDivisor &d) {
+    hipStream_t st = ctx->lanes[lane].stream;
+    KZG_LAUNCH(ctx, st, "k_pd_load", k_pd_load, pd_grid(d.fl_all), PD_T, 0, bd, d.nb - 1, 1, d.fl_all, d.f, d.fl_all, to_m);
+    const size_t base = ctx->opt_poly_divide_base ? (size_t)ctx->opt_poly_divide_base : (size_t)PD_BASE;
+    KZG_TRY(series_inverse_run(ctx, lane, d.f, d.fl_all, d.m, base, d.g, d.A, d.G));  // (A, G: free until the quotient stage)
+    KZG_LAUNCH(ctx, st, "k_pd_load", k_pd_load, pd_grid(d.Tq), PD_T, 0, d.g, 0, 0, d.m, d.G, d.Tq, 0);
+    KZG_TRY(pd_ntt(ctx, lane, d.G, d.log_tq, 0));
+    if (want_r) {
+        KZG_LAUNCH(ctx, st, "k_pd_fold_b", k_pd_fold_b, pd_grid(d.N), PD_T, 0, bd, d.nb, d.B, d.N, to_m);
+        KZG_TRY(pd_ntt(ctx, lane, d.B, d.log_N, 0));
+    }
+    return KZG_OK;
+}
+
+// one dividend ai (na coefficients, device): qi (m coefficients, may be null) and, with want_r, ri (nr coefficients, may be null) with
+// *flag cleared at a non-zero remainder coefficient
+int poly_dividend_run(kzg_ctx *ctx, int lane, const PolyDivisor &d, const Fr *ai, Fr *qi, bool want_r, Fr *ri, int *flag) {
+    hipStream_t st = ctx->lanes[lane].stream;
+    KZG_LAUNCH(ctx, st, "k_pd_load", k_pd_load, pd_grid(d.Tq), PD_T, 0, ai, d.na - 1, 1, d.m, d.A, d.Tq, 0);  // rev(a) mod X^m
+    KZG_TRY(pd_ntt(ctx, lane, d.A, d.log_tq, 0));
+    KZG_LAUNCH(ctx, st, "k_pd_mul", k_pd_mul, pd_grid(d.Tq), PD_T, 0, d.A, d.G, d.Tq);
+    KZG_TRY(pd_ntt(ctx, lane, d.A, d.log_tq, 1));
+    if (qi) KZG_LAUNCH(ctx, st, "k_pd_emit_rev", k_pd_emit_rev, pd_grid(d.m), PD_T, 0, d.A, d.m, qi);
+    if (!want_r) return KZG_OK;
+    KZG_TRY(pd_fold_run(ctx, st, ai, d.na, 0, d.N, d.tmp0, d.tmp1, d.af));
+    KZG_TRY(pd_fold_run(ctx, st, d.A, d.m, 1, d.N, d.tmp0, d.tmp1, d.qf));
+    KZG_TRY(pd_ntt(ctx, lane, d.qf, d.log_N, 0));
+    KZG_LAUNCH(ctx, st, "k_pd_mul", k_pd_mul, pd_grid(d.N), PD_T, 0, d.qf, d.B, d.N);
+    KZG_TRY(pd_ntt(ctx, lane, d.qf, d.log_N, 1));
+    KZG_LAUNCH(ctx, st, "k_pd_rem", k_pd_rem, pd_grid(d.nr), PD_T, 0, d.af, d.qf, d.nr, ri, flag);
+    return KZG_OK;
+}
+
+// dst[i] = src[i] mod r for i < cnt, zero for cnt <= i < total: a dividend shorter than the divisor is its own remainder
+int poly_pad_run(kzg_ctx *ctx, hipStream_t st, const Fr *src, size_t cnt, Fr *dst, size_t total) {
+    KZG_LAUNCH(ctx, st, "k_pd_load", k_pd_load, pd_grid(total), PD_T, 0, src, 0, 0, cnt, dst, total, 0);
+    return KZG_OK;
+}
+
 }  // namespace kzg
 
 using namespace kzg;
@@ -238,10 +293,11 @@ extern "C" int kzg_poly_divide(kzg_ctx *ctx, const void *a, size_t na, size_t ba
 
     const bool want_q = q_out && m, want_r = (r_out || exact) && nr && m;  // (m == 0: the remainder is the dividend itself)
     const size_t C = std::min(batch, std::min(PD_CHUNK_MAX, std::max<size_t>(1, PD_CHUNK_COEFFS / na)));
-    const uint32_t log_tq = m ? (uint32_t)ilog2_ceil(2 * m - 1) : 0, log_N = nr ? (uint32_t)ilog2_ceil(nr) : 0;
-    const size_t Tq = (size_t)1 << log_tq, N = (size_t)1 << log_N, fl_all = std::min(nb, std::max<size_t>(m, 1));
+    PolyDivisor dv;
+    poly_divisor_shape(na, nb, &dv);
+    const uint32_t log_tq = dv.log_tq, log_N = dv.log_N;
+    const size_t Tq = dv.Tq, N = dv.N, fl_all = dv.fl_all, t0 = dv.t0, t1 = dv.t1;
     const bool general = m && nb > 1;
-    const size_t t0 = pd_fold_tmp0(std::max(na, m), N), t1 = pd_fold_tmp1(std::max(na, m), N);
     size_t need = 65536 + align_up(C * sizeof(int), 256) + align_up(nb * 32, 256) + align_up(fl_all * 32, 256);
     if (!in_dev) need += align_up(C * na * 32, 256);
     const bool stage_q = !out_dev && want_q, stage_r = !out_dev && r_out && nr;  // host outputs: a chunk's results are staged
@@ -282,21 +338,13 @@ extern "C" int kzg_poly_divide(kzg_ctx *ctx, const void *a, size_t na, size_t ba
         KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_b, b, nb * 32, hipMemcpyHostToDevice, st));
         bd = d_b;
     }
-    if (m) {
-        // f = rev(b) mod X^m, Montgomery
-        KZG_LAUNCH(ctx, st, "k_pd_load", k_pd_load, pd_grid(fl_all), PD_T, 0, bd, nb - 1, 1, fl_all, d_f, fl_all, to_m);
-    }
+    dv.f = d_f, dv.g = d_g, dv.G = d_G, dv.A = d_A, dv.B = d_B, dv.af = d_af, dv.qf = d_qf, dv.tmp0 = d_t0, dv.tmp1 = d_t1;
     if (m && nb == 1) {
+        // f = b[0], Montgomery
+        KZG_LAUNCH(ctx, st, "k_pd_load", k_pd_load, pd_grid(fl_all), PD_T, 0, bd, nb - 1, 1, fl_all, d_f, fl_all, to_m);
         KZG_LAUNCH(ctx, st, "k_pd_inv_base", k_pd_inv_base, 1, PD_BASE, 0, d_f, 1u, 1u, d_f);  // d_f[0] = 1 / b[0]
     } else if (general) {
-        const size_t base = ctx->opt_poly_divide_base ? (size_t)ctx->opt_poly_divide_base : (size_t)PD_BASE;
-        KZG_TRY(series_inverse_run(ctx, lane, d_f, fl_all, m, base, d_g, d_A, d_G));  // (d_A, d_G: free until the quotient stage)
-        KZG_LAUNCH(ctx, st, "k_pd_load", k_pd_load, pd_grid(Tq), PD_T, 0, d_g, 0, 0, m, d_G, Tq, 0);
-        KZG_TRY(pd_ntt(ctx, lane, d_G, log_tq, 0));
-        if (want_r) {
-            KZG_LAUNCH(ctx, st, "k_pd_fold_b", k_pd_fold_b, pd_grid(N), PD_T, 0, bd, nb, d_B, N, to_m);
-            KZG_TRY(pd_ntt(ctx, lane, d_B, log_N, 0));
-        }
+        KZG_TRY(poly_divisor_run(ctx, lane, bd, to_m, want_r, dv));
     }
 
     // ---- the dividends, a chunk at a time ----
@@ -325,18 +373,7 @@ extern "C" int kzg_poly_divide(kzg_ctx *ctx, const void *a, size_t na, size_t ba
                 if (want_q) KZG_LAUNCH(ctx, st, "k_pd_scale", k_pd_scale, pd_grid(na), PD_T, 0, ai, d_f, qi, na);
                 continue;
             }
-            KZG_LAUNCH(ctx, st, "k_pd_load", k_pd_load, pd_grid(Tq), PD_T, 0, ai, na - 1, 1, m, d_A, Tq, 0);  // rev(a) mod X^m
-            KZG_TRY(pd_ntt(ctx, lane, d_A, log_tq, 0));
-            KZG_LAUNCH(ctx, st, "k_pd_mul", k_pd_mul, pd_grid(Tq), PD_T, 0, d_A, d_G, Tq);
-            KZG_TRY(pd_ntt(ctx, lane, d_A, log_tq, 1));
-            if (want_q) KZG_LAUNCH(ctx, st, "k_pd_emit_rev", k_pd_emit_rev, pd_grid(m), PD_T, 0, d_A, m, qi);
-            if (!want_r) continue;
-            KZG_TRY(pd_fold_run(ctx, st, ai, na, 0, N, d_t0, d_t1, d_af));
-            KZG_TRY(pd_fold_run(ctx, st, d_A, m, 1, N, d_t0, d_t1, d_qf));
-            KZG_TRY(pd_ntt(ctx, lane, d_qf, log_N, 0));
-            KZG_LAUNCH(ctx, st, "k_pd_mul", k_pd_mul, pd_grid(N), PD_T, 0, d_qf, d_B, N);
-            KZG_TRY(pd_ntt(ctx, lane, d_qf, log_N, 1));
-            KZG_LAUNCH(ctx, st, "k_pd_rem", k_pd_rem, pd_grid(nr), PD_T, 0, d_af, d_qf, nr, ri, ei ? ei : d_exact);
+            KZG_TRY(poly_dividend_run(ctx, lane, dv, ai, want_q ? qi : nullptr, want_r, ri, ei ? ei : d_exact));
         }
         if (!out_dev) {
             if (stage_q) KZG_HIP_CHECK(ctx, hipMemcpyAsync((Fr *)q_out + b0 * m, d_q, B * m * 32, hipMemcpyDeviceToHost, st));

@@ -442,6 +442,12 @@ extern "C" int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value) 
     } else if (k == "point_tree_leaf") {
         if (value != 0 && (value < 1 || value > 16 || (value & (value - 1)))) return fail(ctx, KZG_ERR_SHAPE, "point_tree_leaf must be 0 (16) or a power of two in 1..16");
         ctx->opt_point_tree_leaf = (int)value;
+    } else if (k == "g2_msm_slice") {
+        if (value != 0 && (value < 1 || value > 2048 || (value & (value - 1)))) return fail(ctx, KZG_ERR_SHAPE, "g2_msm_slice must be 0 (2048) or a power of two in 1..2048");
+        ctx->opt_g2_msm_slice = (int)value;
+    } else if (k == "g2_msm_slots") {
+        if (value < 0 || value > 16) return fail(ctx, KZG_ERR_SHAPE, "g2_msm_slots must be 0 (16) or 1..16 slice slots");
+        ctx->opt_g2_msm_slots = (int)value;
     } else if (k == "ntt_vec_log") {
         if (value < 0 || value > 2) return fail(ctx, KZG_ERR_SHAPE, "ntt_vec_log must be 0..2");
         ctx->opt_ntt_vec_log = (int)value;

@@ -402,6 +402,55 @@ KZG_NI void g2_add(G2Jacobian &r, const G2Jacobian &p, const G2Jacobian &q) {
     f2_mul(o.z, t, h);
     r = o;
 }
+// madd-2007-bl: Jacobian + affine (Z2 = 1), with the identity on either side and the doubling / inverse cases; r may be p
+KZG_NI void g2_madd(G2Jacobian &r, const G2Jacobian &p, const G2Affine &q) {
+    if (q.is_inf()) {
+        r = p;
+        return;
+    }
+    if (p.is_inf()) {
+        r.x = q.x;
+        r.y = q.y;
+        r.z = Fq2::one();
+        return;
+    }
+    Fq2 z1z1, u2, s2, h, hh, i, j, rr, v, t;
+    f2_sqr(z1z1, p.z);
+    f2_mul(u2, q.x, z1z1);
+    f2_mul(s2, q.y, p.z);
+    f2_mul(s2, s2, z1z1);
+    f2_sub(h, u2, p.x);
+    f2_sub(rr, s2, p.y);
+    if (h.is_zero()) {
+        if (rr.is_zero()) {
+            g2_dbl(r, p);
+        } else {
+            g2_set_inf(r);
+        }
+        return;
+    }
+    f2_dbl(rr, rr);
+    f2_sqr(hh, h);
+    f2_dbl(i, hh);
+    f2_dbl(i, i);
+    f2_mul(j, h, i);
+    f2_mul(v, p.x, i);
+    G2Jacobian o;
+    f2_sqr(o.x, rr);
+    f2_sub(o.x, o.x, j);
+    f2_sub(o.x, o.x, v);
+    f2_sub(o.x, o.x, v);
+    f2_sub(t, v, o.x);
+    f2_mul(t, rr, t);
+    f2_mul(j, p.y, j);
+    f2_dbl(j, j);
+    f2_sub(o.y, t, j);
+    f2_add(t, p.z, h);
+    f2_sqr(t, t);
+    f2_sub(t, t, z1z1);
+    f2_sub(o.z, t, hh);
+    r = o;
+}
 KZG_NI void g2_neg_affine(G2Affine &r, const G2Affine &a) {
     r.x = a.x;
     f2_neg(r.y, a.y);
