@@ -74,6 +74,11 @@ extern "C" {
  *   kzg_ntt_fr                              log_n <= 28                      (2^24: two LDS passes of <= 2^12 points; above: one
  *                                                                             more four-step level of <= 16 around them)
  *   kzg_coset_ntt_fr                        log_n <= 28;  kzg_poly_mul: products of up to 2^27 coefficients;
+ *   kzg_ntt_fr_batch,
+ *   kzg_coset_ntt_fr_batch                  log_n <= 28; any batch and stride: vectors go in chunks of max(1, 2^21 / n) (option "ntt_batch_chunk");
+ *                                                                             the workspace is one chunk's scratch (chunk x n x 32 B: 64 MiB, or one
+ *                                                                             vector; none at all up to 2^12 points) and does not grow with batch; host
+ *                                                                             data is staged in pieces of max(1, 2^21 / n) vectors (<= 64 MiB, or one vector)
  *   kzg_witness_coeff_batched               polynomials of up to 2^26 coefficients (the SRS with its window tables is 118 GB there);
  *   kzg_verify_poly_eval                    as far as the monomial SRS goes (MSM limit below)
  *   kzg_witness_coeff_batched,
@@ -170,7 +175,12 @@ int kzg_sync(kzg_ctx *ctx);
  * "trusted_points" (0 / 1), "streams" (1..16: batch pipelining depth, default 13), "accum_streams" (0..4), "accum_blocks[_batch]",
  * "sort_threads[_batch]", "ntt_vec_log" / "ntt_vec2_log" (tile widths of the NTT passes), "ntt_kernel" (1 = default: tile load / store fused
  * into the first / last stage pair; 0 = the round-5 three-phase passes, 2 = two butterflies per thread: A/B only), "ntt_three_from" (sizes from
- * 2^this on take three passes of <= 2^8 points, default 23; 0 = never), "hw_queues" (0 = measure), "tail_quads" (0 / 1: latency-mode tail kernels of a
+ * 2^this on take three passes of <= 2^8 points, default 23; 0 = never),
+ * "ntt_batch_chunk" (0 = default, max(1, 2^21 / n); 1..2^20: kzg_ntt_fr_batch / kzg_coset_ntt_fr_batch work in chunks of that many vectors -- from 2^13
+ *  points on a chunk's scratch is chunk x n x 32 bytes; the same bytes), "ntt_batch_rows_log" (0 = auto; 1 + v: the batched single-tile kernel
+ *  of sizes up to 2^12 takes 2^v transforms per workgroup, as far as 2^v x n <= 4096 and the LDS layouts go; the same bytes, for A/B and for tests
+ *  that put tile boundaries at single-digit batches), "ntt_batch_loop_from" (0 = default, 20; 13..22: batched sizes from 2^this on run as one
+ *  kzg_ntt_fr per vector; the same bytes, for A/B), "hw_queues" (0 = measure), "tail_quads" (0 / 1: latency-mode tail kernels of a
  * lone MSM), "host_affine" (1 / 0: a lone result bound for host memory is converted to affine and serialised by the calling
  * thread -- the same field code compiled for the host -- instead of one GPU lane; same bytes, ~90 us less latency),
  * "sort_single_pass" (0 / 1: 17-bit windows sorted in one pass instead of two levels; A/B only),
@@ -361,6 +371,18 @@ int kzg_compute_omega(size_t d, size_t *m, uint32_t *exp, void *omega, int sfmt)
 int kzg_ntt_fr(kzg_ctx *ctx, void *data, uint32_t log_n, int inverse, int flags);
 /* coset_fft / icoset_fft (src/ft.rs:168-178): distribute_powers(g = 7) then fft; ifft then g^-i. */
 int kzg_coset_ntt_fr(kzg_ctx *ctx, void *data, uint32_t log_n, int inverse, int sfmt, int flags);
+/* `batch` transforms of 2^log_n points each, in place, natural order in and out; vector b starts at data + b * stride * 32 bytes.
+ * stride is in elements: 0 means 2^log_n (contiguous), otherwise stride >= 2^log_n; the words between the vectors are neither
+ * read for the result nor changed.  The bytes of `batch` calls of kzg_ntt_fr / kzg_coset_ntt_fr, one per vector, in fewer launches:
+ * up to 2^12 points a workgroup takes several whole transforms into its LDS (one launch per chunk); from 2^13 to 2^19 points the two
+ * pass kernels of kzg_ntt_fr run once per chunk with the vector index folded into their grids; from 2^20 points on (and with option
+ * "ntt_kernel" = 0) one transform fills the chip and the call is a loop over the vectors (measured on one MI355X, batched kernels against
+ * the loop inside one call: 0.18 against 0.33 ms at 2^18 x 8, 0.40 against 0.46 ms at 2^19 x 8, 0.39 against 0.38 ms at 2^20 x 4, 0.42 against
+ * 0.42 ms at 2^21 x 2).  The coset call scales
+ * all vectors in one launch.  KZG_ERR_SHAPE: 0 < stride < 2^log_n, (batch - 1) * stride + 2^log_n elements or their bytes overflow
+ * size_t, log_n > 28; KZG_ERR_DEGREE_TOO_LARGE: log_n >= 32; batch = 0: KZG_OK, nothing touched.  Blocking; callable from many threads. */
+int kzg_ntt_fr_batch(kzg_ctx *ctx, void *data, uint32_t log_n, size_t batch, size_t stride, int inverse, int flags);
+int kzg_coset_ntt_fr_batch(kzg_ctx *ctx, void *data, uint32_t log_n, size_t batch, size_t stride, int inverse, int sfmt, int flags);
 
 /* EvaluationDomain::z (src/ft.rs:182-187): tau^d - 1.  Host-only helper. */
 int kzg_domain_z(size_t d, const void *tau, int sfmt, void *out);

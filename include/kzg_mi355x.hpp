@@ -353,6 +353,11 @@ struct EvaluationDomain {  // src/ft.rs:17-25
     void ifft(const Engine &e) { e.check(kzg_ntt_fr(e.ctx(), coeffs.data(), exp, 1, 0)); }  // :115-140
     void coset_fft(const Engine &e) { e.check(kzg_coset_ntt_fr(e.ctx(), coeffs.data(), exp, 0, KZG_FR_CANONICAL_LE_32, 0)); }
     void icoset_fft(const Engine &e) { e.check(kzg_coset_ntt_fr(e.ctx(), coeffs.data(), exp, 1, KZG_FR_CANONICAL_LE_32, 0)); }
+    // the same four for many domains of ONE size in one kzg_ntt_fr_batch / kzg_coset_ntt_fr_batch call (not reference methods)
+    static void fft_many(const Engine &e, const std::vector<EvaluationDomain *> &ds) { many(e, ds, false, 0); }
+    static void ifft_many(const Engine &e, const std::vector<EvaluationDomain *> &ds) { many(e, ds, false, 1); }
+    static void coset_fft_many(const Engine &e, const std::vector<EvaluationDomain *> &ds) { many(e, ds, true, 0); }
+    static void icoset_fft_many(const Engine &e, const std::vector<EvaluationDomain *> &ds) { many(e, ds, true, 1); }
     Scalar z(const Scalar &tau) const {  // :182-187
         Scalar out;
         if (kzg_domain_z(coeffs.size(), tau.le.data(), KZG_FR_CANONICAL_LE_32, out.le.data())) throw ReferencePanic("z");
@@ -367,7 +372,37 @@ struct EvaluationDomain {  // src/ft.rs:17-25
         if (o.coeffs.size() != coeffs.size()) throw ReferencePanic("assert_eq!(self.coeffs.len(), other.coeffs.len())");
         e.check(kzg_fr_vec_sub(e.ctx(), coeffs.data(), o.coeffs.data(), coeffs.size(), KZG_FR_CANONICAL_LE_32, 0));
     }
+
+  private:
+    static void many(const Engine &e, const std::vector<EvaluationDomain *> &ds, bool coset, int inverse);
 };
+
+// kzg_ntt_fr_batch / kzg_coset_ntt_fr_batch on host vectors: data holds `batch` vectors of 2^log_n scalars, vector b at element
+// b * stride (stride 0: back to back); transformed in place.  Not reference methods.
+inline void ntt_batch(const Engine &e, std::vector<Scalar> &data, uint32_t log_n, size_t batch, size_t stride = 0, bool inverse = false) {
+    static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+    const size_t n = (size_t)1 << log_n;
+    if (log_n < 32 && batch && data.size() < (batch - 1) * (stride ? stride : n) + n) throw ReferencePanic("ntt_batch: shape");
+    e.check(kzg_ntt_fr_batch(e.ctx(), data.data(), log_n, batch, stride, inverse ? 1 : 0, 0));
+}
+inline void coset_ntt_batch(const Engine &e, std::vector<Scalar> &data, uint32_t log_n, size_t batch, size_t stride = 0, bool inverse = false) {
+    const size_t n = (size_t)1 << log_n;
+    if (log_n < 32 && batch && data.size() < (batch - 1) * (stride ? stride : n) + n) throw ReferencePanic("coset_ntt_batch: shape");
+    e.check(kzg_coset_ntt_fr_batch(e.ctx(), data.data(), log_n, batch, stride, inverse ? 1 : 0, KZG_FR_CANONICAL_LE_32, 0));
+}
+
+inline void EvaluationDomain::many(const Engine &e, const std::vector<EvaluationDomain *> &ds, bool coset, int inverse) {
+    if (ds.empty()) return;
+    for (const EvaluationDomain *d : ds)
+        if (d->exp != ds[0]->exp || d->coeffs.size() != ds[0]->coeffs.size()) throw ReferencePanic("the domains of one batched transform must have one size");
+    const size_t n = ds[0]->coeffs.size();
+    std::vector<Scalar> all;
+    all.reserve(n * ds.size());
+    for (const EvaluationDomain *d : ds) all.insert(all.end(), d->coeffs.begin(), d->coeffs.end());
+    if (coset) coset_ntt_batch(e, all, ds[0]->exp, ds.size(), 0, inverse != 0);
+    else ntt_batch(e, all, ds[0]->exp, ds.size(), 0, inverse != 0);
+    for (size_t b = 0; b < ds.size(); b++) std::copy(all.begin() + b * n, all.begin() + (b + 1) * n, ds[b]->coeffs.begin());
+}
 
 // kzg_recover_cosets: the polynomial of at most n coefficients whose values on the cosets `coset_ids` (coset i = { w^(i + tK) },
 // K = N / l, cells[j] = the l values on coset_ids[j]) are `cells`; evals (optional) receives its N evaluations.  Not a reference method.

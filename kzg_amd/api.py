@@ -245,6 +245,42 @@ class Engine:
             _raise(self, rc)
         return unpack_scalars(buf.raw)
 
+    def _ntt_batch(self, coset, data, log_n, batch, stride, inverse):
+        n = 1 << log_n
+        if isinstance(data, DeviceBuffer):
+            assert batch is not None and data.n >= ((batch - 1) * (stride or n) + n if batch else 0)
+            if coset:
+                rc = self.lib.kzg_coset_ntt_fr_batch(self.ctx, data.ptr, log_n, batch, stride or 0, 1 if inverse else 0, data.sfmt, L.IN_DEVICE)
+            else:
+                rc = self.lib.kzg_ntt_fr_batch(self.ctx, data.ptr, log_n, batch, stride or 0, 1 if inverse else 0, L.IN_DEVICE)
+            if rc:
+                _raise(self, rc)
+            return data
+        vectors = [pack_scalars(v) for v in data]
+        if any(len(v) != 32 * n for v in vectors) or (batch is not None and batch != len(vectors)):
+            raise ValueError("ntt_batch: every vector must hold 2^log_n scalars, and batch (if given) must be their number")
+        if stride not in (None, 0, n):
+            raise ValueError("ntt_batch: stride applies to device buffers; vectors given as lists are contiguous")
+        blob = b"".join(vectors)
+        buf = ctypes.create_string_buffer(blob, len(blob) or 1)
+        if coset:
+            rc = self.lib.kzg_coset_ntt_fr_batch(self.ctx, buf, log_n, len(vectors), 0, 1 if inverse else 0, L.FR_CANONICAL, 0)
+        else:
+            rc = self.lib.kzg_ntt_fr_batch(self.ctx, buf, log_n, len(vectors), 0, 1 if inverse else 0, 0)
+        if rc:
+            _raise(self, rc)
+        out = unpack_scalars(buf.raw[:len(blob)])
+        return [out[i * n:(i + 1) * n] for i in range(len(vectors))]
+
+    def ntt_batch(self, data, log_n, batch=None, stride=None, inverse=False):
+        """kzg_ntt_fr_batch: `batch` transforms of 2^log_n points in one call.  data: a DeviceBuffer (in place; vector b at element
+        b * stride, stride None = 2^log_n) or a list of equal-length scalar lists / canonical blobs (returns a list of int lists)."""
+        return self._ntt_batch(False, data, log_n, batch, stride, inverse)
+
+    def coset_ntt_batch(self, data, log_n, batch=None, stride=None, inverse=False):
+        """kzg_coset_ntt_fr_batch: as ntt_batch, on the coset 7 H (coset_fft / icoset_fft of every vector)."""
+        return self._ntt_batch(True, data, log_n, batch, stride, inverse)
+
     def poly_eval(self, coeffs, x, n=None):
         ptr, nn, sfmt, flags, _keep = self._scalars_arg(coeffs)
         n = nn if n is None else n
@@ -1486,6 +1522,34 @@ class EvaluationDomain:
 
     def icoset_fft(self, engine):  # :173-178
         self.coeffs = engine.coset_ntt(self.coeffs, self.exp, inverse=True)
+
+    @staticmethod
+    def _many(engine, domains, coset, inverse):
+        domains = list(domains)
+        if len({d.exp for d in domains}) > 1 or len({len(d.coeffs) for d in domains}) > 1:
+            raise ValueError("the domains of one batched transform must have one size")
+        if not domains:
+            return
+        fn = engine.coset_ntt_batch if coset else engine.ntt_batch
+        for d, c in zip(domains, fn([d.coeffs for d in domains], domains[0].exp, inverse=inverse)):
+            d.coeffs = c
+
+    @staticmethod
+    def fft_many(engine, domains):
+        """fft of every domain (all of one size) in one kzg_ntt_fr_batch call; not a reference method"""
+        EvaluationDomain._many(engine, domains, False, False)
+
+    @staticmethod
+    def ifft_many(engine, domains):
+        EvaluationDomain._many(engine, domains, False, True)
+
+    @staticmethod
+    def coset_fft_many(engine, domains):
+        EvaluationDomain._many(engine, domains, True, False)
+
+    @staticmethod
+    def icoset_fft_many(engine, domains):
+        EvaluationDomain._many(engine, domains, True, True)
 
     def z(self, tau):  # :182-187
         out = ctypes.create_string_buffer(32)

@@ -628,6 +628,56 @@ extern "C" int kzg_ntt_fr(kzg_ctx *ctx, void *data, uint32_t log_n, int inverse,
     return KZG_OK;
 }
 
+// kzg_ntt_fr_batch / kzg_coset_ntt_fr_batch.  Device data is transformed where it lies.  Host data goes through the lane in pieces of
+// max(1, 2^21 / n) vectors (64 MiB, or one vector above that), packed back to back on the device: the words between the caller's
+// vectors never leave the host.
+static int ntt_batch_entry(kzg_ctx *ctx, void *data, uint32_t log_n, size_t batch, size_t stride, int inverse, int flags, bool coset) {
+    if (!ctx || !data) return KZG_ERR_SHAPE;
+    if (log_n >= FR_TWO_ADICITY) return fail(ctx, KZG_ERR_DEGREE_TOO_LARGE, "polynomial degree too large");
+    if (log_n > 28) return fail(ctx, KZG_ERR_SHAPE, "NTT sizes above 2^28 are not supported (as kzg_ntt_fr)");
+    const size_t n = (size_t)1 << log_n;
+    if (stride && stride < n) return fail(ctx, KZG_ERR_SHAPE, "batched NTT: stride must be 0 (contiguous) or at least 2^log_n elements");
+    if (!stride) stride = n;
+    if (batch == 0) return KZG_OK;
+    size_t span, span_bytes;
+    if (__builtin_mul_overflow(batch - 1, stride, &span) || __builtin_add_overflow(span, n, &span) || __builtin_mul_overflow(span, (size_t)32, &span_bytes))
+        return fail(ctx, KZG_ERR_SHAPE, "batched NTT: (batch - 1) * stride + 2^log_n elements do not fit the address space");
+    Lease ls;
+    KZG_TRY(lease_lane(ctx, &ls));
+    const int lane = ls.lane;
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const bool on_dev = (flags & KZG_IN_DEVICE) != 0;
+    const size_t piece = on_dev ? batch : std::min(batch, log_n >= 21 ? (size_t)1 : (size_t)1 << (21 - log_n));
+    KZG_TRY(lane_reserve(ctx, lane, (on_dev ? 0 : align_up(piece * n * 32 + 256, 256)) + ntt_batch_workspace_bytes(ctx, log_n, piece) + 65536));
+    hipStream_t st = ctx->lanes[lane].stream;
+    const Fr g7 = from_u64<FrParams>(FR_MULT_GENERATOR);
+    Fr *stage = on_dev ? nullptr : (Fr *)lane_alloc(ctx, lane, piece * n * 32);
+    if (!on_dev && !stage) return fail(ctx, KZG_ERR_ALLOC, "input staging not reserved");
+    const size_t mark = ctx->lanes[lane].arena_used;
+    for (size_t b0 = 0; b0 < batch; b0 += piece) {
+        const size_t cnt = std::min(piece, batch - b0);
+        Fr *d = on_dev ? (Fr *)data : stage;
+        uint8_t *host = (uint8_t *)data + b0 * stride * 32;
+        if (!on_dev) KZG_HIP_CHECK(ctx, hipMemcpy2DAsync(d, n * 32, host, stride * 32, n * 32, cnt, hipMemcpyHostToDevice, st));
+        ctx->lanes[lane].arena_used = mark;
+        if (coset) KZG_TRY(coset_ntt_batch_run(ctx, lane, d, log_n, cnt, on_dev ? stride : n, inverse, g7));
+        else KZG_TRY(ntt_batch_run(ctx, lane, d, log_n, cnt, on_dev ? stride : n, inverse));
+        if (!on_dev) KZG_HIP_CHECK(ctx, hipMemcpy2DAsync(host, stride * 32, d, n * 32, n * 32, cnt, hipMemcpyDeviceToHost, st));
+    }
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (ctx->prof) prof_collect(ctx);
+    return KZG_OK;
+}
+
+extern "C" int kzg_ntt_fr_batch(kzg_ctx *ctx, void *data, uint32_t log_n, size_t batch, size_t stride, int inverse, int flags) {
+    return ntt_batch_entry(ctx, data, log_n, batch, stride, inverse, flags, false);
+}
+
+extern "C" int kzg_coset_ntt_fr_batch(kzg_ctx *ctx, void *data, uint32_t log_n, size_t batch, size_t stride, int inverse, int sfmt, int flags) {
+    (void)sfmt;  // linear map with Montgomery constants: the data's form is preserved (as kzg_coset_ntt_fr)
+    return ntt_batch_entry(ctx, data, log_n, batch, stride, inverse, flags, true);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Fr polynomial helpers
 // ---------------------------------------------------------------------------------------------

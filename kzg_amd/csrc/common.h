@@ -158,6 +158,9 @@ struct kzg_ctx {
     int opt_ntt_three_from = 23;       // NTT sizes from 2^this on take three passes of <= 2^8 points (ntt_run3); 0 = never
     int opt_ntt_vec2_log = 1;          // pass 2: at most 2^v rows per tile (rows are contiguous: narrow tiles cost no coalescing on the load side)
     int opt_ntt_xcd = 1;               // XCD-aware tile order: bit 0 = pass 1, bit 1 = pass 2 (ntt.hip, xcd_tile)
+    int opt_ntt_batch_chunk = 0;       // kzg_ntt_fr_batch: transforms per chunk; 0 = max(1, 2^21 / n)
+    int opt_ntt_batch_rows_log = 0;    // ... log_n <= 12: 1 + log2 of the transforms per LDS tile; 0 = the rule (ntt.hip, ntt_rows_log)
+    int opt_ntt_batch_loop_from = 0;   // ... sizes from 2^this on run as a loop of ntt_run; 0 = NTT_BATCH_LOOP_FROM
     int opt_accum_blocks_batch = 0;    // batched MSMs (0 = auto): leave 1/16 of the wave slots to the latency-bound tail and sort
                                        // kernels of the neighbouring MSMs in flight (measured +6 % throughput)
     int opt_tail_quads = 1;            // single MSMs: four lanes per point operation in the tail kernels (latency mode, msm_tail.hip)
@@ -439,6 +442,8 @@ int vanishing_poly_run(kzg_ctx *ctx, hipStream_t st, const Fr *d_xs_mont, size_t
 // coset_fft / icoset_fft with shift g (src/ft.rs:142-178): v[i] *= g^i then the transform; the inverse transform then v[i] *= g^-i.
 // nnz (forward only): d[nnz ..) is zero, so only d[0, nnz) is scaled
 int coset_ntt_run(kzg_ctx *ctx, int lane, Fr *d, uint32_t log_n, int inverse, const Fr &g, size_t nnz = (size_t)-1);
+// the same for `batch` vectors, vector b at d + b * stride, on ntt_batch_run: one scaling launch for the whole batch
+int coset_ntt_batch_run(kzg_ctx *ctx, int lane, Fr *d, uint32_t log_n, size_t batch, size_t stride, int inverse, const Fr &g);
 
 // cached per-context tables, released by kzg_ctx_destroy
 void ntt_plans_free(kzg_ctx *ctx);   // ntt.hip
@@ -454,6 +459,12 @@ inline size_t ntt_workspace_bytes(uint32_t log_n) {
     return log_n > 24 ? n * 32 + ((size_t)1 << 24) * 32 + (2 << 20) : n * 32 + 4096;
 }
 bool ntt_short_input_ok(uint32_t log_n, size_t nnz);  // ntt_run(..., nnz) will not read d_data[nnz ..)
+// `batch` transforms of 2^log_n points in place, transform b at d_data + b * stride (stride >= n, in elements); chunked, see ntt.hip
+constexpr uint32_t NTT_BATCH_LOOP_FROM = 20;  // from this size on the batch is a loop of ntt_run (measured: DESIGN.md, batched NTT)
+int ntt_batch_run(kzg_ctx *ctx, int lane, Fr *d_data, uint32_t log_n, size_t batch, size_t stride, int inverse);
+bool ntt_batch_looped(const kzg_ctx *ctx, uint32_t log_n);                             // ... as one ntt_run per transform
+size_t ntt_batch_chunk(const kzg_ctx *ctx, uint32_t log_n);                            // transforms per chunk
+size_t ntt_batch_workspace_bytes(const kzg_ctx *ctx, uint32_t log_n, size_t batch);  // arena bytes one ntt_batch_run takes from its lane
 int pow_table(kzg_ctx *ctx, hipStream_t stream, const Fr &base_mont, const Fr &scale_mont, size_t count, Fr *d_out);
 Fr host_omega(uint32_t exp);  // Montgomery-form 2^exp-th root of unity per compute_omega (src/ft.rs:73)
 

@@ -237,6 +237,52 @@ __global__ __launch_bounds__(1024) void k_ntt_single(Fr *data, uint32_t t, const
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) data[i] = fr29_pack_canonical(mulshoup29(lds_fr29[swz(i, sw)], scale, scale_p));
 }
 
+// Batched single-tile transforms (ntt_batch_run, log_n <= 12): a workgroup takes 2^v whole transforms ("rows", row b at data + b *
+// stride) into LDS at lds[swz(row << t | bitrev(i))] -- the layout of a pass-2 tile of 2^v rows -- runs the stages over all of them
+// and writes every row back in natural order, in place.  Rows at or beyond `rows` (the partial last tile of a chunk) are neither
+// loaded nor stored: their LDS slots hold zeros.  t = 0 only canonicalises, t = 1 is one butterfly per row (as k_ntt_single).
+__global__ __launch_bounds__(1024) void k_ntt_rows(Fr *data, size_t stride, uint32_t rows, uint32_t t, uint32_t v, const Tw29 tw, Fr29 scale,
+                                                   Fr29 scale_p, uint64_t sw) {
+    const uint32_t n = 1u << t, tile = 1u << (t + v);
+    const uint32_t row0 = blockIdx.x << v;
+    const uint32_t live = rows - row0 < (1u << v) ? rows - row0 : (1u << v);  // rows of this tile that exist (the grid has no empty tile)
+    Fr *base = data + (size_t)row0 * stride;
+    Fr29 zero;
+#pragma unroll
+    for (int l = 0; l < R29_N; l++) zero.v[l] = 0;
+    if (tile == 4 * blockDim.x) {  // the usual shape (tile / 4 threads): the four loads of a thread in flight before the first unpack
+        Fr raw[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t e = threadIdx.x + i * blockDim.x;
+            if ((e >> t) < live) raw[i] = base[(size_t)(e >> t) * stride + (e & (n - 1))];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t e = threadIdx.x + i * blockDim.x;
+            lds_fr29[swz(((e >> t) << t) | bitrev(e & (n - 1), t), sw)] = (e >> t) < live ? fr29_unpack(raw[i]) : zero;
+        }
+    } else {
+        for (uint32_t e = threadIdx.x; e < tile; e += blockDim.x)
+            lds_fr29[swz(((e >> t) << t) | bitrev(e & (n - 1), t), sw)] = (e >> t) < live ? fr29_unpack(base[(size_t)(e >> t) * stride + (e & (n - 1))]) : zero;
+    }
+    __syncthreads();
+    if (t == 1) {
+        for (uint32_t b = threadIdx.x; b < (1u << v); b += blockDim.x) {
+            const uint32_t p0 = swz(b << 1, sw), p1 = p0 ^ 1;
+            Fr29 u = lds_fr29[p0], w = lds_fr29[p1], sm, df;
+            fr29_butterfly_lazy(u, w, sm, df);
+            lds_fr29[p0] = fr29_normalize(sm);
+            lds_fr29[p1] = fr29_normalize(df);
+        }
+        __syncthreads();
+    } else if (t >= 2) {
+        lds_ntt_stages29(lds_fr29, t, 1u << v, tw, sw);
+    }
+    for (uint32_t e = threadIdx.x; e < tile; e += blockDim.x)
+        if ((e >> t) < live) base[(size_t)(e >> t) * stride + (e & (n - 1))] = fr29_pack_canonical(mulshoup29(lds_fr29[swz(e, sw)], scale, scale_p));
+}
+
 // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share one, MI355X_MICROARCH.md), each with its own L2.  The tile
 // a block takes is therefore chosen so that the blocks of ONE XCD take ADJACENT tiles: in pass 1 their 128-byte column segments then
 // make up runs of a row in one L2 (4 KB per row and XCD at 2^20 instead of 128 B in each of eight L2s): pass 1 -6 % at 2^20, -13 % at
@@ -383,6 +429,11 @@ struct NttTile {
     Tw29 tw, tw_lo, tw_hi;
     const Fr29 *tw_full;
     Fr29 scale, scale_p;
+    // BATCH instantiations only (ntt_batch_run): the grid holds the tiles of several transforms, tile -> (vector = tile >> bt_log,
+    // tile of that vector = the low bits); vector b is read at in + b * in_stride and written at out + b * out_stride (elements): the
+    // caller's stride on the data side, n on the scratch side.  Behind every field the other instantiations read.
+    uint32_t bt_log = 0;
+    size_t in_stride = 0, out_stride = 0;
 };
 
 template <int PASS, bool SHORT>
@@ -408,12 +459,18 @@ __device__ __forceinline__ Fr29 ntt_tile_input(const Fr *in, const NttTile &a, u
     return x;
 }
 
-template <int PASS, int BPT, bool SHORT>
+template <int PASS, int BPT, bool SHORT, bool BATCH = false>
 __global__ __launch_bounds__(1024 / BPT) void k_ntt_tile(const Fr *in, Fr *out, const NttTile a) {
     Fr29 *lds = lds_fr29;
     const uint32_t t = a.t, vl = a.vec_log, vec = 1u << vl, Q = 1u << (t - 2);
     const uint32_t nthreads = blockDim.x;  // = (vec << t) / (4 BPT)
-    const uint32_t tile = xcd_tile(blockIdx.x, gridDim.x, a.xcd);
+    uint32_t tile = xcd_tile(blockIdx.x, gridDim.x, a.xcd);
+    if constexpr (BATCH) {  // this tile's vector: both pointers move to it, the tile number becomes the one inside the transform
+        const uint32_t bv = tile >> a.bt_log;
+        tile &= (1u << a.bt_log) - 1u;
+        in += (size_t)bv * a.in_stride;
+        out += (size_t)bv * a.out_stride;
+    }
     // column pass: first column of the tile inside its batch, and the batch's base; row pass: first row (k1) of the tile and its k2
     const uint32_t tile0 = (PASS == 1 ? (tile & ((1u << a.tpb_log) - 1u)) : (tile & ((1u << a.g1_log) - 1u))) << vl;
     const uint32_t hi_id = PASS == 1 ? (tile >> a.tpb_log) : (tile >> a.g1_log);   // batch (pass 1) / k2 (pass 2); 0 for two-pass transforms
@@ -664,6 +721,8 @@ static int ntt_plan(kzg_ctx *ctx, hipStream_t st, uint32_t log_n, int inverse, N
         for (const void *k : {(const void *)k_ntt_tile<1, 1, false>, (const void *)k_ntt_tile<1, 2, false>, (const void *)k_ntt_tile<2, 1, false>,
                               (const void *)k_ntt_tile<2, 2, false>, (const void *)k_ntt_tile<2, 1, true>, (const void *)k_ntt_tile<2, 2, true>})
             KZG_HIP_CHECK(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
+        for (const void *k : {(const void *)k_ntt_rows, (const void *)k_ntt_tile<1, 1, false, true>, (const void *)k_ntt_tile<2, 1, false, true>})
+            KZG_HIP_CHECK(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
         ctx->attr_ntt_set = true;
     }
     NttPlan *p = new NttPlan();
@@ -856,6 +915,25 @@ static int ntt_run_large(kzg_ctx *ctx, int lane, Fr *d_data, uint32_t log_n, int
     return KZG_OK;
 }
 
+// Tile widths of the two passes: vec adjacent columns / rows per block.  `rows`: transforms that share the grid (1: ntt_run).
+static void ntt_tile_widths(const kzg_ctx *ctx, const NttPlan *p, size_t rows, uint32_t *v1, uint32_t *v2) {
+    // vec adjacent columns/rows per block: as many as fit the LDS (4096 elements x 36 B = 144 KiB), at most 4 -- but never so many
+    // that fewer than 256 blocks are left for the 256 CUs (2^19: 128 blocks of 4096 -> 256 of 2048, pass 1 54.4 -> 38.8 us; 2^18:
+    // 35.0 -> 28.1 us; profiles/r05_ntt_tile_probe.txt)
+    const uint32_t vmax = (uint32_t)ctx->opt_ntt_vec_log;
+    uint32_t vec1 = 12 - p->k1 < vmax ? 12 - p->k1 : vmax;
+    while (vec1 && (rows << (p->k2 - vec1)) < 256u) vec1--;
+    // rows are contiguous, so narrower pass-2 tiles cost no coalescing and two blocks share a CU: one loads / stores while the
+    // other computes (same-box at 2^20: 58.2 -> 54.2 us; 2^22: 2048-element tiles 224.7 -> 205.2 us); pass 1 needs its 128-byte
+    // column segments
+    const uint32_t vmax2 = vmax < (uint32_t)ctx->opt_ntt_vec2_log ? vmax : (uint32_t)ctx->opt_ntt_vec2_log;
+    uint32_t vec2 = 12 - p->k2 < vmax2 ? 12 - p->k2 : vmax2;
+    if (ctx->opt_ntt_vec2_log <= 1 && p->k2 <= 11 && p->k2 + vec2 > 11) vec2 = 11 - p->k2;
+    while (vec2 && (rows << (p->k1 - vec2)) < 256u) vec2--;
+    *v1 = vec1;
+    *v2 = vec2;
+}
+
 // does ntt_run take the short-input path for a transform of 2^log_n points whose input has nnz leading non-zero elements?  (Then
 // d_data[nnz ..) is never read and need not be zero-filled.)
 bool ntt_short_input_ok(uint32_t log_n, size_t nnz) { return log_n > 12 && log_n <= 24 && nnz <= ((size_t)1 << (log_n / 2)); }
@@ -884,19 +962,8 @@ int ntt_run(kzg_ctx *ctx, int lane, Fr *d_data, uint32_t log_n, int inverse, siz
     size_t n = (size_t)1 << log_n;
     Fr *scratch = (Fr *)lane_alloc(ctx, lane, n * sizeof(Fr));
     if (!scratch) return fail(ctx, KZG_ERR_ALLOC, "NTT workspace not reserved");
-    // vec adjacent columns/rows per block: as many as fit the LDS (4096 elements x 36 B = 144 KiB), at most 4 -- but never so many
-    // that fewer than 256 blocks are left for the 256 CUs (2^19: 128 blocks of 4096 -> 256 of 2048, pass 1 54.4 -> 38.8 us; 2^18:
-    // 35.0 -> 28.1 us; profiles/r05_ntt_tile_probe.txt)
-    const uint32_t vmax = (uint32_t)ctx->opt_ntt_vec_log;
-    uint32_t vec1 = 12 - p->k1 < vmax ? 12 - p->k1 : vmax;
-    while (vec1 && (1u << (p->k2 - vec1)) < 256u) vec1--;
-    // rows are contiguous, so narrower pass-2 tiles cost no coalescing and two blocks share a CU: one loads / stores while the
-    // other computes (same-box at 2^20: 58.2 -> 54.2 us; 2^22: 2048-element tiles 224.7 -> 205.2 us); pass 1 needs its 128-byte
-    // column segments
-    const uint32_t vmax2 = vmax < (uint32_t)ctx->opt_ntt_vec2_log ? vmax : (uint32_t)ctx->opt_ntt_vec2_log;
-    uint32_t vec2 = 12 - p->k2 < vmax2 ? 12 - p->k2 : vmax2;
-    if (ctx->opt_ntt_vec2_log <= 1 && p->k2 <= 11 && p->k2 + vec2 > 11) vec2 = 11 - p->k2;
-    while (vec2 && (1u << (p->k1 - vec2)) < 256u) vec2--;
+    uint32_t vec1, vec2;
+    ntt_tile_widths(ctx, p, 1, &vec1, &vec2);
     size_t lds1 = ((size_t)1 << (p->k1 + vec1)) * sizeof(Fr29), lds2 = ((size_t)1 << (p->k2 + vec2)) * sizeof(Fr29);
     unsigned g1 = 1u << (p->k2 - vec1), g2 = 1u << (p->k1 - vec2);
     // one radix-4 butterfly per thread and stage; smaller tiles leave room for a second block per CU
@@ -939,6 +1006,110 @@ int ntt_run(kzg_ctx *ctx, int lane, Fr *d_data, uint32_t log_n, int inverse, siz
                p->tw_hi, p->lo_bits, p->tw_full, LDS_SWIZZLE[p->k1][vec1], xcd1);
     KZG_LAUNCH(ctx, st, "k_ntt_pass2", k_ntt_pass2<false>, g2, th2, lds2, scratch, d_data, p->k1, p->k2, vec2, p->tw2, p->scale, p->scale_p,
                p->tw_full ? 1 : 0, LDS_SWIZZLE[p->k2][vec2], 0u, (const Fr29 *)nullptr, Tw29(), Tw29(), 0u, xcd2);
+    return KZG_OK;
+}
+
+// ---- many transforms of one size per call (kzg_ntt_fr_batch) ---------------------------------------------------------------------
+// Three regimes by size:
+//   log_n <= 12          k_ntt_rows: 2^v whole transforms per workgroup, one launch per chunk;
+//   13 <= log_n < L      the two-pass kernels with the vector index folded into the grid (k_ntt_tile<.., BATCH>): one pass-1 and one
+//                        pass-2 launch per chunk, the scratch holds chunk x n elements;
+//   otherwise            ntt_run per vector (L = option ntt_batch_loop_from, default NTT_BATCH_LOOP_FROM; also every size that takes
+//                        three passes, every size above 2^24 and the round-5 kernels of option ntt_kernel = 0): one transform fills the
+//                        chip there.
+// Vectors go in chunks of option ntt_batch_chunk (0: max(1, 2^21 / n), 64 MiB of data), so neither grid nor scratch grow with batch.
+bool ntt_batch_looped(const kzg_ctx *ctx, uint32_t log_n) {
+    if (log_n <= 12) return false;
+    const uint32_t from = ctx->opt_ntt_batch_loop_from ? (uint32_t)ctx->opt_ntt_batch_loop_from : NTT_BATCH_LOOP_FROM;
+    if (!ctx->opt_ntt_kernel || log_n >= from || log_n > 21) return true;
+    return ctx->opt_ntt_three_from && log_n >= (uint32_t)ctx->opt_ntt_three_from && log_n >= 20;
+}
+
+size_t ntt_batch_chunk(const kzg_ctx *ctx, uint32_t log_n) {
+    if (ctx->opt_ntt_batch_chunk) return (size_t)ctx->opt_ntt_batch_chunk;
+    return log_n >= 21 ? 1 : (size_t)1 << (21 - log_n);
+}
+
+size_t ntt_batch_workspace_bytes(const kzg_ctx *ctx, uint32_t log_n, size_t batch) {
+    if (log_n <= 12) return 4096;
+    if (ntt_batch_looped(ctx, log_n)) return ntt_workspace_bytes(log_n);
+    const size_t chunk = ntt_batch_chunk(ctx, log_n);
+    return ((chunk < batch ? chunk : batch) << log_n) * sizeof(Fr) + 4096;
+}
+
+// rows per tile (log2) of k_ntt_rows for a chunk of `rows` transforms of 2^t points: as many as make a tile of 2048 elements (72 KiB: two
+// workgroups share a CU's LDS and one loads or stores while the other computes, as with the pass-2 tiles -- 2^20 elements as 2^8 x 4096:
+// 60.9 us with 4096-element tiles, 58.8 with 2048; as 2^10 x 1024: 70.0 against 66.5 with 1024; profiles/ntt_batch.txt), fewer while
+// the grid would drop below 256 workgroups and the workgroup keeps 256 threads (the rule ntt_tile_widths applies to the pass tiles).
+// The option may force any tile of up to 4096 elements.
+static uint32_t ntt_rows_log(const kzg_ctx *ctx, uint32_t t, size_t rows) {
+    uint32_t v = 12 - t;
+    if (ctx->opt_ntt_batch_rows_log) {
+        v = std::min(v, (uint32_t)ctx->opt_ntt_batch_rows_log - 1u);
+    } else {
+        if (v) v--;
+        while (v && ((size_t)1 << (v - 1)) >= rows) v--;  // no tile wider than the chunk
+        while (v && ((rows + ((size_t)1 << v) - 1) >> v) < 256u && t + v >= 11) v--;
+    }
+    // LDS_SWIZZLE has the columns v <= 5.  Transforms of up to 16 points (t <= 4) use the plain layout, as the table's own rows do at
+    // those t (all zero), at any v; from 32 points on v stays inside the table and the chunk takes more workgroups
+    if (t >= 5 && v > 5) v = 5;
+    return v;
+}
+
+int ntt_batch_run(kzg_ctx *ctx, int lane, Fr *d_data, uint32_t log_n, size_t batch, size_t stride, int inverse) {
+    if (log_n >= FR_TWO_ADICITY) return fail(ctx, KZG_ERR_DEGREE_TOO_LARGE, "polynomial degree too large");
+    if (log_n > 28) return fail(ctx, KZG_ERR_SHAPE, "NTT sizes above 2^28 are not supported (2^24-point two-pass transforms under one 16-point outer level)");
+    const size_t n = (size_t)1 << log_n;
+    if (ntt_batch_looped(ctx, log_n)) {
+        for (size_t b = 0; b < batch; b++) {
+            const size_t mark = ctx->lanes[lane].arena_used;  // a transform's scratch is released before the next
+            KZG_TRY(ntt_run(ctx, lane, d_data + b * stride, log_n, inverse));
+            ctx->lanes[lane].arena_used = mark;
+        }
+        return KZG_OK;
+    }
+    hipStream_t st = ctx->lanes[lane].stream;
+    NttPlan *p = nullptr;
+    KZG_TRY(ntt_plan(ctx, st, log_n, inverse, &p));
+    const size_t chunk = ntt_batch_chunk(ctx, log_n);
+    if (log_n <= 12) {
+        for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+            const size_t rows = std::min(chunk, batch - b0);
+            const uint32_t v = ntt_rows_log(ctx, log_n, rows);
+            if (v > 12 - log_n || (v > 5 && log_n > 4)) return fail(ctx, KZG_ERR_INTERNAL, "batched NTT: no LDS layout for this tile");
+            const uint64_t sw = v <= 5 ? LDS_SWIZZLE[log_n][v] : 0;
+            const size_t tile = (size_t)1 << (log_n + v);
+            const unsigned threads = (unsigned)std::min<size_t>(1024, std::max<size_t>(64, tile / 4));
+            const size_t grid = (rows + ((size_t)1 << v) - 1) >> v;
+            if (grid > 0x7fffffffu || rows > 0xffffffffu) return fail(ctx, KZG_ERR_SHAPE, "batched NTT: ntt_batch_chunk leaves more than 2^31 - 1 tiles per chunk");
+            KZG_LAUNCH(ctx, st, "k_ntt_rows", k_ntt_rows, (unsigned)grid, threads, tile * sizeof(Fr29), d_data + b0 * stride, stride, (uint32_t)rows,
+                       log_n, v, p->tw1, p->scale, p->scale_p, sw);
+        }
+        return KZG_OK;
+    }
+    if (chunk > ((size_t)1 << 20)) return fail(ctx, KZG_ERR_SHAPE, "batched NTT: ntt_batch_chunk above 2^20 transforms of 2^13 points or more");
+    Fr *scratch = (Fr *)lane_alloc(ctx, lane, (std::min(chunk, batch) << log_n) * sizeof(Fr));
+    if (!scratch) return fail(ctx, KZG_ERR_ALLOC, "NTT workspace not reserved");
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t rows = std::min(chunk, batch - b0);
+        uint32_t vec1, vec2;
+        ntt_tile_widths(ctx, p, rows, &vec1, &vec2);
+        if (p->k1 > 12 || p->k2 > 12 || vec1 > 5 || vec2 > 5) return fail(ctx, KZG_ERR_INTERNAL, "batched NTT: no LDS layout for this tile");
+        NttTile a1, a2;
+        a1.t = p->k1; a1.kother = p->k2; a1.vec_log = vec1; a1.lo_bits = p->lo_bits; a1.nnz = 0; a1.xcd = ctx->opt_ntt_xcd & 1; a1.scale_folded = 0;
+        a1.sw = LDS_SWIZZLE[p->k1][vec1]; a1.tw = p->tw1; a1.tw_lo = p->tw_lo; a1.tw_hi = p->tw_hi; a1.tw_full = p->tw_full;
+        a1.scale = p->scale; a1.scale_p = p->scale_p;
+        a1.bt_log = p->k2 - vec1; a1.in_stride = stride; a1.out_stride = n;
+        a2 = a1;
+        a2.t = p->k2; a2.kother = p->k1; a2.vec_log = vec2; a2.xcd = ctx->opt_ntt_xcd == 1 ? 0 : (ctx->opt_ntt_xcd >> 1 & 1);
+        a2.scale_folded = p->tw_full ? 1 : 0; a2.sw = LDS_SWIZZLE[p->k2][vec2]; a2.tw = p->tw2; a2.tw_full = nullptr;
+        a2.bt_log = p->k1 - vec2; a2.in_stride = n; a2.out_stride = stride;
+        const unsigned nb1 = 1u << (p->k1 + vec1 - 2), nb2 = 1u << (p->k2 + vec2 - 2);  // radix-4 butterflies per tile = threads
+        const unsigned g1 = (unsigned)(rows << a1.bt_log), g2 = (unsigned)(rows << a2.bt_log);
+        KZG_LAUNCH(ctx, st, "k_ntt_pass1", (k_ntt_tile<1, 1, false, true>), g1, nb1, (size_t)4 * nb1 * sizeof(Fr29), d_data + b0 * stride, scratch, a1);
+        KZG_LAUNCH(ctx, st, "k_ntt_pass2", (k_ntt_tile<2, 1, false, true>), g2, nb2, (size_t)4 * nb2 * sizeof(Fr29), scratch, d_data + b0 * stride, a2);
+    }
     return KZG_OK;
 }
 

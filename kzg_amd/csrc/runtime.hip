@@ -448,6 +448,15 @@ extern "C" int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value) 
     } else if (k == "g2_msm_slots") {
         if (value < 0 || value > 16) return fail(ctx, KZG_ERR_SHAPE, "g2_msm_slots must be 0 (16) or 1..16 slice slots");
         ctx->opt_g2_msm_slots = (int)value;
+    } else if (k == "ntt_batch_chunk") {
+        if (value < 0 || value > (1 << 20)) return fail(ctx, KZG_ERR_SHAPE, "ntt_batch_chunk must be 0 (max(1, 2^21 / n) transforms) or 1..2^20 transforms");
+        ctx->opt_ntt_batch_chunk = (int)value;
+    } else if (k == "ntt_batch_rows_log") {
+        if (value < 0 || value > 13) return fail(ctx, KZG_ERR_SHAPE, "ntt_batch_rows_log must be 0 (auto) or 1 + log2 of the transforms per tile, 1..13");
+        ctx->opt_ntt_batch_rows_log = (int)value;
+    } else if (k == "ntt_batch_loop_from") {
+        if (value != 0 && (value < 13 || value > 22)) return fail(ctx, KZG_ERR_SHAPE, "ntt_batch_loop_from must be 0 (default) or 13..22");
+        ctx->opt_ntt_batch_loop_from = (int)value;
     } else if (k == "ntt_vec_log") {
         if (value < 0 || value > 2) return fail(ctx, KZG_ERR_SHAPE, "ntt_vec_log must be 0..2");
         ctx->opt_ntt_vec_log = (int)value;

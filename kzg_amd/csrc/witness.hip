@@ -127,6 +127,40 @@ int coset_ntt_run(kzg_ctx *ctx, int lane, Fr *d, uint32_t log_n, int inverse, co
     return unit ? (int)KZG_OK : distribute_powers(ctx, st, d, n, inv(g));
 }
 
+// distribute_powers over `rows` vectors of 2^log_n <= 2^20 elements, vector b at data + b * stride: element i of every vector times g^i
+// from the two cached tables (i < DP_TAB^2), the index taken inside its vector; the words between the vectors are not touched.
+__global__ __launch_bounds__(256) void k_distribute_powers_batch(Fr *data, uint32_t log_n, size_t stride, size_t rows, const Fr *lo_tab,
+                                                                  const Fr *hi_tab) {
+    const size_t total = rows << log_n;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = e & (((size_t)1 << log_n) - 1);
+        Fr *x = data + (e >> log_n) * stride + i;
+        *x = mul(*x, mul(hi_tab[i >> 10], lo_tab[i & (DP_TAB - 1)]));
+    }
+}
+
+// coset_ntt_run for a batch (kzg_coset_ntt_fr_batch): one scaling launch for all vectors in front of (forward) or behind (inverse)
+// ntt_batch_run; the sizes ntt_batch_run takes vector by vector go through coset_ntt_run as it is.
+int coset_ntt_batch_run(kzg_ctx *ctx, int lane, Fr *d, uint32_t log_n, size_t batch, size_t stride, int inverse, const Fr &g) {
+    if (ntt_batch_looped(ctx, log_n) || log_n > 20) {
+        for (size_t b = 0; b < batch; b++) {
+            const size_t mark = ctx->lanes[lane].arena_used;
+            KZG_TRY(coset_ntt_run(ctx, lane, d + b * stride, log_n, inverse, g));
+            ctx->lanes[lane].arena_used = mark;
+        }
+        return KZG_OK;
+    }
+    hipStream_t st = ctx->lanes[lane].stream;
+    const Fr *lo_tab = nullptr, *hi_tab = nullptr;
+    KZG_TRY(coset_tables(ctx, st, inverse ? inv(g) : g, &lo_tab, &hi_tab));
+    const size_t blocks = ((batch << log_n) + 255) / 256;
+    const unsigned grid = (unsigned)std::min<size_t>(blocks, (size_t)1 << 20);
+    if (!inverse) KZG_LAUNCH(ctx, st, "k_distribute_powers_batch", k_distribute_powers_batch, grid, 256, 0, d, log_n, stride, batch, lo_tab, hi_tab);
+    KZG_TRY(ntt_batch_run(ctx, lane, d, log_n, batch, stride, inverse));
+    if (inverse) KZG_LAUNCH(ctx, st, "k_distribute_powers_batch", k_distribute_powers_batch, grid, 256, 0, d, log_n, stride, batch, lo_tab, hi_tab);
+    return KZG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // interpolation through k points (k <= 16384: the k x k matrix of scaled quotients Z / (X - x_i) is 8.6 GB there)
 // ---------------------------------------------------------------------------------------------
