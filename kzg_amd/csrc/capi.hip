@@ -990,10 +990,7 @@ extern "C" int kzg_fr_fold(kzg_ctx *ctx, const void *vecs, size_t d, size_t t, s
     Fr *d_o = out_dev ? (Fr *)out : (Fr *)lane_alloc(ctx, lane, GC * d * 32);
     Fr *d_gam = (Fr *)lane_alloc(ctx, lane, groups * 32);
     if ((!in_dev && !d_in) || !d_o || !d_gam) return fail(ctx, KZG_ERR_ALLOC, "workspace");
-    struct Drain {  // nothing of the call is in flight once its host-side buffers go out of scope
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
+    StreamDrain drain{st};
     KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_gam, gm.data(), groups * 32, hipMemcpyHostToDevice, st));
     for (size_t g0 = 0; g0 < groups; g0 += GC) {
         const size_t G = std::min(GC, groups - g0);
@@ -1241,11 +1238,6 @@ struct MoBlob {  // host tables that go to the device in one copy
     }
 };
 
-struct MoDrain {  // nothing of the call is in flight once its host-side buffers go out of scope
-    hipStream_t st;
-    ~MoDrain() { hipStreamSynchronize(st); }
-};
-
 // the end of the four calls: g (len scalars on the device, sfmt) against the SRS -> the point at `out`; len == 0: the identity
 int mo_commit_point(kzg_ctx *ctx, const kzg_srs *srs, const Fr *d_g, size_t len, int sfmt, int flags, void *out, int ofmt) {
     MsmPoint *res = nullptr;
@@ -1329,7 +1321,7 @@ extern "C" int kzg_fr_lincomb(kzg_ctx *ctx, const void *vecs, size_t d, size_t n
     uint32_t *d_idx = (uint32_t *)lane_alloc(ctx, lane, std::max(count, P) * 4 + 4);
     if ((!in_dev && !d_in) || !d_o || !d_w || !d_idx) return fail(ctx, KZG_ERR_ALLOC, "workspace");
     std::vector<uint32_t> local;
-    MoDrain drain{st};
+    StreamDrain drain{st};
     if (count) KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_w, wm.data(), count * 32, hipMemcpyHostToDevice, st));
     if (in_dev) {
         if (count) KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_idx, idx, count * 4, hipMemcpyHostToDevice, st));
@@ -1435,7 +1427,7 @@ extern "C" int kzg_multiopen_eval_commit(kzg_ctx *ctx, const kzg_srs *lagrange, 
                                      (n_off ? align_up(open_powtab_bytes(d), 256) + 2 * align_up(ncap * d * 32, 256) + align_up(std::min<size_t>(max_claims, 65535) * nblk * 32, 256) : 0) +
                                      (n_on ? 2 * vec + align_up(nblk * 32, 256) : 0) + msm_workspace_bytes(lagrange, d) + 65536));
     std::vector<uint8_t> ys_sorted;  // (outlives the drain of the stream that fills it)
-    MoDrain drain{st};
+    StreamDrain drain{st};
     const void *d_polys = nullptr;
     if (count) KZG_TRY(stage_in(ctx, 0, evals, n_polys * d * 32, flags, &d_polys));  // host polynomials: once, whole
     Fr *d_g = g_dev ? (Fr *)g_out : (Fr *)lane_alloc(ctx, 0, d * 32);
@@ -1520,7 +1512,7 @@ extern "C" int kzg_multiopen_eval_finish(kzg_ctx *ctx, const kzg_srs *lagrange, 
     KZG_TRY(lane_reserve(ctx, 0, stage_bytes(n_polys * d * 32, flags) + stage_bytes(d * 32, flags) + 2 * vec + align_up(n_polys * 36 + 1024, 256) + 1024 +
                                      open_eval_fr_workspace_bytes(d, 1) + msm_workspace_bytes(lagrange, d) + 65536));
     MoBlob blob;  // (outlives the drain of the stream that reads it)
-    MoDrain drain{st};
+    StreamDrain drain{st};
     if (!count) {  // no claim: v = 0
         if (y_out) memset(y_out, 0, 32);
         if (out_pi) return mo_commit_point(ctx, lagrange, nullptr, 0, sfmt, flags, out_pi, ofmt);
@@ -1589,7 +1581,7 @@ extern "C" int kzg_multiopen_coeff_commit(kzg_ctx *ctx, const kzg_srs *srs, cons
     KZG_TRY(lane_reserve(ctx, 0, stage_bytes(n_polys * n * 32, flags) + 3 * vec + align_up(blob.h.size(), 256) + align_up(count * 32 + 32, 256) + 1024 + horner +
                                      msm_workspace_bytes(srs, glen) + 65536));
     std::vector<uint8_t> ys_sorted;  // (outlives the drain of the stream that fills it)
-    MoDrain drain{st};
+    StreamDrain drain{st};
     const void *d_polys = nullptr;
     if (count) KZG_TRY(stage_in(ctx, 0, coeffs, n_polys * n * 32, flags, &d_polys));  // host polynomials: once, whole
     Fr *d_g = g_dev ? (Fr *)g_out : (Fr *)lane_alloc(ctx, 0, glen * 32 + 32);
@@ -1657,7 +1649,7 @@ extern "C" int kzg_multiopen_coeff_finish(kzg_ctx *ctx, const kzg_srs *srs, cons
     KZG_TRY(lane_reserve(ctx, 0, stage_bytes(n_polys * n * 32, flags) + stage_bytes(n * 32, flags) + 2 * vec + align_up(n_polys * 36 + 1024, 256) + 1024 + horner +
                                      msm_workspace_bytes(srs, glen) + 65536));
     MoBlob blob;  // (outlives the drain of the stream that reads it)
-    MoDrain drain{st};
+    StreamDrain drain{st};
     if (!count) {
         if (y_out) memset(y_out, 0, 32);
         if (out_pi) return mo_commit_point(ctx, srs, nullptr, 0, sfmt, flags, out_pi, ofmt);

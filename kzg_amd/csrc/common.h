@@ -269,6 +269,11 @@ struct Lease {
 };
 int lease_lane(kzg_ctx *ctx, Lease *ls);
 
+struct StreamDrain {  // nothing of the call is in flight once its host-side buffers go out of scope
+    hipStream_t st;
+    ~StreamDrain() { hipStreamSynchronize(st); }
+};
+
 // validation of decoded points (what blstrs' G1Affine / G2Affine deserialisation enforces upstream):
 //   POINTS_TRUSTED   nothing (the engine's own intermediate results)
 //   POINTS_ON_CURVE  limbs canonical (< q) and on the curve

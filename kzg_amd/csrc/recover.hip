@@ -282,11 +282,6 @@ static int rec_ntt_each(kzg_ctx *ctx, int lane, size_t mark, Fr *d, size_t count
     return KZG_OK;
 }
 
-struct StreamDrain {  // nothing of the call is in flight once its host-side buffers go out of scope
-    hipStream_t st;
-    ~StreamDrain() { hipStreamSynchronize(st); }
-};
-
 }  // namespace kzg
 
 using namespace kzg;

@@ -301,10 +301,7 @@ extern "C" int kzg_verify_cosets(kzg_ctx *ctx, const kzg_cosets_verifier *plan, 
     const bool in_dev = (flags & KZG_IN_DEVICE) != 0;
     const size_t chunk = vc_chunk(ctx, plan), B0 = std::min(chunk, count);
     KZG_TRY(lane_reserve(ctx, lane, n_commitments * (psz + sizeof(G1Xyzz)) + B0 * (9 + psz + 2 * sizeof(G1Xyzz) + (in_dev ? 1 : 2) * l * 32) + 65536));
-    struct Drain {  // nothing of the call is in flight once its host-side buffers go out of scope
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
+    StreamDrain drain{st};
     int *bad = (int *)lane_alloc(ctx, lane, 256);
     uint8_t *d_ok = (uint8_t *)lane_alloc(ctx, lane, B0);
     uint32_t *d_ids = (uint32_t *)lane_alloc(ctx, lane, B0 * 4), *d_cidx = (uint32_t *)lane_alloc(ctx, lane, B0 * 4);

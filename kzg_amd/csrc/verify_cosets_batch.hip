@@ -14,6 +14,9 @@
 // window's 128 buckets to sum_b b B_b), the fixed-base sum of `a` (k_vc_sum) and the finish of vcb_finish.h on the calling thread or
 // in the one-thread kernel k_vcb_finish.  The buckets live in the lane arena for the whole call and every bucket has one owner
 // thread, so chunk after chunk adds into them without atomics.  DESIGN.md section 3.5f.
+//
+// The file also holds, next to the stages they launch, the driver core this call shares with the three of verify_eval_batch.hip
+// (vcb_shared.h): vcb_work, vcb_points, vcb_commit_weights, vcb_cagg.  vcb_run below is what is this call's alone.
 #include <algorithm>
 #include <chrono>
 #include <vector>
@@ -255,6 +258,67 @@ int vcb_conclude(kzg_ctx *ctx, int lane, const VcbSums *d_sums, const G2Affine *
     return KZG_OK;
 }
 
+// ---- the driver core behind vcb_shared.h -----------------------------------------------------------------------------------------
+int vcb_work(kzg_ctx *ctx, int lane, int pfmt, size_t B0, size_t BP, size_t c_count, size_t extra_bytes, size_t slots0, VcbWork *w) {
+    const size_t psz = point_format_bytes(pfmt), set = (size_t)VCB_G * VCB_SET, bucket_bytes = 3 * set * sizeof(G1Xyzz);
+    KZG_TRY(lane_reserve(ctx, lane, bucket_bytes + sizeof(VcbSums) + c_count * 32 + BP * (psz + sizeof(G1Xyzz)) + B0 * (3 * 4 + 3 * 32) +
+                                        extra_bytes + 65536));
+    w->ctx = ctx;
+    w->lane = lane;
+    w->pfmt = pfmt;
+    w->st = ctx->lanes[lane].stream;
+    w->psz = psz;
+    w->BP = BP;
+    w->slots = slots0;
+    w->bad = (int *)lane_alloc(ctx, lane, 256);
+    w->d_ok = (uint8_t *)lane_alloc(ctx, lane, 256);
+    w->d_parts = (G1Affine *)lane_alloc(ctx, lane, 4 * sizeof(G1Affine));
+    G1Xyzz *bk = (G1Xyzz *)lane_alloc(ctx, lane, bucket_bytes);
+    w->sums = (VcbSums *)lane_alloc(ctx, lane, sizeof(VcbSums));
+    w->d_c = (Fr *)lane_alloc(ctx, lane, c_count * 32);
+    w->d_which = (uint32_t *)lane_alloc(ctx, lane, B0 * 4);
+    w->d_start = (uint32_t *)lane_alloc(ctx, lane, (B0 + 1) * 4);
+    w->d_order = (uint32_t *)lane_alloc(ctx, lane, B0 * 4);
+    w->d_rho = (Fr *)lane_alloc(ctx, lane, B0 * 32);
+    w->d_s1 = (Fr *)lane_alloc(ctx, lane, B0 * 32);
+    w->d_s2 = (Fr *)lane_alloc(ctx, lane, B0 * 32);
+    w->raw = (uint8_t *)lane_alloc(ctx, lane, BP * psz);
+    w->W = (G1Xyzz *)lane_alloc(ctx, lane, BP * sizeof(G1Xyzz));
+    if (!w->bad || !w->d_ok || !w->d_parts || !bk || !w->sums || !w->d_c || !w->d_which || !w->d_start || !w->d_order || !w->d_rho ||
+        !w->d_s1 || !w->d_s2 || !w->raw || !w->W)
+        return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    for (int s = 0; s < 3; s++) w->bk[s] = bk + s * set;
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(w->bad, 0, sizeof(int), w->st));
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(bk, 0, bucket_bytes, w->st));  // zz = 0: the identity
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(w->d_c, 0, c_count * 32, w->st));
+    return KZG_OK;
+}
+
+int vcb_points(VcbWork *w, const void *src, size_t B, const Fr *sc0, const Fr *sc1, G1Xyzz *bk0, G1Xyzz *bk1, int sets) {
+    KZG_HIP_CHECK(w->ctx, hipMemcpyAsync(w->raw, src, B * w->psz, hipMemcpyHostToDevice, w->st));
+    KZG_TRY(decode_points(w->ctx, w->st, w->raw, B, w->pfmt, w->W, w->bad, untrusted_level(w->ctx)));
+    KZG_TRY(vb_accumulate(w->ctx, w->st, (const G1Xyzz *)w->W, sc0, sc1, B, bk0, bk1, sets));
+    w->slots = std::max(w->slots, (B + VCB_S - 1) / VCB_S);
+    return KZG_OK;
+}
+
+int vcb_commit_weights(VcbWork *w, VcbLists *lists, const uint32_t *cm, size_t B) {
+    const size_t n = lists->build(cm, B);
+    KZG_HIP_CHECK(w->ctx, hipMemcpyAsync(w->d_which, lists->which.data(), n * 4, hipMemcpyHostToDevice, w->st));
+    KZG_HIP_CHECK(w->ctx, hipMemcpyAsync(w->d_start, lists->start.data(), (n + 1) * 4, hipMemcpyHostToDevice, w->st));
+    KZG_HIP_CHECK(w->ctx, hipMemcpyAsync(w->d_order, lists->order.data(), B * 4, hipMemcpyHostToDevice, w->st));
+    return vcb_cweights(w->ctx, w->st, w->d_rho, w->d_which, w->d_start, w->d_order, n, w->d_c);
+}
+
+int vcb_cagg(VcbWork *w, const void *commitments, size_t n_commitments) {
+    for (size_t m0 = 0; m0 < n_commitments; m0 += w->BP) {
+        const size_t B = std::min(w->BP, n_commitments - m0);
+        KZG_TRY(vcb_canon(w->ctx, w->st, w->d_c + m0, B, 1, w->d_c + m0));
+        KZG_TRY(vcb_points(w, (const uint8_t *)commitments + m0 * w->psz, B, w->d_c + m0, w->d_c + m0, w->bk[2], w->bk[2], 1));
+    }
+    return KZG_OK;
+}
+
 namespace {
 struct BatchParts {  // the extra outputs of kzg_test_verify_cosets_batch_parts (host)
     void *a = nullptr, *cw = nullptr, *points = nullptr;
@@ -282,16 +346,15 @@ int vcb_run(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitmen
     const size_t l = (size_t)1 << log_l, K = (size_t)1 << (plan->log_n - log_l);
     if (count > (SIZE_MAX >> 6) / l || n_commitments > (SIZE_MAX >> 9)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": count too large");
     const size_t chunk = vc_chunk(ctx, plan), B0 = std::min(chunk, count), BP = std::min(chunk, std::max(count, n_commitments));
-    std::vector<uint32_t> meta, cnt, which, start, order;  // ids, then commitment indices, as the kernels read them; the counting sort
+    std::vector<uint32_t> meta;  // ids, then commitment indices, as the kernels read them
+    VcbLists lists;
+    bool room = lists.reserve(n_commitments, B0);
     try {  // (no exception may leave through the C ABI)
         meta.resize(2 * count);
-        cnt.assign(n_commitments, 0);
-        which.resize(B0);
-        start.resize(B0 + 1);
-        order.resize(B0);
     } catch (const std::bad_alloc &) {
-        return fail(ctx, KZG_ERR_ALLOC, std::string(who) + ": host memory for the ids");
+        room = false;
     }
+    if (!room) return fail(ctx, KZG_ERR_ALLOC, std::string(who) + ": host memory for the ids");
     for (size_t k = 0; k < count; k++) {
         if (coset_ids[k] >= K) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": coset id >= K");
         if (commitment_idx[k] >= n_commitments) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": commitment index >= n_commitments");
@@ -304,91 +367,43 @@ int vcb_run(kzg_ctx *ctx, const kzg_cosets_verifier *plan, const void *commitmen
     const int lane = ls.lane;
     KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->lanes[lane].stream;
+    StreamDrain drain{st};
     const bool in_dev = (flags & KZG_IN_DEVICE) != 0;
-    const size_t fold_blocks = (B0 + VCB_FOLD_CELLS - 1) / VCB_FOLD_CELLS, bucket_bytes = 3 * (size_t)VCB_G * VCB_SET * sizeof(G1Xyzz);
-    KZG_TRY(lane_reserve(ctx, lane, bucket_bytes + sizeof(VcbSums) + n_commitments * 32 + BP * (psz + sizeof(G1Xyzz)) +
-                                        B0 * (4 * 4 + 3 * 32 + (in_dev ? 1 : 2) * l * 32) + (fold_blocks + 1) * l * 32 + 65536));
-    struct Drain {  // nothing of the call is in flight once its host-side buffers go out of scope
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
-    int *bad = (int *)lane_alloc(ctx, lane, 256);
-    uint8_t *d_ok = (uint8_t *)lane_alloc(ctx, lane, 256);
-    G1Affine *d_parts = (G1Affine *)lane_alloc(ctx, lane, 4 * sizeof(G1Affine));
-    G1Xyzz *bk = (G1Xyzz *)lane_alloc(ctx, lane, bucket_bytes);
-    VcbSums *sums = (VcbSums *)lane_alloc(ctx, lane, sizeof(VcbSums));
+    const size_t fold_blocks = (B0 + VCB_FOLD_CELLS - 1) / VCB_FOLD_CELLS;
+    VcbWork w;  // no gs[0] pair here: no slice slot is in use before the first chunk
+    KZG_TRY(vcb_work(ctx, lane, pfmt, B0, BP, std::max<size_t>(n_commitments, 1), B0 * (4 + (in_dev ? 1 : 2) * l * 32) + (fold_blocks + 1) * l * 32, 0, &w));
     Fr *d_a = (Fr *)lane_alloc(ctx, lane, l * 32), *d_part = (Fr *)lane_alloc(ctx, lane, fold_blocks * l * 32);
-    Fr *d_c = (Fr *)lane_alloc(ctx, lane, std::max<size_t>(n_commitments, 1) * 32);
-    uint32_t *d_ids = (uint32_t *)lane_alloc(ctx, lane, B0 * 4), *d_which = (uint32_t *)lane_alloc(ctx, lane, B0 * 4);
-    uint32_t *d_start = (uint32_t *)lane_alloc(ctx, lane, (B0 + 1) * 4), *d_order = (uint32_t *)lane_alloc(ctx, lane, B0 * 4);
-    Fr *d_rho = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_s1 = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_s2 = (Fr *)lane_alloc(ctx, lane, B0 * 32);
+    uint32_t *d_ids = (uint32_t *)lane_alloc(ctx, lane, B0 * 4);
     Fr *d_cells = in_dev ? nullptr : (Fr *)lane_alloc(ctx, lane, B0 * l * 32), *d_r = (Fr *)lane_alloc(ctx, lane, B0 * l * 32);
-    uint8_t *raw = (uint8_t *)lane_alloc(ctx, lane, BP * psz);
-    G1Xyzz *W = (G1Xyzz *)lane_alloc(ctx, lane, BP * sizeof(G1Xyzz));
-    if (!bad || !d_ok || !d_parts || !bk || !sums || !d_a || !d_part || !d_c || !d_ids || !d_which || !d_start || !d_order || !d_rho || !d_s1 ||
-        !d_s2 || (!in_dev && !d_cells) || !d_r || !raw || !W)
-        return fail(ctx, KZG_ERR_ALLOC, "workspace");
-    G1Xyzz *bk1 = bk, *bk2 = bk + (size_t)VCB_G * VCB_SET, *bk3 = bk + 2 * (size_t)VCB_G * VCB_SET;
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(bad, 0, sizeof(int), st));
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(bk, 0, bucket_bytes, st));  // zz = 0: the identity
+    if (!d_a || !d_part || !d_ids || (!in_dev && !d_cells) || !d_r) return fail(ctx, KZG_ERR_ALLOC, "workspace");
     KZG_HIP_CHECK(ctx, hipMemsetAsync(d_a, 0, l * 32, st));
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(d_c, 0, std::max<size_t>(n_commitments, 1) * 32, st));
-    size_t slots = 0;  // slice slots any chunk has used
     for (size_t k0 = 0; k0 < count; k0 += chunk) {
         const size_t B = std::min(chunk, count - k0);
-        // the chunk's cells listed per commitment, commitments in the order of their first cell
-        size_t lists = 0;
-        const uint32_t *cm = meta.data() + count + k0;
-        for (size_t k = 0; k < B; k++)
-            if (!cnt[cm[k]]++) which[lists++] = cm[k];
-        uint32_t at = 0;
-        for (size_t g = 0; g < lists; g++) {
-            start[g] = at;
-            at += cnt[which[g]];
-            cnt[which[g]] = start[g];
-        }
-        start[lists] = at;
-        for (size_t k = 0; k < B; k++) order[cnt[cm[k]]++] = (uint32_t)k;
-        for (size_t g = 0; g < lists; g++) cnt[which[g]] = 0;
         KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_ids, meta.data() + k0, B * 4, hipMemcpyHostToDevice, st));
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_which, which.data(), lists * 4, hipMemcpyHostToDevice, st));
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_start, start.data(), (lists + 1) * 4, hipMemcpyHostToDevice, st));
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_order, order.data(), B * 4, hipMemcpyHostToDevice, st));
         const Fr *src = (const Fr *)((const uint8_t *)cells + k0 * l * 32);
         if (!in_dev) {
             KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_cells, src, B * l * 32, hipMemcpyHostToDevice, st));
             src = d_cells;
         }
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)proofs + k0 * psz, B * psz, hipMemcpyHostToDevice, st));
-        KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
-        KZG_TRY(powers_run(ctx, st, rm, k0, B, d_rho));
+        KZG_TRY(powers_run(ctx, st, rm, k0, B, w.d_rho));
         KZG_TRY(vc_interp(ctx, st, plan, src, d_ids, B, d_r));
-        KZG_LAUNCH(ctx, st, "k_vcb_scalars", k_vcb_scalars, vcb_grid(B), 256, 0, (const Fr *)d_rho, (const uint32_t *)d_ids, B, log_l,
-                   (const Fr *)plan->pos_lo, (const Fr *)plan->pos_hi, d_s1, d_s2);
-        KZG_TRY(vcb_fold(ctx, st, d_r, d_rho, B, log_l, d_part, d_a));
-        KZG_TRY(vcb_cweights(ctx, st, d_rho, d_which, d_start, d_order, lists, d_c));
-        KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_s1, d_s2, B, bk1, bk2, 2));
-        slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
+        KZG_LAUNCH(ctx, st, "k_vcb_scalars", k_vcb_scalars, vcb_grid(B), 256, 0, (const Fr *)w.d_rho, (const uint32_t *)d_ids, B, log_l,
+                   (const Fr *)plan->pos_lo, (const Fr *)plan->pos_hi, w.d_s1, w.d_s2);
+        KZG_TRY(vcb_fold(ctx, st, d_r, w.d_rho, B, log_l, d_part, d_a));                                    // a
+        KZG_TRY(vcb_commit_weights(&w, &lists, meta.data() + count + k0, B));                               // c
+        KZG_TRY(vcb_points(&w, (const uint8_t *)proofs + k0 * psz, B, w.d_s1, w.d_s2, w.bk[0], w.bk[1], 2));  // P1, P2
         // the host lists and the chunk's device buffers are free again
         KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
     }
-    // Cagg: the commitments against the canonical c, in chunks like the cells (d_s1 holds a chunk's scalars)
-    for (size_t m0 = 0; m0 < n_commitments; m0 += BP) {
-        const size_t B = std::min(BP, n_commitments - m0);
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)commitments + m0 * psz, B * psz, hipMemcpyHostToDevice, st));
-        KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
-        KZG_TRY(vcb_canon(ctx, st, d_c + m0, B, 1, d_c + m0));
-        KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_c + m0, d_c + m0, B, bk3, bk3, 1));
-        slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
-    }
-    KZG_TRY(vb_reduce(ctx, st, bk, (uint32_t)slots, sums));
-    KZG_TRY(vc_sum(ctx, st, plan, d_a, 1, sfmt, &sums->ragg));
+    KZG_TRY(vcb_cagg(&w, commitments, n_commitments));
+    KZG_TRY(vb_reduce(ctx, st, w.bk[0], (uint32_t)w.slots, w.sums));
+    KZG_TRY(vc_sum(ctx, st, plan, d_a, 1, sfmt, &w.sums->ragg));
     if (parts) {
         if (sfmt == KZG_FR_MONT_LE_32) KZG_TRY(vcb_canon(ctx, st, d_a, l, 1, d_a));
         KZG_HIP_CHECK(ctx, hipMemcpyAsync(parts->a, d_a, l * 32, hipMemcpyDeviceToHost, st));
-        if (n_commitments) KZG_HIP_CHECK(ctx, hipMemcpyAsync(parts->cw, d_c, n_commitments * 32, hipMemcpyDeviceToHost, st));
+        if (n_commitments) KZG_HIP_CHECK(ctx, hipMemcpyAsync(parts->cw, w.d_c, n_commitments * 32, hipMemcpyDeviceToHost, st));
     }
-    return vcb_conclude(ctx, lane, sums, plan->hq, plan->lines, plan->h_hq, plan->h_lines, bad, d_ok, d_parts, parts ? parts->points : nullptr, ok);
+    return vcb_conclude(ctx, lane, w.sums, plan->hq, plan->lines, plan->h_hq, plan->h_lines, w.bad, w.d_ok, w.d_parts, parts ? parts->points : nullptr, ok);
 }
 }  // namespace
 

@@ -14,6 +14,11 @@
 // loop; with indices k_vcb_cweights per chunk and the commitments against c after the last chunk.  (gs[0], -yagg) rides as one more
 // pair of the third set, so the set's total is Cagg - [yagg] gs[0] and the Ragg slot of the finish stays the identity.  Then
 // k_vcb_reduce and the finish of vcb_finish.h, on the calling thread or in k_vcb_finish.  DESIGN.md section 3.5g.
+//
+// kzg_verify_fold (vf_run) and kzg_verify_multiopen (vm_run) are the same equation with other weights, and live here for that.  All
+// three stand on the driver core of vcb_shared.h (workspace, points into buckets, commitment weights, the Cagg loop) and on what only
+// they share, below: veb_front / veb_chunks (the shape checks and the chunk rule), veb_work, veb_witnesses, veb_weighted, veb_finish.
+// What is left in a driver is its own mathematics: which points meet which scalars, in which pass.
 #include <algorithm>
 #include <vector>
 
@@ -43,6 +48,90 @@ __global__ void k_veb_yagg(const Fr *y, int is_mont, Fr *yc, Fr *yn) {
 }
 
 namespace {
+// ---- what the three calls of this file share beyond the core of vcb_shared.h ----
+// The first shape checks, in the name of `who`; `points` is what the call's encoded points are.  Nothing is touched.
+int veb_front(kzg_ctx *ctx, const char *who, const char *points, const kzg_srs *gs, const kzg_srs_g2 *hs, int sfmt, int pfmt) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    if (!gs || !hs) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL SRS");
+    if (sfmt != KZG_FR_MONT_LE_32 && sfmt != KZG_FR_CANONICAL_LE_32) return fail(ctx, KZG_ERR_SHAPE, "unknown scalar format");
+    if (!point_format_bytes(pfmt) || pfmt == KZG_G1_JACOBIAN_MONT_144) return fail(ctx, KZG_ERR_SHAPE, std::string(points) + " are affine (G1Affine)");
+    if (gs->n < 1 || hs->n < 2) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + " needs gs[0], hs[0], hs[1]");
+    if (gs->device != ctx->device || hs->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the SRS is resident on another GPU than this context's");
+    return KZG_OK;
+}
+
+struct VebChunks {
+    bool indexed;
+    size_t chunk, B0, BP;  // openings per chunk | of the largest chunk | points the largest step decodes at once
+};
+// one commitment per `word` unless the call has indices, then the chunk rule (option verify_eval_batch_chunk lowers VEB_CHUNK)
+int veb_chunks(kzg_ctx *ctx, const char *who, const char *word, size_t count, size_t n_commitments, const uint32_t *commitment_idx, VebChunks *c) {
+    c->indexed = commitment_idx != nullptr;
+    if (!c->indexed && n_commitments != count) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": without indices there is one commitment per " + word);
+    c->chunk = VEB_CHUNK;
+    if (ctx->opt_verify_eval_batch_chunk > 0) c->chunk = std::min(c->chunk, (size_t)ctx->opt_verify_eval_batch_chunk);
+    c->B0 = std::min(c->chunk, count);
+    c->BP = c->indexed ? std::min(c->chunk, std::max(count, n_commitments)) : c->B0;
+    return KZG_OK;
+}
+int veb_indices(kzg_ctx *ctx, const char *who, const uint32_t *commitment_idx, size_t count, size_t n_commitments) {
+    for (size_t k = 0; k < count; k++)
+        if (commitment_idx[k] >= n_commitments) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": commitment index >= n_commitments");
+    return KZG_OK;
+}
+
+struct VebWork : VcbWork {
+    int is_mont;
+    Fr *d_x, *d_y;  // a chunk's points and values, in the caller's scalar format
+    Fr *d_yagg;     // yagg (sfmt), yagg, -yagg (canonical)
+    Fr *d_part;     // the fold's scratch
+};
+int veb_work(kzg_ctx *ctx, int lane, int sfmt, int pfmt, const VebChunks &c, size_t n_commitments, VebWork *w) {
+    const size_t fold_blocks = (c.B0 + VCB_FOLD_CELLS - 1) / VCB_FOLD_CELLS;
+    // gs[0] takes slice slot 0 in the end (and so do the single points of kzg_verify_multiopen)
+    KZG_TRY(vcb_work(ctx, lane, pfmt, c.B0, c.BP, c.indexed ? std::max<size_t>(n_commitments, 1) : 1, c.B0 * 2 * 32 + (fold_blocks + 4) * 32, 1, w));
+    w->is_mont = sfmt == KZG_FR_MONT_LE_32 ? 1 : 0;
+    w->d_yagg = (Fr *)lane_alloc(ctx, lane, 3 * 32);
+    w->d_part = (Fr *)lane_alloc(ctx, lane, fold_blocks * 32);
+    w->d_x = (Fr *)lane_alloc(ctx, lane, c.B0 * 32);
+    w->d_y = (Fr *)lane_alloc(ctx, lane, c.B0 * 32);
+    if (!w->d_yagg || !w->d_part || !w->d_x || !w->d_y) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(w->sums, 0, sizeof(VcbSums), w->st));  // the Ragg slot stays the identity
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(w->d_yagg, 0, 3 * 32, w->st));
+    return KZG_OK;
+}
+
+// Witnesses k0 .. k0 + B of the call against r^k and r^k x_k: P1 and P2.  Leaves rho in w->d_rho and rho canonical in w->d_s1.
+int veb_witnesses(VebWork *w, const Fr &rm, const void *xs, const void *witnesses, size_t k0, size_t B) {
+    KZG_HIP_CHECK(w->ctx, hipMemcpyAsync(w->d_x, (const uint8_t *)xs + k0 * 32, B * 32, hipMemcpyHostToDevice, w->st));
+    KZG_TRY(powers_run(w->ctx, w->st, rm, k0, B, w->d_rho));
+    KZG_LAUNCH(w->ctx, w->st, "k_veb_scalars", k_veb_scalars, vcb_grid(B), 256, 0, (const Fr *)w->d_rho, (const Fr *)w->d_x, B, w->is_mont, w->d_s1, w->d_s2);
+    return vcb_points(w, (const uint8_t *)witnesses + k0 * w->psz, B, w->d_s1, w->d_s2, w->bk[0], w->bk[1], 2);
+}
+
+// Values k0 .. k0 + B of the call and their commitments against the chunk's weights rho, formed on the host (Montgomery): yagg +=
+// sum_k rho_k y_k, and c += the weights per commitment or, one commitment per value (commitment_idx null: c_k = rho_k), the chunk's
+// commitments into the third set at once
+int veb_weighted(VebWork *w, VcbLists *lists, const Fr *rho, const void *ys, const uint32_t *commitment_idx, const void *commitments, size_t k0,
+                 size_t B) {
+    KZG_HIP_CHECK(w->ctx, hipMemcpyAsync(w->d_rho, rho, B * 32, hipMemcpyHostToDevice, w->st));
+    KZG_HIP_CHECK(w->ctx, hipMemcpyAsync(w->d_y, (const uint8_t *)ys + k0 * 32, B * 32, hipMemcpyHostToDevice, w->st));
+    KZG_TRY(vcb_fold(w->ctx, w->st, w->d_y, w->d_rho, B, 0, w->d_part, w->d_yagg));
+    if (commitment_idx) return vcb_commit_weights(w, lists, commitment_idx + k0, B);
+    KZG_TRY(vcb_canon(w->ctx, w->st, w->d_rho, B, 1, w->d_s1));
+    return vcb_points(w, (const uint8_t *)commitments + k0 * w->psz, B, w->d_s1, w->d_s1, w->bk[2], w->bk[2], 1);
+}
+
+// The end: - [yagg] gs[0] as one more pair of the third set (row 0 of the SRS table is gs itself), the reduction, the pairing check.
+// out_yagg, out_points (may be null): the outputs of kzg_test_verify_eval_batch_parts.
+int veb_finish(VebWork *w, const kzg_srs *gs, const kzg_srs_g2 *hs, void *out_yagg, void *out_points, int *ok) {
+    KZG_LAUNCH(w->ctx, w->st, "k_veb_yagg", k_veb_yagg, 1, 1, 0, (const Fr *)w->d_yagg, w->is_mont, w->d_yagg + 1, w->d_yagg + 2);
+    KZG_TRY(vb_accumulate(w->ctx, w->st, (const G1Affine *)gs->table, w->d_yagg + 2, w->d_yagg + 2, 1, w->bk[2], w->bk[2], 1));
+    KZG_TRY(vb_reduce(w->ctx, w->st, w->bk[0], (uint32_t)w->slots, w->sums));
+    if (out_yagg) KZG_HIP_CHECK(w->ctx, hipMemcpyAsync(out_yagg, w->d_yagg + 1, 32, hipMemcpyDeviceToHost, w->st));
+    return vcb_conclude(w->ctx, w->lane, w->sums, hs->pts, hs->lines, hs->h_pts, hs->h_lines, w->bad, w->d_ok, w->d_parts, out_points, ok);
+}
+
 struct EvalParts {  // the extra outputs of kzg_test_verify_eval_batch_parts (host)
     void *yagg = nullptr, *cw = nullptr, *points = nullptr;
 };
@@ -52,13 +141,7 @@ int veb_run(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *x
             const EvalParts *parts) {
     const char *who = "kzg_verify_eval_batch";
     // ---- shape: everything is decided before memory is touched or a kernel launched ----
-    if (!ctx) return KZG_ERR_SHAPE;
-    if (!gs || !hs) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL SRS");
-    if (sfmt != KZG_FR_MONT_LE_32 && sfmt != KZG_FR_CANONICAL_LE_32) return fail(ctx, KZG_ERR_SHAPE, "unknown scalar format");
-    const size_t psz = point_format_bytes(pfmt);
-    if (!psz || pfmt == KZG_G1_JACOBIAN_MONT_144) return fail(ctx, KZG_ERR_SHAPE, "commitments / witnesses are affine (G1Affine)");
-    if (gs->n < 1 || hs->n < 2) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + " needs gs[0], hs[0], hs[1]");
-    if (gs->device != ctx->device || hs->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the SRS is resident on another GPU than this context's");
+    KZG_TRY(veb_front(ctx, who, "commitments / witnesses", gs, hs, sfmt, pfmt));
     if (!count) {
         if (ok) *ok = 1;
         return KZG_OK;
@@ -67,137 +150,53 @@ int veb_run(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *x
     Fr rm;
     KZG_TRY(load_challenge(ctx, who, r, sfmt, &rm));
     if (count > (SIZE_MAX >> 9) || n_commitments > (SIZE_MAX >> 9)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": count too large");
-    const bool indexed = commitment_idx != nullptr;
-    if (!indexed && n_commitments != count) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": without indices there is one commitment per opening");
-    size_t chunk = VEB_CHUNK;
-    if (ctx->opt_verify_eval_batch_chunk > 0) chunk = std::min(chunk, (size_t)ctx->opt_verify_eval_batch_chunk);
-    const size_t B0 = std::min(chunk, count), BP = indexed ? std::min(chunk, std::max(count, n_commitments)) : B0;
-    std::vector<uint32_t> cnt, which, start, order;  // the counting sort of a chunk's openings by commitment
-    if (indexed) {
-        for (size_t k = 0; k < count; k++)
-            if (commitment_idx[k] >= n_commitments) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": commitment index >= n_commitments");
-        try {  // (no exception may leave through the C ABI)
-            cnt.assign(n_commitments, 0);
-            which.resize(B0);
-            start.resize(B0 + 1);
-            order.resize(B0);
-        } catch (const std::bad_alloc &) {
-            return fail(ctx, KZG_ERR_ALLOC, std::string(who) + ": host memory for the indices");
-        }
+    VebChunks c;
+    KZG_TRY(veb_chunks(ctx, who, "opening", count, n_commitments, commitment_idx, &c));
+    VcbLists lists;
+    if (c.indexed) {
+        KZG_TRY(veb_indices(ctx, who, commitment_idx, count, n_commitments));
+        if (!lists.reserve(n_commitments, c.B0)) return fail(ctx, KZG_ERR_ALLOC, std::string(who) + ": host memory for the indices");
     }
 
     kzg::Lease ls;
     KZG_TRY(lease_lane(ctx, &ls));
-    const int lane = ls.lane;
     KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->lanes[lane].stream;
-    const int is_mont = sfmt == KZG_FR_MONT_LE_32 ? 1 : 0;
-    const size_t fold_blocks = (B0 + VCB_FOLD_CELLS - 1) / VCB_FOLD_CELLS, bucket_bytes = 3 * (size_t)VCB_G * VCB_SET * sizeof(G1Xyzz);
-    const size_t c_bytes = indexed ? std::max<size_t>(n_commitments, 1) * 32 : 32;
-    KZG_TRY(lane_reserve(ctx, lane, bucket_bytes + sizeof(VcbSums) + c_bytes + (BP + (indexed ? 0 : B0)) * (psz + sizeof(G1Xyzz)) +
-                                        B0 * (3 * 4 + 5 * 32) + (fold_blocks + 4) * 32 + 65536));
-    struct Drain {  // nothing of the call is in flight once its host-side buffers go out of scope
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
-    int *bad = (int *)lane_alloc(ctx, lane, 256);
-    uint8_t *d_ok = (uint8_t *)lane_alloc(ctx, lane, 256);
-    G1Affine *d_parts = (G1Affine *)lane_alloc(ctx, lane, 4 * sizeof(G1Affine));
-    G1Xyzz *bk = (G1Xyzz *)lane_alloc(ctx, lane, bucket_bytes);
-    VcbSums *sums = (VcbSums *)lane_alloc(ctx, lane, sizeof(VcbSums));
-    Fr *d_yagg = (Fr *)lane_alloc(ctx, lane, 3 * 32), *d_part = (Fr *)lane_alloc(ctx, lane, fold_blocks * 32);  // yagg (sfmt), yagg, -yagg
-    Fr *d_c = (Fr *)lane_alloc(ctx, lane, c_bytes);
-    uint32_t *d_which = (uint32_t *)lane_alloc(ctx, lane, B0 * 4), *d_start = (uint32_t *)lane_alloc(ctx, lane, (B0 + 1) * 4);
-    uint32_t *d_order = (uint32_t *)lane_alloc(ctx, lane, B0 * 4);
-    Fr *d_rho = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_s1 = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_s2 = (Fr *)lane_alloc(ctx, lane, B0 * 32);
-    Fr *d_x = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_y = (Fr *)lane_alloc(ctx, lane, B0 * 32);
-    uint8_t *raw = (uint8_t *)lane_alloc(ctx, lane, BP * psz);
-    G1Xyzz *W = (G1Xyzz *)lane_alloc(ctx, lane, BP * sizeof(G1Xyzz));
-    uint8_t *raw_c = indexed ? raw : (uint8_t *)lane_alloc(ctx, lane, B0 * psz);  // a chunk's commitments next to its witnesses
-    G1Xyzz *Cm = indexed ? W : (G1Xyzz *)lane_alloc(ctx, lane, B0 * sizeof(G1Xyzz));
-    if (!bad || !d_ok || !d_parts || !bk || !sums || !d_yagg || !d_part || !d_c || !d_which || !d_start || !d_order || !d_rho || !d_s1 || !d_s2 ||
-        !d_x || !d_y || !raw || !W || !raw_c || !Cm)
-        return fail(ctx, KZG_ERR_ALLOC, "workspace");
-    G1Xyzz *bk1 = bk, *bk2 = bk + (size_t)VCB_G * VCB_SET, *bk3 = bk + 2 * (size_t)VCB_G * VCB_SET;
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(bad, 0, sizeof(int), st));
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(bk, 0, bucket_bytes, st));         // zz = 0: the identity
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(sums, 0, sizeof(VcbSums), st));    // the Ragg slot stays the identity
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(d_yagg, 0, 3 * 32, st));
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(d_c, 0, c_bytes, st));
-    size_t slots = 1;  // slice slots any chunk has used (gs[0] takes slot 0)
-    for (size_t k0 = 0; k0 < count; k0 += chunk) {
-        const size_t B = std::min(chunk, count - k0);
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_x, (const uint8_t *)xs + k0 * 32, B * 32, hipMemcpyHostToDevice, st));
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_y, (const uint8_t *)ys + k0 * 32, B * 32, hipMemcpyHostToDevice, st));
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)witnesses + k0 * psz, B * psz, hipMemcpyHostToDevice, st));
-        KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
-        KZG_TRY(powers_run(ctx, st, rm, k0, B, d_rho));
-        KZG_LAUNCH(ctx, st, "k_veb_scalars", k_veb_scalars, vcb_grid(B), 256, 0, (const Fr *)d_rho, (const Fr *)d_x, B, is_mont, d_s1, d_s2);
-        KZG_TRY(vcb_fold(ctx, st, d_y, d_rho, B, 0, d_part, d_yagg));
-        KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_s1, d_s2, B, bk1, bk2, 2));
-        if (indexed) {  // the chunk's openings listed per commitment, commitments in the order of their first opening
-            size_t lists = 0;
-            const uint32_t *cm = commitment_idx + k0;
-            for (size_t k = 0; k < B; k++)
-                if (!cnt[cm[k]]++) which[lists++] = cm[k];
-            uint32_t at = 0;
-            for (size_t g = 0; g < lists; g++) {
-                start[g] = at;
-                at += cnt[which[g]];
-                cnt[which[g]] = start[g];
-            }
-            start[lists] = at;
-            for (size_t k = 0; k < B; k++) order[cnt[cm[k]]++] = (uint32_t)k;
-            for (size_t g = 0; g < lists; g++) cnt[which[g]] = 0;
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_which, which.data(), lists * 4, hipMemcpyHostToDevice, st));
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_start, start.data(), (lists + 1) * 4, hipMemcpyHostToDevice, st));
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_order, order.data(), B * 4, hipMemcpyHostToDevice, st));
-            KZG_TRY(vcb_cweights(ctx, st, d_rho, d_which, d_start, d_order, lists, d_c));
+    hipStream_t st = ctx->lanes[ls.lane].stream;
+    StreamDrain drain{st};
+    VebWork w;
+    KZG_TRY(veb_work(ctx, ls.lane, sfmt, pfmt, c, n_commitments, &w));
+    for (size_t k0 = 0; k0 < count; k0 += c.chunk) {
+        const size_t B = std::min(c.chunk, count - k0);
+        KZG_TRY(veb_witnesses(&w, rm, xs, witnesses, k0, B));
+        KZG_HIP_CHECK(ctx, hipMemcpyAsync(w.d_y, (const uint8_t *)ys + k0 * 32, B * 32, hipMemcpyHostToDevice, st));
+        KZG_TRY(vcb_fold(ctx, st, w.d_y, w.d_rho, B, 0, w.d_part, w.d_yagg));
+        if (c.indexed) {
+            KZG_TRY(vcb_commit_weights(&w, &lists, commitment_idx + k0, B));
         } else {  // c_k = rho_k: the chunk's commitments into the third set at once
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw_c, (const uint8_t *)commitments + k0 * psz, B * psz, hipMemcpyHostToDevice, st));
-            KZG_TRY(decode_points(ctx, st, raw_c, B, pfmt, Cm, bad, untrusted_level(ctx)));
-            KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)Cm, d_s1, d_s1, B, bk3, bk3, 1));
-            if (parts) KZG_HIP_CHECK(ctx, hipMemcpyAsync((uint8_t *)parts->cw + k0 * 32, d_s1, B * 32, hipMemcpyDeviceToHost, st));
+            KZG_TRY(vcb_points(&w, (const uint8_t *)commitments + k0 * w.psz, B, w.d_s1, w.d_s1, w.bk[2], w.bk[2], 1));
+            if (parts) KZG_HIP_CHECK(ctx, hipMemcpyAsync((uint8_t *)parts->cw + k0 * 32, w.d_s1, B * 32, hipMemcpyDeviceToHost, st));
         }
-        slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
         // the host lists and the chunk's device buffers are free again
         KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
     }
-    if (indexed) {  // Cagg: the commitments against the canonical c, in chunks like the openings
-        for (size_t m0 = 0; m0 < n_commitments; m0 += BP) {
-            const size_t B = std::min(BP, n_commitments - m0);
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)commitments + m0 * psz, B * psz, hipMemcpyHostToDevice, st));
-            KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
-            KZG_TRY(vcb_canon(ctx, st, d_c + m0, B, 1, d_c + m0));
-            KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_c + m0, d_c + m0, B, bk3, bk3, 1));
-            slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
-        }
-        if (parts) KZG_HIP_CHECK(ctx, hipMemcpyAsync(parts->cw, d_c, n_commitments * 32, hipMemcpyDeviceToHost, st));
+    if (c.indexed) {
+        KZG_TRY(vcb_cagg(&w, commitments, n_commitments));
+        if (parts) KZG_HIP_CHECK(ctx, hipMemcpyAsync(parts->cw, w.d_c, n_commitments * 32, hipMemcpyDeviceToHost, st));
     }
-    // - [yagg] gs[0]: one more pair of the third set (row 0 of the SRS table is gs itself)
-    KZG_LAUNCH(ctx, st, "k_veb_yagg", k_veb_yagg, 1, 1, 0, (const Fr *)d_yagg, is_mont, d_yagg + 1, d_yagg + 2);
-    KZG_TRY(vb_accumulate(ctx, st, (const G1Affine *)gs->table, d_yagg + 2, d_yagg + 2, 1, bk3, bk3, 1));
-    KZG_TRY(vb_reduce(ctx, st, bk, (uint32_t)slots, sums));
-    if (parts) KZG_HIP_CHECK(ctx, hipMemcpyAsync(parts->yagg, d_yagg + 1, 32, hipMemcpyDeviceToHost, st));
-    return vcb_conclude(ctx, lane, sums, hs->pts, hs->lines, hs->h_pts, hs->h_lines, bad, d_ok, d_parts, parts ? parts->points : nullptr, ok);
+    return veb_finish(&w, gs, hs, parts ? parts->yagg : nullptr, parts ? parts->points : nullptr, ok);
 }
+
 // kzg_verify_fold: `groups` folded openings (kzg_open_fold_eval / kzg_open_fold_coeff), one verdict.  The equation of veb_run with two
 // kinds of weights: the witness of group g carries r^g (and r^g z_g), value and commitment (g, i) carry rho_{g,i} = r^g gamma_g^i.  So
-// the call runs veb_run's stages in two passes over its own chunks: the witnesses against r^g (k_powers, k_veb_scalars, the first two
-// bucket sets), then the values and commitments against rho (formed on the host, one product per opening, and uploaded per chunk: the
-// fold of yagg, and k_vcb_cweights or the third bucket set).  The end is veb_run's.  DESIGN.md section 3.4c.
+// the call runs in two passes over its own chunks: the witnesses against r^g (veb_witnesses), then the values and commitments against
+// rho, formed on the host (fold_weights of vcb_host.h, one product per value) and uploaded per chunk (veb_weighted).  DESIGN.md
+// section 3.4c.
 int vf_run(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *zs, const void *ys, int sfmt, const void *commitments,
            size_t n_commitments, const uint32_t *commitment_idx, const void *witnesses, int pfmt, size_t t, size_t groups, const void *gammas,
            const void *r, int *ok) {
     const char *who = "kzg_verify_fold";
     // ---- shape: everything is decided before memory is touched or a kernel launched ----
-    if (!ctx) return KZG_ERR_SHAPE;
-    if (!gs || !hs) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL SRS");
-    if (sfmt != KZG_FR_MONT_LE_32 && sfmt != KZG_FR_CANONICAL_LE_32) return fail(ctx, KZG_ERR_SHAPE, "unknown scalar format");
-    const size_t psz = point_format_bytes(pfmt);
-    if (!psz || pfmt == KZG_G1_JACOBIAN_MONT_144) return fail(ctx, KZG_ERR_SHAPE, "commitments / witnesses are affine (G1Affine)");
-    if (gs->n < 1 || hs->n < 2) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + " needs gs[0], hs[0], hs[1]");
-    if (gs->device != ctx->device || hs->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the SRS is resident on another GPU than this context's");
+    KZG_TRY(veb_front(ctx, who, "commitments / witnesses", gs, hs, sfmt, pfmt));
     if (t == 0) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": t == 0");
     if (!groups) {
         if (ok) *ok = 1;
@@ -225,156 +224,56 @@ int vf_run(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *zs
         memcpy(x.v, (const uint8_t *)zs + 32 * g, 32);
         if (!is_canonical(x)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": a point z >= modulus");
     }
-    const bool indexed = commitment_idx != nullptr;
-    if (!indexed && n_commitments != count) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": without indices there is one commitment per value");
-    size_t chunk = VEB_CHUNK;
-    if (ctx->opt_verify_eval_batch_chunk > 0) chunk = std::min(chunk, (size_t)ctx->opt_verify_eval_batch_chunk);
-    const size_t B0 = std::min(chunk, count), BP = indexed ? std::min(chunk, std::max(count, n_commitments)) : B0;
-    std::vector<uint32_t> cnt, which, start, order;  // the counting sort of a chunk's values by commitment
-    std::vector<Fr> rho;                             // a chunk's weights
-    if (indexed)
-        for (size_t k = 0; k < count; k++)
-            if (commitment_idx[k] >= n_commitments) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": commitment index >= n_commitments");
+    VebChunks c;
+    KZG_TRY(veb_chunks(ctx, who, "value", count, n_commitments, commitment_idx, &c));
+    if (c.indexed) KZG_TRY(veb_indices(ctx, who, commitment_idx, count, n_commitments));
+    VcbLists lists;
+    std::vector<Fr> rho;  // a chunk's weights
+    bool room = !c.indexed || lists.reserve(n_commitments, c.B0);
     try {
-        rho.resize(B0);
-        if (indexed) {
-            cnt.assign(n_commitments, 0);
-            which.resize(B0);
-            start.resize(B0 + 1);
-            order.resize(B0);
-        }
+        rho.resize(c.B0);
     } catch (const std::bad_alloc &) {
-        return fail(ctx, KZG_ERR_ALLOC, std::string(who) + ": host memory for the weights and indices");
+        room = false;
     }
+    if (!room) return fail(ctx, KZG_ERR_ALLOC, std::string(who) + ": host memory for the weights and indices");
 
     kzg::Lease ls;
     KZG_TRY(lease_lane(ctx, &ls));
-    const int lane = ls.lane;
     KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->lanes[lane].stream;
-    const int is_mont = sfmt == KZG_FR_MONT_LE_32 ? 1 : 0;
-    const size_t fold_blocks = (B0 + VCB_FOLD_CELLS - 1) / VCB_FOLD_CELLS, bucket_bytes = 3 * (size_t)VCB_G * VCB_SET * sizeof(G1Xyzz);
-    const size_t c_bytes = indexed ? std::max<size_t>(n_commitments, 1) * 32 : 32;
-    KZG_TRY(lane_reserve(ctx, lane, bucket_bytes + sizeof(VcbSums) + c_bytes + BP * (psz + sizeof(G1Xyzz)) + B0 * (3 * 4 + 5 * 32) + (fold_blocks + 4) * 32 + 65536));
-    struct Drain {  // nothing of the call is in flight once its host-side buffers go out of scope
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
-    int *bad = (int *)lane_alloc(ctx, lane, 256);
-    uint8_t *d_ok = (uint8_t *)lane_alloc(ctx, lane, 256);
-    G1Affine *d_parts = (G1Affine *)lane_alloc(ctx, lane, 4 * sizeof(G1Affine));
-    G1Xyzz *bk = (G1Xyzz *)lane_alloc(ctx, lane, bucket_bytes);
-    VcbSums *sums = (VcbSums *)lane_alloc(ctx, lane, sizeof(VcbSums));
-    Fr *d_yagg = (Fr *)lane_alloc(ctx, lane, 3 * 32), *d_part = (Fr *)lane_alloc(ctx, lane, fold_blocks * 32);  // yagg (sfmt), yagg, -yagg
-    Fr *d_c = (Fr *)lane_alloc(ctx, lane, c_bytes);
-    uint32_t *d_which = (uint32_t *)lane_alloc(ctx, lane, B0 * 4), *d_start = (uint32_t *)lane_alloc(ctx, lane, (B0 + 1) * 4);
-    uint32_t *d_order = (uint32_t *)lane_alloc(ctx, lane, B0 * 4);
-    Fr *d_rho = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_s1 = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_s2 = (Fr *)lane_alloc(ctx, lane, B0 * 32);
-    Fr *d_x = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_y = (Fr *)lane_alloc(ctx, lane, B0 * 32);
-    uint8_t *raw = (uint8_t *)lane_alloc(ctx, lane, BP * psz);
-    G1Xyzz *W = (G1Xyzz *)lane_alloc(ctx, lane, BP * sizeof(G1Xyzz));
-    if (!bad || !d_ok || !d_parts || !bk || !sums || !d_yagg || !d_part || !d_c || !d_which || !d_start || !d_order || !d_rho || !d_s1 || !d_s2 ||
-        !d_x || !d_y || !raw || !W)
-        return fail(ctx, KZG_ERR_ALLOC, "workspace");
-    G1Xyzz *bk1 = bk, *bk2 = bk + (size_t)VCB_G * VCB_SET, *bk3 = bk + 2 * (size_t)VCB_G * VCB_SET;
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(bad, 0, sizeof(int), st));
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(bk, 0, bucket_bytes, st));         // zz = 0: the identity
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(sums, 0, sizeof(VcbSums), st));    // the Ragg slot stays the identity
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(d_yagg, 0, 3 * 32, st));
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(d_c, 0, c_bytes, st));
-    size_t slots = 1;  // slice slots any chunk has used (gs[0] takes slot 0)
+    hipStream_t st = ctx->lanes[ls.lane].stream;
+    StreamDrain drain{st};
+    VebWork w;
+    KZG_TRY(veb_work(ctx, ls.lane, sfmt, pfmt, c, n_commitments, &w));
     // ---- the witnesses: P1 and P2 against r^g and r^g z_g ----
-    for (size_t g0 = 0; g0 < groups; g0 += chunk) {
-        const size_t B = std::min(chunk, groups - g0);
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_x, (const uint8_t *)zs + g0 * 32, B * 32, hipMemcpyHostToDevice, st));
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)witnesses + g0 * psz, B * psz, hipMemcpyHostToDevice, st));
-        KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
-        KZG_TRY(powers_run(ctx, st, rm, g0, B, d_rho));
-        KZG_LAUNCH(ctx, st, "k_veb_scalars", k_veb_scalars, vcb_grid(B), 256, 0, (const Fr *)d_rho, (const Fr *)d_x, B, is_mont, d_s1, d_s2);
-        KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_s1, d_s2, B, bk1, bk2, 2));
-        slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
+    for (size_t g0 = 0; g0 < groups; g0 += c.chunk) {
+        const size_t B = std::min(c.chunk, groups - g0);
+        KZG_TRY(veb_witnesses(&w, rm, zs, witnesses, g0, B));
         KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
     }
     // ---- values and commitments against rho_{g,i} = r^g gamma_g^i; the weights walk (g, i) across the chunk boundaries ----
-    size_t wg = 0, wi = 0;
-    Fr rg = Fr::one(), w = Fr::one();  // r^wg, r^wg gamma_wg^wi
-    for (size_t k0 = 0; k0 < count; k0 += chunk) {
-        const size_t B = std::min(chunk, count - k0);
-        for (size_t k = 0; k < B; k++) {
-            rho[k] = w;
-            if (++wi == t) {
-                wi = 0;
-                wg++;
-                rg = mul(rg, rm);
-                w = rg;
-            } else {
-                w = mul(w, gm[wg]);
-            }
-        }
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_rho, rho.data(), B * 32, hipMemcpyHostToDevice, st));
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_y, (const uint8_t *)ys + k0 * 32, B * 32, hipMemcpyHostToDevice, st));
-        KZG_TRY(vcb_fold(ctx, st, d_y, d_rho, B, 0, d_part, d_yagg));
-        if (indexed) {  // the chunk's values listed per commitment, commitments in the order of their first value
-            size_t lists = 0;
-            const uint32_t *cm = commitment_idx + k0;
-            for (size_t k = 0; k < B; k++)
-                if (!cnt[cm[k]]++) which[lists++] = cm[k];
-            uint32_t at = 0;
-            for (size_t g = 0; g < lists; g++) {
-                start[g] = at;
-                at += cnt[which[g]];
-                cnt[which[g]] = start[g];
-            }
-            start[lists] = at;
-            for (size_t k = 0; k < B; k++) order[cnt[cm[k]]++] = (uint32_t)k;
-            for (size_t g = 0; g < lists; g++) cnt[which[g]] = 0;
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_which, which.data(), lists * 4, hipMemcpyHostToDevice, st));
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_start, start.data(), (lists + 1) * 4, hipMemcpyHostToDevice, st));
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_order, order.data(), B * 4, hipMemcpyHostToDevice, st));
-            KZG_TRY(vcb_cweights(ctx, st, d_rho, d_which, d_start, d_order, lists, d_c));
-        } else {  // c_k = rho_k: the chunk's commitments into the third set at once
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)commitments + k0 * psz, B * psz, hipMemcpyHostToDevice, st));
-            KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
-            KZG_TRY(vcb_canon(ctx, st, d_rho, B, 1, d_s1));
-            KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_s1, d_s1, B, bk3, bk3, 1));
-        }
-        slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
-        // the host lists and the chunk's device buffers are free again
+    FoldWalk walk;
+    for (size_t k0 = 0; k0 < count; k0 += c.chunk) {
+        const size_t B = std::min(c.chunk, count - k0);
+        fold_weights(&walk, t, rm, gm.data(), B, rho.data());
+        KZG_TRY(veb_weighted(&w, &lists, rho.data(), ys, commitment_idx, commitments, k0, B));
+        // the host lists and weights and the chunk's device buffers are free again
         KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
     }
-    if (indexed) {  // Cagg: the commitments against the canonical c, in chunks like the values
-        for (size_t m0 = 0; m0 < n_commitments; m0 += BP) {
-            const size_t B = std::min(BP, n_commitments - m0);
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)commitments + m0 * psz, B * psz, hipMemcpyHostToDevice, st));
-            KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
-            KZG_TRY(vcb_canon(ctx, st, d_c + m0, B, 1, d_c + m0));
-            KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_c + m0, d_c + m0, B, bk3, bk3, 1));
-            slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
-        }
-    }
-    // - [yagg] gs[0]: one more pair of the third set (row 0 of the SRS table is gs itself)
-    KZG_LAUNCH(ctx, st, "k_veb_yagg", k_veb_yagg, 1, 1, 0, (const Fr *)d_yagg, is_mont, d_yagg + 1, d_yagg + 2);
-    KZG_TRY(vb_accumulate(ctx, st, (const G1Affine *)gs->table, d_yagg + 2, d_yagg + 2, 1, bk3, bk3, 1));
-    KZG_TRY(vb_reduce(ctx, st, bk, (uint32_t)slots, sums));
-    return vcb_conclude(ctx, lane, sums, hs->pts, hs->lines, hs->h_pts, hs->h_lines, bad, d_ok, d_parts, nullptr, ok);
+    if (c.indexed) KZG_TRY(vcb_cagg(&w, commitments, n_commitments));
+    return veb_finish(&w, gs, hs, nullptr, nullptr, ok);
 }
+
 // kzg_verify_multiopen: N claims at any points answered by the two elements D and pi (kzg_multiopen_*_commit / _finish; DESIGN.md section
 // 3.4d).  With w_k = r^k / (t - z_k): E = sum_m W_m C_m, W_m = sum_{m(k) = m} w_k, g2 = sum_k w_k y_k, and the proof is a plain opening of
-// E - D at (t, g2) with the witness pi.  So this is vf_run with other weights: the ONE witness against 1 and t (k_veb_scalars), D as
-// one more pair of the third set against -1, then the values and commitments against w_k, formed on the host per chunk (one inversion
-// each, multiopen_plan.h): the fold gives g2, k_vcb_cweights or the third set gives E.  The end is veb_run's.
+// E - D at (t, g2) with the witness pi.  So: the ONE witness against 1 and t (k_veb_scalars), D as one more pair of the third set
+// against -1, then the values and commitments against w_k, formed on the host per chunk (one inversion each, multiopen_plan.h) and
+// uploaded (veb_weighted): the fold gives g2, k_vcb_cweights or the third set gives E.
 int vm_run(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *zs, const void *ys, int sfmt, const void *commitments,
            size_t n_commitments, const uint32_t *commitment_idx, size_t count, const void *r, const void *t, const void *d_point, const void *pi,
            int pfmt, int *ok) {
     const char *who = "kzg_verify_multiopen";
     // ---- shape: everything is decided before memory is touched or a kernel launched ----
-    if (!ctx) return KZG_ERR_SHAPE;
-    if (!gs || !hs) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": NULL SRS");
-    if (sfmt != KZG_FR_MONT_LE_32 && sfmt != KZG_FR_CANONICAL_LE_32) return fail(ctx, KZG_ERR_SHAPE, "unknown scalar format");
-    const size_t psz = point_format_bytes(pfmt);
-    if (!psz || pfmt == KZG_G1_JACOBIAN_MONT_144) return fail(ctx, KZG_ERR_SHAPE, "commitments / D / pi are affine (G1Affine)");
-    if (gs->n < 1 || hs->n < 2) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + " needs gs[0], hs[0], hs[1]");
-    if (gs->device != ctx->device || hs->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the SRS is resident on another GPU than this context's");
+    KZG_TRY(veb_front(ctx, who, "commitments / D / pi", gs, hs, sfmt, pfmt));
     if (!count) {
         if (ok) *ok = 1;
         return KZG_OK;
@@ -386,135 +285,55 @@ int vm_run(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, const void *zs
     memcpy(tm.v, t, 32);
     if (!is_canonical(tm)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": the challenge t >= modulus");
     if (sfmt != KZG_FR_MONT_LE_32) tm = to_mont(tm);
-    const bool indexed = commitment_idx != nullptr;
-    if (!indexed && n_commitments != count) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": without indices there is one commitment per claim");
-    size_t chunk = VEB_CHUNK;
-    if (ctx->opt_verify_eval_batch_chunk > 0) chunk = std::min(chunk, (size_t)ctx->opt_verify_eval_batch_chunk);
-    const size_t B0 = std::min(chunk, count), BP = indexed ? std::min(chunk, std::max(count, n_commitments)) : B0;
-    std::vector<uint32_t> cnt, which, start, order;  // the counting sort of a chunk's claims by commitment
-    std::vector<Fr> zm, w;                           // the points (Montgomery) | a chunk's weights
+    VebChunks c;
+    KZG_TRY(veb_chunks(ctx, who, "claim", count, n_commitments, commitment_idx, &c));
+    VcbLists lists;
+    std::vector<Fr> zm, wt;  // the points (Montgomery) | a chunk's weights
+    bool room = !c.indexed || lists.reserve(n_commitments, c.B0);
     try {  // (no exception may leave through the C ABI)
         zm.resize(count);
-        w.resize(B0);
-        if (indexed) {
-            cnt.assign(n_commitments, 0);
-            which.resize(B0);
-            start.resize(B0 + 1);
-            order.resize(B0);
-        }
+        wt.resize(c.B0);
     } catch (const std::bad_alloc &) {
-        return fail(ctx, KZG_ERR_ALLOC, std::string(who) + ": host memory for the weights and indices");
+        room = false;
     }
+    if (!room) return fail(ctx, KZG_ERR_ALLOC, std::string(who) + ": host memory for the weights and indices");
     for (size_t k = 0; k < count; k++) {
         Fr x;
         memcpy(x.v, (const uint8_t *)zs + 32 * k, 32);
         if (!is_canonical(x)) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": a point z >= modulus");
         zm[k] = sfmt == KZG_FR_MONT_LE_32 ? x : to_mont(x);
         if (zm[k] == tm) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": t equals a point z_k (draw another t)");
-        if (indexed && commitment_idx[k] >= n_commitments) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": commitment index >= n_commitments");
+        if (c.indexed && commitment_idx[k] >= n_commitments) return fail(ctx, KZG_ERR_SHAPE, std::string(who) + ": commitment index >= n_commitments");
     }
     const Fr one = Fr::one(), minus_one = from_mont(neg(Fr::one()));  // the witness's weight (Montgomery) | D's scalar (canonical)
 
     kzg::Lease ls;
     KZG_TRY(lease_lane(ctx, &ls));
-    const int lane = ls.lane;
     KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->lanes[lane].stream;
-    const int is_mont = sfmt == KZG_FR_MONT_LE_32 ? 1 : 0;
-    const size_t fold_blocks = (B0 + VCB_FOLD_CELLS - 1) / VCB_FOLD_CELLS, bucket_bytes = 3 * (size_t)VCB_G * VCB_SET * sizeof(G1Xyzz);
-    const size_t c_bytes = indexed ? std::max<size_t>(n_commitments, 1) * 32 : 32;
-    KZG_TRY(lane_reserve(ctx, lane, bucket_bytes + sizeof(VcbSums) + c_bytes + BP * (psz + sizeof(G1Xyzz)) + B0 * (3 * 4 + 5 * 32) + (fold_blocks + 4) * 32 + 65536));
-    struct Drain {  // nothing of the call is in flight once its host-side buffers go out of scope
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
-    int *bad = (int *)lane_alloc(ctx, lane, 256);
-    uint8_t *d_ok = (uint8_t *)lane_alloc(ctx, lane, 256);
-    G1Affine *d_parts = (G1Affine *)lane_alloc(ctx, lane, 4 * sizeof(G1Affine));
-    G1Xyzz *bk = (G1Xyzz *)lane_alloc(ctx, lane, bucket_bytes);
-    VcbSums *sums = (VcbSums *)lane_alloc(ctx, lane, sizeof(VcbSums));
-    Fr *d_yagg = (Fr *)lane_alloc(ctx, lane, 3 * 32), *d_part = (Fr *)lane_alloc(ctx, lane, fold_blocks * 32);  // g2 (sfmt), g2, -g2
-    Fr *d_c = (Fr *)lane_alloc(ctx, lane, c_bytes);
-    uint32_t *d_which = (uint32_t *)lane_alloc(ctx, lane, B0 * 4), *d_start = (uint32_t *)lane_alloc(ctx, lane, (B0 + 1) * 4);
-    uint32_t *d_order = (uint32_t *)lane_alloc(ctx, lane, B0 * 4);
-    Fr *d_rho = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_s1 = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_s2 = (Fr *)lane_alloc(ctx, lane, B0 * 32);
-    Fr *d_x = (Fr *)lane_alloc(ctx, lane, B0 * 32), *d_y = (Fr *)lane_alloc(ctx, lane, B0 * 32);
-    uint8_t *raw = (uint8_t *)lane_alloc(ctx, lane, BP * psz);
-    G1Xyzz *W = (G1Xyzz *)lane_alloc(ctx, lane, BP * sizeof(G1Xyzz));
-    if (!bad || !d_ok || !d_parts || !bk || !sums || !d_yagg || !d_part || !d_c || !d_which || !d_start || !d_order || !d_rho || !d_s1 || !d_s2 ||
-        !d_x || !d_y || !raw || !W)
-        return fail(ctx, KZG_ERR_ALLOC, "workspace");
-    G1Xyzz *bk1 = bk, *bk2 = bk + (size_t)VCB_G * VCB_SET, *bk3 = bk + 2 * (size_t)VCB_G * VCB_SET;
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(bad, 0, sizeof(int), st));
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(bk, 0, bucket_bytes, st));         // zz = 0: the identity
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(sums, 0, sizeof(VcbSums), st));    // the Ragg slot stays the identity
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(d_yagg, 0, 3 * 32, st));
-    KZG_HIP_CHECK(ctx, hipMemsetAsync(d_c, 0, c_bytes, st));
-    size_t slots = 1;  // slice slots any chunk has used (gs[0], pi and D take slot 0)
+    hipStream_t st = ctx->lanes[ls.lane].stream;
+    StreamDrain drain{st};
+    VebWork w;
+    KZG_TRY(veb_work(ctx, ls.lane, sfmt, pfmt, c, n_commitments, &w));
     // ---- the witness: P1 = pi, P2 = t pi ----
-    KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_rho, one.v, 32, hipMemcpyHostToDevice, st));
-    KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_x, t, 32, hipMemcpyHostToDevice, st));
-    KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, pi, psz, hipMemcpyHostToDevice, st));
-    KZG_TRY(decode_points(ctx, st, raw, 1, pfmt, W, bad, untrusted_level(ctx)));
-    KZG_LAUNCH(ctx, st, "k_veb_scalars", k_veb_scalars, 1, 256, 0, (const Fr *)d_rho, (const Fr *)d_x, (size_t)1, is_mont, d_s1, d_s2);
-    KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_s1, d_s2, 1, bk1, bk2, 2));
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(w.d_rho, one.v, 32, hipMemcpyHostToDevice, st));
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(w.d_x, t, 32, hipMemcpyHostToDevice, st));
+    KZG_LAUNCH(ctx, st, "k_veb_scalars", k_veb_scalars, 1, 256, 0, (const Fr *)w.d_rho, (const Fr *)w.d_x, (size_t)1, w.is_mont, w.d_s1, w.d_s2);
+    KZG_TRY(vcb_points(&w, pi, 1, w.d_s1, w.d_s2, w.bk[0], w.bk[1], 2));
     // ---- D: one more commitment, of weight -1 ----
-    KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_s1, minus_one.v, 32, hipMemcpyHostToDevice, st));
-    KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, d_point, psz, hipMemcpyHostToDevice, st));
-    KZG_TRY(decode_points(ctx, st, raw, 1, pfmt, W, bad, untrusted_level(ctx)));
-    KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_s1, d_s1, 1, bk3, bk3, 1));
+    KZG_HIP_CHECK(ctx, hipMemcpyAsync(w.d_s1, minus_one.v, 32, hipMemcpyHostToDevice, st));
+    KZG_TRY(vcb_points(&w, d_point, 1, w.d_s1, w.d_s1, w.bk[2], w.bk[2], 1));
     KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
     // ---- values and commitments against w_k = r^k / (t - z_k); r^k walks across the chunk boundaries ----
     Fr rk = Fr::one();
-    for (size_t k0 = 0; k0 < count; k0 += chunk) {
-        const size_t B = std::min(chunk, count - k0);
-        if (!mo_weights(zm.data() + k0, B, rm, tm, &rk, w.data())) return fail(ctx, KZG_ERR_INTERNAL, std::string(who) + ": t equals a point");
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_rho, w.data(), B * 32, hipMemcpyHostToDevice, st));
-        KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_y, (const uint8_t *)ys + k0 * 32, B * 32, hipMemcpyHostToDevice, st));
-        KZG_TRY(vcb_fold(ctx, st, d_y, d_rho, B, 0, d_part, d_yagg));
-        if (indexed) {  // the chunk's claims listed per commitment, commitments in the order of their first claim
-            size_t lists = 0;
-            const uint32_t *cm = commitment_idx + k0;
-            for (size_t k = 0; k < B; k++)
-                if (!cnt[cm[k]]++) which[lists++] = cm[k];
-            uint32_t at = 0;
-            for (size_t g = 0; g < lists; g++) {
-                start[g] = at;
-                at += cnt[which[g]];
-                cnt[which[g]] = start[g];
-            }
-            start[lists] = at;
-            for (size_t k = 0; k < B; k++) order[cnt[cm[k]]++] = (uint32_t)k;
-            for (size_t g = 0; g < lists; g++) cnt[which[g]] = 0;
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_which, which.data(), lists * 4, hipMemcpyHostToDevice, st));
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_start, start.data(), (lists + 1) * 4, hipMemcpyHostToDevice, st));
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_order, order.data(), B * 4, hipMemcpyHostToDevice, st));
-            KZG_TRY(vcb_cweights(ctx, st, d_rho, d_which, d_start, d_order, lists, d_c));
-        } else {  // W_k = w_k: the chunk's commitments into the third set at once
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)commitments + k0 * psz, B * psz, hipMemcpyHostToDevice, st));
-            KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
-            KZG_TRY(vcb_canon(ctx, st, d_rho, B, 1, d_s1));
-            KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_s1, d_s1, B, bk3, bk3, 1));
-        }
-        slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
-        // the host lists and the chunk's device buffers are free again
+    for (size_t k0 = 0; k0 < count; k0 += c.chunk) {
+        const size_t B = std::min(c.chunk, count - k0);
+        if (!mo_weights(zm.data() + k0, B, rm, tm, &rk, wt.data())) return fail(ctx, KZG_ERR_INTERNAL, std::string(who) + ": t equals a point");
+        KZG_TRY(veb_weighted(&w, &lists, wt.data(), ys, commitment_idx, commitments, k0, B));
+        // the host lists and weights and the chunk's device buffers are free again
         KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
     }
-    if (indexed) {  // E: the commitments against the canonical W, in chunks like the claims
-        for (size_t m0 = 0; m0 < n_commitments; m0 += BP) {
-            const size_t B = std::min(BP, n_commitments - m0);
-            KZG_HIP_CHECK(ctx, hipMemcpyAsync(raw, (const uint8_t *)commitments + m0 * psz, B * psz, hipMemcpyHostToDevice, st));
-            KZG_TRY(decode_points(ctx, st, raw, B, pfmt, W, bad, untrusted_level(ctx)));
-            KZG_TRY(vcb_canon(ctx, st, d_c + m0, B, 1, d_c + m0));
-            KZG_TRY(vb_accumulate(ctx, st, (const G1Xyzz *)W, d_c + m0, d_c + m0, B, bk3, bk3, 1));
-            slots = std::max(slots, (B + VCB_S - 1) / VCB_S);
-        }
-    }
-    // - [g2] gs[0]: one more pair of the third set (row 0 of the SRS table is gs itself)
-    KZG_LAUNCH(ctx, st, "k_veb_yagg", k_veb_yagg, 1, 1, 0, (const Fr *)d_yagg, is_mont, d_yagg + 1, d_yagg + 2);
-    KZG_TRY(vb_accumulate(ctx, st, (const G1Affine *)gs->table, d_yagg + 2, d_yagg + 2, 1, bk3, bk3, 1));
-    KZG_TRY(vb_reduce(ctx, st, bk, (uint32_t)slots, sums));
-    return vcb_conclude(ctx, lane, sums, hs->pts, hs->lines, hs->h_pts, hs->h_lines, bad, d_ok, d_parts, nullptr, ok);
+    if (c.indexed) KZG_TRY(vcb_cagg(&w, commitments, n_commitments));
+    return veb_finish(&w, gs, hs, nullptr, nullptr, ok);
 }
 }  // namespace
 

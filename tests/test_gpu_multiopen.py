@@ -711,6 +711,30 @@ def test_verifier_null_indices_and_the_forgery_of_a_predictable_t(eng, params):
     assert kv.verify_multiopen([z], [ys[0]], commitments[:1], forged_D, ident.raw, r, t) is False
 
 
+@pytest.fixture(scope="module")
+def proof3(eng, params):
+    """three claims, one polynomial of 12 coefficients each: the shape without indices"""
+    rng = random.Random(330)
+    polys = [[rng.randrange(R) for _ in range(12)] for _ in range(3)]
+    zs = [rng.randrange(R) for _ in range(3)]
+    r, t = rng.randrange(1, R), fresh(rng, zs)
+    prover = kzg_amd.KZGProver(params)
+    ys, D, pi, _ = prover.multiopen(polys, zs, r, lambda D_: t)
+    return zs, ys, [prover.commit(kzg_amd.Polynomial(p)) for p in polys], r, t, D, pi
+
+
+@pytest.mark.parametrize("chunk", [1, 2])
+def test_verifier_null_indices_at_a_lowered_chunk(eng, params, proof3, chunk):
+    """one commitment per claim goes into the third bucket set chunk by chunk: three claims in chunks of 1 and of 2"""
+    zs, ys, commitments, r, t, D, pi = proof3
+    eng.set_option("verify_eval_batch_chunk", chunk)
+    try:
+        assert verify_raw(eng, params, zs, ys, commitments, None, r, t, D, pi) == (0, 1)
+        assert verify_raw(eng, params, zs, ys[:2] + [(ys[2] + 1) % R], commitments, None, r, t, D, pi) == (0, 0)
+    finally:
+        eng.set_option("verify_eval_batch_chunk", 0)
+
+
 def test_verifier_malformed_points_and_shape_errors_leave_ok_unwritten(eng, params, proof):
     polys, idx, zs, ys, r, t, commitments, D, pi, vt, model = proof
     off_curve = (1).to_bytes(48, "little") * 2

@@ -500,6 +500,26 @@ def test_verify_fold_chunks_and_both_pairing_sites(eng, params, calls):
         eng.set_option("host_pairing", 1)
 
 
+def test_verify_fold_at_t_1_is_kzg_verify_eval_batch(eng, params):
+    """t = 1: rho_{g,0} = r^g, so both calls compute the same equation.  Five openings, the same r, points, values, commitments and
+    witnesses into both, with indices and with one commitment per opening: the same verdict, honest and with one value flipped."""
+    c = FoldCall(eng, params, 5, t=1, seed=77)
+    bad = c.copy()
+    bad.ys[3] = (bad.ys[3] + 1) % R
+    r = 0x1234567
+
+    def eval_batch(call):
+        idx = None if call.idx is None else (ctypes.c_uint32 * len(call.idx))(*call.idx)
+        v = ctypes.c_int(UNTOUCHED)
+        rc = eng.lib.kzg_verify_eval_batch(eng.ctx, params.gs.handle, params.hs.handle, pack_scalars(call.zs), pack_scalars(call.ys), CAN,
+                                           b"".join(call.commitments), len(call.commitments), idx, b"".join(call.witnesses), AFF, 5, raw32(r),
+                                           ctypes.byref(v))
+        return rc, v.value
+    for call, want in ((c, 1), (c.per_value(), 1), (bad, 0), (bad.per_value(), 0)):
+        assert verify_raw(eng, params, call, r) == (0, want), (want, call.idx)
+        assert eval_batch(call) == (0, want), (want, call.idx)
+
+
 def test_verify_fold_of_evaluation_form_openings(eng, srs64):
     rng = random.Random(120)
     d, t, groups = 64, 4, 3
