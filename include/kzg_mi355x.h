@@ -13,7 +13,7 @@
  *   - a kzg_ctx is bound to one GPU and is thread-safe.  The reference's blocking calls -- kzg_commit_coeff,
  *     kzg_commit_eval, kzg_msm_g1, kzg_witness_coeff, kzg_witness_coeff_batched, kzg_witness_eval, kzg_verify_poly_coeff /
  *     _eval, kzg_ntt_fr, kzg_coset_ntt_fr, kzg_poly_mul, kzg_poly_divide, kzg_poly_eval, kzg_poly_multi_eval, kzg_interpolate, kzg_quotient_linear / _eval,
- *     kzg_point_tree_product, kzg_point_tree_eval, kzg_point_tree_combine, kzg_point_tree_interpolate, kzg_fr_vec_mul / _sub, kzg_divide_by_z_on_coset (KZGProver / KZGProverEvalForm / KZGVerifier are Clone + &self, src/coeff_form.rs:37-124; an
+ *     kzg_point_tree_product, kzg_point_tree_eval, kzg_point_tree_combine, kzg_point_tree_interpolate, kzg_fr_vec_mul / _sub, kzg_divide_by_z_on_coset, kzg_fr_scan, kzg_fr_grand_product, kzg_fr_batch_inverse (KZGProver / KZGProverEvalForm / KZGVerifier are Clone + &self, src/coeff_form.rs:37-124; an
  *     EvaluationDomain is the caller's own) -- run CONCURRENTLY on one ctx: each call leases one of the context's lanes
  *     (option "streams", default and maximum 16), submits its kernels there and waits for its own result only, so N host
  *     threads calling commit() / create_witness_batched() against one resident SRS fill the GPU like kzg_msm_g1_batch does.
@@ -89,6 +89,12 @@ extern "C" {
  *   kzg_interpolate                         k <= 16384 points                (the k x k basis matrix: 8.6 GB there); any batch
  *   kzg_poly_divide                         na <= 2^27 (the product limit of kzg_poly_mul); any nb and batch: dividends go in chunks of
  *                                                                             min(256, max(1, 2^20 / na)); the workspace does not grow with batch
+ *   kzg_fr_scan, kzg_fr_grand_product,
+ *   kzg_fr_batch_inverse                    n <= 2^28; any t and batch: vectors go in chunks of min(65535, max(1, 65536 / ceil(n / 2048))), three
+ *                                                                             launches each; the workspace is 64 B (scan) / 128 B (grand product) per
+ *                                                                             tile of a chunk (<= 16 MiB at the default tile) beside one staged piece of
+ *                                                                             host data (<= 64 MiB, or one vector -- with its 2 t columns) and does not
+ *                                                                             grow with batch; the inversion: <= 64 MiB of scratch when in == out
  *   kzg_point_tree_setup                    1 <= k <= 2^22 points             (the plan holds 32 x (3 log2 K + 1) bytes per point of the padded
  *                                                                             size K: 9.0 GB at 2^22); kzg_point_tree_eval: n <= 2^28; any batch:
  *                                                                             chunks of max(1, 2^21 / K) blocks, the workspace does not grow with it
@@ -205,6 +211,10 @@ int kzg_sync(kzg_ctx *ctx);
  *  call on its own kernels where it would take one kzg_poly_eval scan per value (up to 7 values): the same bytes, for A/B and tests,
  * "poly_divide_base" (0 = default, 64; a power of two in 1..64: the coefficients of the power-series inverse kzg_poly_divide's one-workgroup
  *  base kernel produces before Newton doubling takes over; the same bytes, for A/B and for tests that drive several Newton levels at tiny shapes),
+ * "fr_scan_tile" (0 = default, 2048; a power of two in 8..2048: the elements one workgroup of kzg_fr_scan / kzg_fr_grand_product scans, that is
+ *  1..256 threads of eight; read per call; the same bytes, for tests that reach tile and carry boundaries at n in the hundreds), "fr_scan_stage"
+ *  (0 = default, 64 MiB; a multiple of 32 up to 64 MiB: the bytes of one staged piece of host data in those calls and kzg_fr_batch_inverse) and
+ *  "fr_scan_chunk" (0 = the rule alone; 1..65535: at most that many vectors per chunk of launches); the same bytes, for tests,
  * "point_tree_leaf" (0 = default, 16; a power of two in 1..16: kzg_point_tree_setup multiplies nodes of up to that many points by its schoolbook
  *  kernels and the levels above through transforms; read at setup and kept by the plan; the same bytes, for tests that reach many levels at tiny k),
  * "g2_msm_slice" (0 = default, 2048; a power of two in 1..2048: the points one workgroup of kzg_msm_g2_bucket sorts by digit) and
@@ -518,6 +528,47 @@ int kzg_open_fold_coeff(kzg_ctx *ctx, const kzg_srs *srs, const void *coeffs, si
  * pieces of at most 64 MiB with the running sum on the device.  Leases one lane.  count == 0: out is zeroed. */
 int kzg_fr_lincomb(kzg_ctx *ctx, const void *vecs, size_t d, size_t n_vecs, const uint32_t *idx, const void *weights, size_t count, int sfmt,
                    int flags, void *out);
+/* ---- scans over Fr, the grand product and batch inversion (not a reference method) -------------------------------------------------
+ * The running product of a permutation argument and the running sum of a logUp-style lookup argument, without leaving the device.
+ * Scalars are sfmt; in KZG_FR_CANONICAL_LE_32 any 256-bit word counts as its residue, in KZG_FR_MONT_LE_32 inputs are below r; outputs
+ * are in sfmt and always below r.  Products are products of the represented values in both formats (Montgomery in: the Montgomery
+ * form of the product out).  KZG_IN_DEVICE covers in / num / den, KZG_OUT_DEVICE covers out / z_out; totals, zeros and zero_den are
+ * ALWAYS host memory.  Aliasing: for kzg_fr_scan and kzg_fr_batch_inverse out == in EXACTLY is allowed (on the device with both flags
+ * set, and for two host buffers); any other overlap of an output with an input or with another output is the caller's error.
+ * kzg_fr_grand_product's z_out overlaps neither num nor den.
+ * All three are blocking calls that lease one lane (they run concurrently with each other and with the calls listed at the top).
+ * Host inputs and outputs are staged in pieces of at most 64 MiB -- whole vectors for kzg_fr_scan (one vector if a vector is larger),
+ * whole vectors' 2 t columns for kzg_fr_grand_product (one vector's columns if they are larger), any run of elements for
+ * kzg_fr_batch_inverse --, and the vectors of a call are worked off in chunks of min(65535, max(1, 65536 / ceil(n / 2048))) vectors, three
+ * kernel launches per chunk: the workspace does not grow with batch (Limits).
+ * KZG_ERR_SHAPE, before any memory is touched: a NULL ctx, an unknown sfmt or op, exclusive not 0 or 1, n == 0, t == 0, a NULL input
+ * or output with work to do, n > 2^28, batch x t x n x 32 beyond size_t.  batch == 0: KZG_OK, nothing touched.
+ * Options, read per call, for tests; the bytes are the same: "fr_scan_tile" (0 = default, 2048; a power of two in 8..2048: the elements
+ * one workgroup of kzg_fr_scan / kzg_fr_grand_product scans, 1..256 threads of eight -- tile and carry boundaries at n in the hundreds),
+ * "fr_scan_stage" (0 = default, 64 MiB; a multiple of 32 up to 64 MiB: the bytes of one staged piece, all three calls) and
+ * "fr_scan_chunk" (0 = the rule above alone; 1..65535: at most that many vectors per chunk). */
+enum { KZG_SCAN_PRODUCT = 0, KZG_SCAN_SUM = 1 };
+
+/* out[i] = 1 / in[i]; a zero (a word whose residue is 0) maps to zero.  *zeros (optional) = how many. */
+int kzg_fr_batch_inverse(kzg_ctx *ctx, const void *in, size_t n, int sfmt, int flags, void *out, size_t *zeros);
+
+/* `batch` vectors of n scalars, contiguous (vector b at element b*n).
+ * exclusive = 0: out[b*n+i] = in[b*n+0] (op) ... (op) in[b*n+i]
+ * exclusive = 1: out[b*n+0] = identity (1 for PRODUCT, 0 for SUM), out[b*n+i] = in[b*n+0] (op) ... (op) in[b*n+i-1]
+ * totals (optional; batch scalars, ALWAYS host memory, sfmt): the (op) of all n elements of each vector. */
+int kzg_fr_scan(kzg_ctx *ctx, const void *in, size_t n, size_t batch, int op, int exclusive, int sfmt, int flags,
+                void *out, void *totals);
+
+/* The permutation / lookup accumulator.  num, den: batch x t x n scalars each, column j of vector b at element (b*t + j)*n
+ * (the layout of kzg_fr_fold).  With f_b[i] = prod_j num[b][j][i] / prod_j den[b][j][i]:
+ *   z_out[b*n + 0] = 1,  z_out[b*n + i] = f_b[0] ... f_b[i-1]  (i < n),  totals[b] = f_b[0] ... f_b[n-1]  (1 for a valid permutation).
+ * totals: optional, host.  zero_den: optional, batch ints, host.
+ * A vector with a zero denominator (a den word whose residue is 0) has its row of z_out and its total written as all zero.  With
+ * zero_den given, zero_den[b] = 1 for those vectors and 0 for the others, and the call returns KZG_OK; with zero_den == NULL the call
+ * returns KZG_ERR_SHAPE if any vector has one (the reference's invert().unwrap() panic; the status argument of kzg_witness_coeff_many
+ * is the model).  A zero in num is legal: z is zero from there on.  No element is inverted: one field inversion per vector. */
+int kzg_fr_grand_product(kzg_ctx *ctx, const void *num, const void *den, size_t n, size_t t, size_t batch, int sfmt, int flags,
+                         void *z_out, void *totals, int *zero_den);
 /* Evaluation form: evals holds n_polys vectors of d values (stride d), d a power of two == kzg_srs_len(lagrange).  First phase:
  * ys_out[k] = p_{m(k)}(z_k) (host, count scalars: the values of kzg_eval_form_eval), g_out = the d values of g on the domain, D at out_d
  * in ofmt (each of the three optional, not all NULL).  evals and g / g_out are host memory, or device memory with KZG_IN_DEVICE; g has the

@@ -447,6 +447,46 @@ inline std::vector<Scalar> fr_lincomb(const Engine &e, const std::vector<Scalar>
     return out;
 }
 
+// kzg_fr_batch_inverse: 1 / v for every v; a zero maps to zero, *zeros (optional) counts them.  Not a reference method.
+inline std::vector<Scalar> batch_inverse(const Engine &e, const std::vector<Scalar> &values, size_t *zeros = nullptr) {
+    static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+    if (values.empty()) throw ReferencePanic("batch_inverse: no values");
+    std::vector<Scalar> out(values.size());
+    e.check(kzg_fr_batch_inverse(e.ctx(), values.data(), values.size(), KZG_FR_CANONICAL_LE_32, 0, out.data(), zeros));
+    return out;
+}
+
+// kzg_fr_scan: the running products (op = KZG_SCAN_PRODUCT) or sums (KZG_SCAN_SUM) of vecs.size() / n vectors of n scalars back to back;
+// exclusive: a vector's scan starts from the identity and leaves its last element out.  totals (optional): every vector's total.  Not a
+// reference method.
+inline std::vector<Scalar> fr_scan(const Engine &e, const std::vector<Scalar> &vecs, size_t n, int op = KZG_SCAN_PRODUCT, bool exclusive = false,
+                                   std::vector<Scalar> *totals = nullptr) {
+    static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+    if (n == 0 || vecs.size() % n != 0) throw ReferencePanic("fr_scan: shape");
+    const size_t batch = vecs.size() / n;
+    std::vector<Scalar> out(vecs.size());
+    if (totals) totals->resize(batch);
+    e.check(kzg_fr_scan(e.ctx(), vecs.data(), n, batch, op, exclusive ? 1 : 0, KZG_FR_CANONICAL_LE_32, 0, out.data(), totals ? totals->data() : nullptr));
+    return out;
+}
+
+// kzg_fr_grand_product: z[b n] = 1, z[b n + i] = prod_{k < i} prod_j num[b][j][k] / den[b][j][k] for num.size() / (t n) vectors of t columns of n
+// scalars (column j of vector b at element (b t + j) n).  totals (optional): every vector's full product.  zero_den (optional): the vectors
+// with a zero denominator are flagged there and have zero rows and totals; without it such a vector throws ReferencePanic.  Not a
+// reference method.
+inline std::vector<Scalar> grand_product(const Engine &e, const std::vector<Scalar> &num, const std::vector<Scalar> &den, size_t n, size_t t,
+                                         std::vector<Scalar> *totals = nullptr, std::vector<int> *zero_den = nullptr) {
+    static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+    if (n == 0 || t == 0 || num.size() != den.size() || num.size() % n != 0 || (num.size() / n) % t != 0) throw ReferencePanic("grand_product: shape");
+    const size_t batch = num.size() / n / t;
+    std::vector<Scalar> z(batch * n);
+    if (totals) totals->resize(batch);
+    if (zero_den) zero_den->resize(batch);
+    e.check(kzg_fr_grand_product(e.ctx(), num.data(), den.data(), n, t, batch, KZG_FR_CANONICAL_LE_32, 0, z.data(), totals ? totals->data() : nullptr,
+                                 zero_den ? zero_den->data() : nullptr));
+    return z;
+}
+
 struct KZGBatchWitness {  // src/coeff_form.rs:12-35
     Polynomial r;
     G1Affine w;

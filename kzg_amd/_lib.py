@@ -27,6 +27,8 @@ G2_AFFINE_MONT, G2_JACOBIAN_MONT, G2_UNCOMPRESSED, G2_COMPRESSED = 0, 1, 2, 3
 G2_POINT_BYTES = {0: 192, 1: 288, 2: 192, 3: 96}
 IN_DEVICE = 1
 OUT_DEVICE = 2
+SCAN_PRODUCT = 0
+SCAN_SUM = 1
 
 _lib = None
 
@@ -159,6 +161,9 @@ def load(path=None):
         "kzg_open_fold_coeff": (i32, [vp, vp, vp, sz, sz, sz, vp, vp, i32, i32, vp, vp, i32]),
         "kzg_verify_fold": (i32, [vp, vp, vp, vp, vp, i32, vp, sz, ctypes.POINTER(u32), vp, i32, sz, sz, vp, vp, ctypes.POINTER(i32)]),
         "kzg_fr_lincomb": (i32, [vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, i32, i32, vp]),
+        "kzg_fr_batch_inverse": (i32, [vp, vp, sz, i32, i32, vp, ctypes.POINTER(sz)]),
+        "kzg_fr_scan": (i32, [vp, vp, sz, sz, i32, i32, i32, i32, vp, vp]),
+        "kzg_fr_grand_product": (i32, [vp, vp, vp, sz, sz, sz, i32, i32, vp, vp, ctypes.POINTER(i32)]),
         "kzg_multiopen_eval_commit": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, i32, i32, vp, vp, vp, i32]),
         "kzg_multiopen_eval_finish": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, vp, vp, i32, i32, vp, vp, i32]),
         "kzg_multiopen_coeff_commit": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, i32, i32, vp, vp, vp, i32]),

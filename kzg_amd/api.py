@@ -523,6 +523,85 @@ class Engine:
             _raise(self, rc)
         return [self._scalar_from(buf.raw[32 * k:32 * k + 32], sfmt) for k in range(d)]
 
+    def batch_inverse(self, values, out=None):
+        """kzg_fr_batch_inverse: 1 / v for every v of `values` (a list of ints, a canonical blob or a DeviceBuffer); a zero maps to
+        zero.  Returns (inverses, zeros): the inverses as ints, or `out` (a DeviceBuffer of the inputs' scalar format, which may be
+        `values` itself) when one is given, and the number of zeros met."""
+        ptr, n, sfmt, flags, _keep = self._scalars_arg(values)
+        zeros = ctypes.c_size_t(0)
+        if out is not None:
+            if out.n < n or out.sfmt != sfmt:
+                raise ReferencePanic("batch_inverse: out holds %d scalars, n = %d (and has the inputs' format)" % (out.n, n))
+            rc = self.lib.kzg_fr_batch_inverse(self.ctx, ptr, n, sfmt, flags | L.OUT_DEVICE, out.ptr, ctypes.byref(zeros))
+            if rc:
+                _raise(self, rc)
+            return out, zeros.value
+        buf = ctypes.create_string_buffer(32 * max(n, 1))
+        rc = self.lib.kzg_fr_batch_inverse(self.ctx, ptr, n, sfmt, flags, buf, ctypes.byref(zeros))
+        if rc:
+            _raise(self, rc)
+        return [self._scalar_from(buf.raw[32 * k:32 * k + 32], sfmt) for k in range(n)], zeros.value
+
+    def fr_scan(self, vecs, n, op="product", exclusive=False, out=None):
+        """kzg_fr_scan: the running products (op = "product") or sums ("sum") of len(vecs) / n vectors of n scalars, vector b at element
+        b n; exclusive: every vector's scan starts from the identity and leaves its last element out.  vecs: a flat list of ints, a
+        canonical blob or a DeviceBuffer.  Returns (out, totals): the scans as ints, or `out` (a DeviceBuffer of the inputs' scalar
+        format, which may be `vecs` itself) when one is given, and every vector's total as ints."""
+        ops = {"product": L.SCAN_PRODUCT, "sum": L.SCAN_SUM}
+        if op not in ops:
+            raise ReferencePanic("fr_scan: op is 'product' or 'sum'")
+        ptr, have, sfmt, flags, _keep = self._scalars_arg(vecs)
+        if n <= 0 or have % n:
+            raise ReferencePanic("fr_scan: %d scalars are no whole number of vectors of n = %d" % (have, n))
+        batch = have // n
+        tb = ctypes.create_string_buffer(32 * max(batch, 1))
+        if out is not None:
+            if out.n < have or out.sfmt != sfmt:
+                raise ReferencePanic("fr_scan: out holds %d scalars, batch * n = %d (and has the inputs' format)" % (out.n, have))
+            rc = self.lib.kzg_fr_scan(self.ctx, ptr, n, batch, ops[op], int(bool(exclusive)), sfmt, flags | L.OUT_DEVICE, out.ptr, tb)
+            if rc:
+                _raise(self, rc)
+            return out, [self._scalar_from(tb.raw[32 * b:32 * b + 32], sfmt) for b in range(batch)]
+        buf = ctypes.create_string_buffer(32 * max(have, 1))
+        rc = self.lib.kzg_fr_scan(self.ctx, ptr, n, batch, ops[op], int(bool(exclusive)), sfmt, flags, buf, tb)
+        if rc:
+            _raise(self, rc)
+        return ([self._scalar_from(buf.raw[32 * k:32 * k + 32], sfmt) for k in range(have)],
+                [self._scalar_from(tb.raw[32 * b:32 * b + 32], sfmt) for b in range(batch)])
+
+    def prefix_product(self, vecs, n, exclusive=False, out=None):
+        return self.fr_scan(vecs, n, "product", exclusive, out)
+
+    def prefix_sum(self, vecs, n, exclusive=False, out=None):
+        return self.fr_scan(vecs, n, "sum", exclusive, out)
+
+    def grand_product(self, num, den, n, t, out=None, strict=True):
+        """kzg_fr_grand_product: z[b n] = 1, z[b n + i] = prod_{k < i} prod_j num[b][j][k] / den[b][j][k] for the len(num) / (t n) vectors
+        of t columns of n scalars (column j of vector b at element (b t + j) n), and every vector's total (1 for a valid permutation).
+        num, den: flat lists of ints, canonical blobs or DeviceBuffers, both of one kind.  Returns (z, totals, zero_den): z as ints, or
+        `out` (a DeviceBuffer of the inputs' scalar format) when one is given.  strict: a zero denominator raises; otherwise the
+        vectors that hold one are flagged in zero_den and their rows and totals are zero."""
+        ptr, have, sfmt, flags, _keep = self._scalars_arg(num)
+        dptr, dhave, dsfmt, dflags, _dkeep = self._scalars_arg(den)
+        if (sfmt, flags) != (dsfmt, dflags) or have != dhave:
+            raise ReferencePanic("grand_product: num and den have one size, format and residence")
+        if n <= 0 or t <= 0 or have % (t * n):
+            raise ReferencePanic("grand_product: %d scalars are no whole number of vectors of t * n = %d" % (have, t * n))
+        batch = have // (t * n)
+        tb = ctypes.create_string_buffer(32 * max(batch, 1))
+        zd = None if strict else (ctypes.c_int * max(batch, 1))()
+        if out is not None:
+            if out.n < batch * n or out.sfmt != sfmt:
+                raise ReferencePanic("grand_product: out holds %d scalars, batch * n = %d (and has the inputs' format)" % (out.n, batch * n))
+            buf, oflags = out.ptr, flags | L.OUT_DEVICE
+        else:
+            buf, oflags = ctypes.create_string_buffer(32 * max(batch * n, 1)), flags
+        rc = self.lib.kzg_fr_grand_product(self.ctx, ptr, dptr, n, t, batch, sfmt, oflags, buf, tb, zd)
+        if rc:
+            _raise(self, rc)
+        z = out if out is not None else [self._scalar_from(buf.raw[32 * k:32 * k + 32], sfmt) for k in range(batch * n)]
+        return z, [self._scalar_from(tb.raw[32 * b:32 * b + 32], sfmt) for b in range(batch)], [0] * batch if zd is None else [int(v) for v in zd[:batch]]
+
     def _multiopen_vectors_arg(self, vecs, length, pad):
         """(pointer, length, n_polys, sfmt, flags, keep-alive) of the polynomials of a multiopen call: a list of vectors (lists of ints,
         EvaluationDomains or Polynomials; with `pad` filled with zeros to the longest) or a flat blob / DeviceBuffer (length given)"""

@@ -149,6 +149,9 @@ struct kzg_ctx {
     int opt_multi_eval_segment = 0;       // kzg_poly_multi_eval: forced segment length, a power of two >= 8 (0 = planned from n, k, batch)
     int opt_multi_eval_points_chunk = 0;  // kzg_poly_multi_eval: at most this many points per pass (0 = 4096 alone); either option takes the kernels at any k
     int opt_poly_divide_base = 0;         // kzg_poly_divide: precision the base kernel of the series inverse produces, a power of two <= 64 (0 = 64)
+    int opt_fr_scan_tile = 0;             // kzg_fr_scan / kzg_fr_grand_product: elements one workgroup scans, a power of two in 8..2048 (0 = 2048)
+    int opt_fr_scan_stage = 0;            // ... and kzg_fr_batch_inverse: bytes of one staged piece of host data, a multiple of 32 up to 64 MiB (0 = 64 MiB)
+    int opt_fr_scan_chunk = 0;            // ... vectors per launch, at most, 1..65535 (0 = the rule min(65535, max(1, 65536 / tiles per vector)) alone)
     int opt_point_tree_leaf = 0;          // kzg_point_tree_setup: nodes of up to this many points are multiplied by the schoolbook kernels, a power of two <= 16 (0 = 16)
     int opt_g2_msm_slice = 0;             // kzg_msm_g2_bucket: points one workgroup sorts by digit, a power of two <= 2048 (0 = 2048)
     int opt_g2_msm_slots = 0;             // kzg_msm_g2_bucket: slice slots of the bucket arena = slices per chunk, 1..16 (0 = 16)
@@ -192,7 +195,7 @@ struct kzg_ctx {
     int accum_blocks_single() const { return opt_accum_blocks ? opt_accum_blocks : 256 * KZG_ACCUM_WAVES; }
     int accum_blocks_batch() const { return opt_accum_blocks_batch ? opt_accum_blocks_batch : 240 * KZG_ACCUM_WAVES; }
     int num_cus = 256;
-    std::atomic<bool> attr_msm_set{false}, attr_ntt_set{false}, attr_wide_set{false}, attr_sort20_set{false}, attr_horner_set{false}, attr_group_set{false};  // > 64 KiB dynamic-LDS opt-in done for this device
+    std::atomic<bool> attr_msm_set{false}, attr_ntt_set{false}, attr_wide_set{false}, attr_sort20_set{false}, attr_horner_set{false}, attr_group_set{false}, attr_frscan_set{false};  // > 64 KiB dynamic-LDS opt-in done for this device
     // profiling
     bool prof = false;
     bool prof_only_accum = false;  // events around k_accum_affine only (bench.py's timed region: two events per kernel launch cost 1.4 % there)
@@ -476,6 +479,9 @@ Fr host_omega(uint32_t exp);  // Montgomery-form 2^exp-th root of unity per comp
 // poly.hip
 int fr_convert(kzg_ctx *ctx, hipStream_t stream, Fr *d_data, size_t n, int to_mont);  // in place
 int batch_inverse(kzg_ctx *ctx, hipStream_t stream, const Fr *d_in, Fr *d_out, size_t n);
+// kzg_fr_batch_inverse: the same kernel with the running products at d_pre (d_out, or scratch when d_in == d_out), canonical words
+// in and out if canon, and the zeros counted into *d_zeros
+int batch_inverse_pub(kzg_ctx *ctx, hipStream_t stream, const Fr *d_in, Fr *d_out, Fr *d_pre, size_t n, bool canon, unsigned long long *d_zeros);
 // d_a[i] *= 1 / d_c[i] (zeros of c: a[i] = 0 and *d_flag |= 1); d_tmp: n elements of scratch
 int batch_inverse_mul(kzg_ctx *ctx, hipStream_t stream, const Fr *d_c, Fr *d_a, Fr *d_tmp, size_t n, int *d_flag);
 // Horner machinery: eval and linear quotient. d_coeffs in Montgomery or canonical form (linear ops:

@@ -9,6 +9,7 @@
 //     counter-based synthetic input generator used by bench.py.
 #include "common.h"
 #include "fr29.h"
+#include "fr_tile.h"
 
 namespace kzg {
 
@@ -29,30 +30,48 @@ int fr_convert(kzg_ctx *ctx, hipStream_t stream, Fr *d_data, size_t n, int to_m)
 
 constexpr int BI_K = 16;
 
-// out[i] = 1/in[i] (Montgomery), zeros map to zero.  in != out.  Thread t owns the BI_K elements t, t + T, t + 2T, ... (T threads:
-// every load and store of a wave is one contiguous 2 KiB run) and inverts their product once (Montgomery's trick).
-__global__ __launch_bounds__(256) void k_batch_inverse(const Fr *in, Fr *out, size_t n, size_t T) {
+// out[i] = 1/in[i] (Montgomery), zeros map to zero.  Thread t owns the BI_K elements t, t + T, t + 2T, ... (T threads: every load and
+// store of a wave is one contiguous 2 KiB run) and inverts their product once (Montgomery's trick).  The running products of the
+// first sweep go to pre: the engine's own callers pass pre == out (then in != out); kzg_fr_batch_inverse (PUB) passes scratch when
+// in == out, takes canonical words (canon: any 256-bit word as its residue in, canonical inverses out) and counts the zeros, one
+// atomic per wave.  A canonical a read as a Montgomery word stands for a / R, and the sweeps return R^2 / a in every element: two
+// from_mont of the ONE inverse a thread forms put that right.
+template <bool PUB>
+__global__ __launch_bounds__(256) void k_batch_inverse(const Fr *in, Fr *out, Fr *pre, size_t n, size_t T, int canon, unsigned long long *zeros) {
     size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T || t >= n) return;
-    Fr prod = Fr::one();
-    size_t last = t;
-    for (size_t i = t; i < n; i += T) {
-        out[i] = prod;
-        Fr v = in[i];
-        if (!v.is_zero()) prod = mul(prod, v);
-        last = i;
-    }
-    Fr iv = inv(prod);
-    for (size_t i = last;; i -= T) {
-        Fr v = in[i];
-        if (v.is_zero()) {
-            out[i] = Fr::zero();
-        } else {
-            Fr r = mul(iv, out[i]);
-            iv = mul(iv, v);
-            out[i] = r;
+    const bool live = t < T && t < n;
+    if (!PUB && !live) return;
+    unsigned nz = 0;
+    if (live) {
+        Fr prod = Fr::one();
+        size_t last = t;
+        for (size_t i = t; i < n; i += T) {
+            pre[i] = prod;
+            Fr v = in[i];
+            if (PUB && canon) v = fr_residue(v);
+            if (!v.is_zero()) prod = mul(prod, v);
+            else nz++;
+            last = i;
         }
-        if (i < T) break;  // i == t
+        Fr iv = inv(prod);
+        if (PUB && canon) iv = from_mont(from_mont(iv));
+        for (size_t i = last;; i -= T) {
+            Fr v = in[i];
+            if (PUB && canon) v = fr_residue(v);
+            if (v.is_zero()) {
+                out[i] = Fr::zero();
+            } else {
+                Fr r = mul(iv, pre[i]);
+                iv = mul(iv, v);
+                out[i] = r;
+            }
+            if (i < T) break;  // i == t
+        }
+    }
+    if (PUB) {  // (no thread of the block has left: whole waves reach the shuffles)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) nz += __shfl_down(nz, off);
+        if ((threadIdx.x & 63) == 0 && nz) atomicAdd(zeros, (unsigned long long)nz);
     }
 }
 
@@ -103,7 +122,15 @@ int batch_inverse(kzg_ctx *ctx, hipStream_t stream, const Fr *d_in, Fr *d_out, s
     if (!n) return KZG_OK;
     size_t T = (n + BI_K - 1) / BI_K;
     T = (T + 255) / 256 * 256;
-    KZG_LAUNCH(ctx, stream, "k_batch_inverse", k_batch_inverse, (unsigned)(T / 256), 256, 0, d_in, d_out, n, T);
+    KZG_LAUNCH(ctx, stream, "k_batch_inverse", k_batch_inverse<false>, (unsigned)(T / 256), 256, 0, d_in, d_out, d_out, n, T, 0, (unsigned long long *)nullptr);
+    return KZG_OK;
+}
+
+int batch_inverse_pub(kzg_ctx *ctx, hipStream_t stream, const Fr *d_in, Fr *d_out, Fr *d_pre, size_t n, bool canon, unsigned long long *d_zeros) {
+    if (!n) return KZG_OK;
+    size_t T = (n + BI_K - 1) / BI_K;
+    T = (T + 255) / 256 * 256;
+    KZG_LAUNCH(ctx, stream, "k_batch_inverse", k_batch_inverse<true>, (unsigned)(T / 256), 256, 0, d_in, d_out, d_pre, n, T, canon ? 1 : 0, d_zeros);
     return KZG_OK;
 }
 
@@ -111,8 +138,7 @@ int batch_inverse(kzg_ctx *ctx, hipStream_t stream, const Fr *d_in, Fr *d_out, s
 // Horner as a blocked suffix scan
 // ---------------------------------------------------------------------------------------------
 constexpr int HT = 256;          // threads per block
-constexpr int HE = 8;            // coefficients per thread
-constexpr int HB = HT * HE;      // coefficients per block
+constexpr int HB = HT * HE;      // coefficients per block (HE = 8 per thread: fr_tile.h)
 
 // Every multiplication of the three kernels is by a constant of the launch (x, a power of x), so it is the NTT's Shoup product on
 // 9 x 29-bit limbs (fr29.h: 143 multiply-adds and 37 shifts / masks, no carry folds) instead of the saturated Montgomery product
@@ -151,38 +177,9 @@ KZG_HD Fr29 horner8(const Fr a[HE], const ShoupConst &x) {
     return v;
 }
 
-// The block's 2048 coefficients (64 KiB) move between global memory and the threads' registers through LDS: a thread owns EIGHT
-// CONSECUTIVE coefficients (256 bytes), so direct loads / stores put the 64 lanes of an instruction 256 bytes apart -- every
-// instruction touched 64 lines for 16 bytes each (k_quotient_apply moved 64 MB in 59 us, k_horner_partials 32 MB in 38 us: 1.1 and
-// 0.9 TB/s).  Now lane l of an instruction moves the 16-byte chunk l of a 4 KiB run (whole lines), and the
-// thread's own 16 chunks sit in LDS at chunk index 17 t + j: the 272-byte stride spreads 16 lanes of a ds_read_b128 over all 64 banks.
-constexpr int H_CHUNKS = HB * 2;                         // 16-byte chunks per block
-constexpr int H_LDS_BYTES = (H_CHUNKS + HT) * 16;        // one pad chunk per thread segment
-typedef uint32_t __attribute__((ext_vector_type(4))) hchunk;
-
-__device__ __forceinline__ uint32_t h_slot(uint32_t c) { return c + (c >> 4); }
-
-// a[k] = coeffs[block start + 8 t + k] (zero beyond n), through the LDS tile `lds` (H_LDS_BYTES)
-__device__ __forceinline__ void load8_tile(const Fr *coeffs, size_t n, hchunk *lds, Fr a[HE]) {
-    const int t = threadIdx.x;
-    const size_t c0 = (size_t)blockIdx.x * H_CHUNKS, cn = n * 2;     // chunk indices; the array holds cn chunks
-    const hchunk *g = (const hchunk *)coeffs;
-    hchunk v[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const size_t c = c0 + (size_t)(t + j * HT);
-        v[j] = c < cn ? g[c] : hchunk{0u, 0u, 0u, 0u};
-    }
-#pragma unroll
-    for (int j = 0; j < 16; j++) lds[h_slot(t + j * HT)] = v[j];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < HE; k++) {
-        const hchunk lo = lds[17 * t + 2 * k], hi = lds[17 * t + 2 * k + 1];
-        a[k].v[0] = lo.x; a[k].v[1] = lo.y; a[k].v[2] = lo.z; a[k].v[3] = lo.w;
-        a[k].v[4] = hi.x; a[k].v[5] = hi.y; a[k].v[6] = hi.z; a[k].v[7] = hi.w;
-    }
-}
+// The block's 2048 coefficients (64 KiB) move between global memory and the threads' registers through LDS in whole lines: load8_tile /
+// tile_put / store8_tile of fr_tile.h.
+constexpr int H_LDS_BYTES = tile_lds_bytes(HT);
 
 // the constants of a launch: x, and x^8 squared k times (k < 8) -- the multipliers of the block tree / scan steps.  They come from
 // the host: every thread used to square its own copy eight times.
@@ -196,7 +193,7 @@ __global__ __launch_bounds__(HT) void k_horner_partials(const Fr *coeffs, size_t
     extern __shared__ __attribute__((aligned(16))) hchunk h_lds[];
     int t = threadIdx.x;
     Fr a[HE];
-    load8_tile(coeffs, n, h_lds, a);
+    load8_tile(coeffs, n, blockIdx.x, HT, h_lds, a);
     Fr29 v = fr29_normalize(horner8(a, c.x));
     __syncthreads();                 // the tile is consumed: its memory carries the tree
     uint32_t *sh = (uint32_t *)h_lds;
@@ -279,7 +276,7 @@ __global__ __launch_bounds__(HT) void k_quotient_apply(const Fr *coeffs, size_t 
     extern __shared__ __attribute__((aligned(16))) hchunk h_lds[];
     int t = threadIdx.x;
     Fr a[HE];
-    load8_tile(coeffs, n, h_lds, a);
+    load8_tile(coeffs, n, blockIdx.x, HT, h_lds, a);
     Fr29 v = horner8(a, c.x);
     const Fr29 Hb = fr29_unpack(H[blockIdx.x]);
     if (t == HT - 1) v = fr29_add_lazy(v, mul_const(Hb, c.p[0]));  // fold the carry from higher blocks in
@@ -305,21 +302,14 @@ __global__ __launch_bounds__(HT) void k_quotient_apply(const Fr *coeffs, size_t 
     Fr out = fr29_canonical(carry);
 #pragma unroll
     for (int k = HE - 1; k >= 0; k--) {
-        h_lds[17 * t + 2 * k] = hchunk{out.v[0], out.v[1], out.v[2], out.v[3]};
-        h_lds[17 * t + 2 * k + 1] = hchunk{out.v[4], out.v[5], out.v[6], out.v[7]};
+        tile_put(h_lds, t, k, out);
         if (k) {
             out = add(fr_residue(a[k]), fr29_pack_canonical(mul_const(carry, c.x)));
             carry = fr29_unpack(out);
         }
     }
     __syncthreads();
-    const size_t c0 = (size_t)blockIdx.x * H_CHUNKS, cq = (n - 1) * 2;     // q has n - 1 coefficients
-    hchunk *g = (hchunk *)q;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const size_t cc = c0 + (size_t)(t + j * HT);
-        if (cc < cq) g[cc] = h_lds[h_slot(t + j * HT)];
-    }
+    store8_tile(q, n - 1, blockIdx.x, HT, h_lds);     // q has n - 1 coefficients
 }
 
 static int horner_common(kzg_ctx *ctx, int lane, const Fr *d_coeffs, size_t n, const Fr &x, Fr **S, Fr **H, Fr **px,

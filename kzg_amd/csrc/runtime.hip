@@ -439,6 +439,15 @@ extern "C" int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value) 
     } else if (k == "poly_divide_base") {
         if (value != 0 && (value < 1 || value > 64 || (value & (value - 1)))) return fail(ctx, KZG_ERR_SHAPE, "poly_divide_base must be 0 (64) or a power of two in 1..64");
         ctx->opt_poly_divide_base = (int)value;
+    } else if (k == "fr_scan_tile") {
+        if (value != 0 && (value < 8 || value > 2048 || (value & (value - 1)))) return fail(ctx, KZG_ERR_SHAPE, "fr_scan_tile must be 0 (2048) or a power of two in 8..2048");
+        ctx->opt_fr_scan_tile = (int)value;
+    } else if (k == "fr_scan_stage") {
+        if (value != 0 && (value < 32 || value > (64 << 20) || (value & 31))) return fail(ctx, KZG_ERR_SHAPE, "fr_scan_stage must be 0 (64 MiB) or a multiple of 32 bytes up to 64 MiB");
+        ctx->opt_fr_scan_stage = (int)value;
+    } else if (k == "fr_scan_chunk") {
+        if (value < 0 || value > 65535) return fail(ctx, KZG_ERR_SHAPE, "fr_scan_chunk must be 0 (the rule alone) or 1..65535 vectors");
+        ctx->opt_fr_scan_chunk = (int)value;
     } else if (k == "point_tree_leaf") {
         if (value != 0 && (value < 1 || value > 16 || (value & (value - 1)))) return fail(ctx, KZG_ERR_SHAPE, "point_tree_leaf must be 0 (16) or a power of two in 1..16");
         ctx->opt_point_tree_leaf = (int)value;
