@@ -98,7 +98,10 @@ extern "C" {
  *   kzg_point_tree_setup                    1 <= k <= 2^22 points             (the plan holds 32 x (3 log2 K + 1) bytes per point of the padded
  *                                                                             size K: 9.0 GB at 2^22); kzg_point_tree_eval: n <= 2^28; any batch:
  *                                                                             chunks of max(1, 2^21 / K) blocks, the workspace does not grow with it
- *   kzg_srs_lagrange_from_monomial_g1       d <= 2^24;  _g2: d <= 1024
+ *   kzg_srs_lagrange_from_monomial_g1       d <= 2^24;  _g2: d <= 2^20
+ *   kzg_ntt_g1 / kzg_ntt_g2                 log_n <= 22 / log_n <= 20; any batch: chunks of at most 2^21 / 2^20 points (option
+ *                                                                             "group_ntt_chunk_points"), the workspace does not grow with it:
+ *                                                                             G1 224 B a point and <= 470 MB of scratch, G2 288 B and <= 302 MB
  *   kzg_fk20_setup                          log_n <= 22                      (the plan holds 2N points of 224 B: 1.9 GB there)
  *   kzg_fk20_cosets_setup                   log_n <= 22, 1 <= log_l <= log_n (the plan holds 8 x 2N rows of 128 B: 8.6 GB there)
  *   kzg_cosets_verifier_setup               log_n <= 22, log_l <= 8           (the plan's window table: 32 x l x 128 affine points of 96 B,
@@ -223,6 +226,13 @@ int kzg_sync(kzg_ctx *ctx);
  * "host_pairing" (1 / 0: the one pairing check that ends kzg_verify_cosets_batch / kzg_verify_eval_batch runs on the calling thread -- the same tower code
  *  compiled for the host -- instead of in a one-thread kernel; the same verdict, default 1),
  * "fk20_cosets_combine" (0 = the shared-doubling Straus kernel, default; 1 = one mul256 per term: the same bytes, for comparison),
+ * "g2_ntt_mul" (0 = the twiddle products of the G2 DFT split by the endomorphism psi into one joint chain, default; 1 = signed digits over
+ *  the whole scalar: the same bytes, for comparison), "group_ntt_chunk_points" (0 = default, 2^21 for kzg_ntt_g1 and 2^20 for kzg_ntt_g2;
+ *  1..2^22: the points of one chunk of arrays, at least one array) and "group_ntt_threads" (0 = default, 2^18 for G1 and 2^17 for G2; a
+ *  power of two in 256..2^17: the threads of one grid-stride launch of those calls and so their scratch slots); read per call; the same
+ *  bytes, for tests that make every thread loop at 2,048 points,
+ * "g2_lagrange_dft_from" (default 2048; a power of two in 2..2^20: kzg_srs_lagrange_from_monomial_g2 runs the G2 inverse DFT from this
+ *  size on and one d-term sum per row below it; the same points either way),
  * unknown keys -> KZG_ERR_SHAPE */
 int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value);
 /* "device=<d> lanes=<n> accum_streams=<m> hw_queues_found=<q> narrowed_from=<L>+<A>|none witness_cache_slots=<s>": the plan of the
@@ -267,6 +277,26 @@ int kzg_g1_sum(kzg_ctx *ctx, const void *points, size_t count, int pfmt, int fla
 /* `groups` independent sums: out[g] = sum_i points[g*count + i] (batched multi-GPU combine). */
 int kzg_g1_sum_batch(kzg_ctx *ctx, const void *points, size_t count, size_t groups, int pfmt, int flags, void *out,
                      int ofmt);
+/* The DFT over the group (not a reference method; EvaluationDomain::fft / ifft, src/ft.rs:100-140, with points for values): `batch`
+ * arrays of d = 2^log_n points, array b at points + b d, w = compute_omega(d).omega.
+ *   forward:  out[b][m] = sum_j [w^(jm)] P[b][j]
+ *   inverse:  out[b][j] = [1/d] sum_m [w^(-jm)] P[b][m]
+ * Natural order in and out; the inverse is scaled, so the two directions undo each other.  Moves a vector of commitments or proofs
+ * between coefficient and evaluation form, extends one by a low-degree extension (inverse, pad, forward), or builds Lagrange parameters
+ * from a ceremony file.  kzg_ntt_g1 runs the G1 DFT of the FK20 calls (radix 2, the twiddle products split by the GLV endomorphism,
+ * the 1/d one 255-bit product per point); log_n <= 22.  points in any KZG_G1_* format, out in any KZG_G1_* format; host memory, or
+ * device memory with KZG_IN_DEVICE / KZG_OUT_DEVICE; out may be points when the two formats have the same size.  The points are
+ * checked like those of kzg_srs_upload_g1 (curve and subgroup; option "trusted_points": curve only -- the caller then vouches for the
+ * subgroup, on which the endomorphism split relies): KZG_ERR_BAD_POINT with out untouched.  log_n == 0 copies the input, re-encoded;
+ * batch == 0: KZG_OK, nothing written.  KZG_ERR_SHAPE before out is touched: a NULL argument, an unknown format, log_n over the
+ * limit, in place with formats of different sizes.  The batch runs in chunks of at most 2^21 points (option
+ * "group_ntt_chunk_points"; with more than one chunk every point is checked before the first is written), so the workspace does not
+ * grow with batch.  Takes the context exclusively. */
+int kzg_ntt_g1(kzg_ctx *ctx, const void *points, uint32_t log_n, size_t batch, int inverse, int pfmt, int flags, void *out, int ofmt);
+/* The same over G2, on kernels of its own (kzg_amd/csrc/g2ntt.hip): log_n <= 20, chunks of at most 2^20 points, KZG_G2_* formats,
+ * the points checked like those of kzg_srs_upload_g2.  The twiddle products are split four ways by the endomorphism psi (option
+ * "g2_ntt_mul" = 1: signed digits over the whole scalar, the same bytes).  DESIGN.md section 3.5h. */
+int kzg_ntt_g2(kzg_ctx *ctx, const void *points, uint32_t log_n, size_t batch, int inverse, int pfmt, int flags, void *out, int ofmt);
 
 /* ---- multi-GPU: the SRS sharded over up to 8 GPUs, partial commitments combined over RCCL / xGMI ---------------------
  * (north star: "MSM shards the SRS across up to 8 GPUs with an RCCL all-reduce of partial bucket sums"; the seam is the
@@ -684,7 +714,9 @@ int kzg_verify_poly_eval(kzg_ctx *ctx, const kzg_srs *monomial, const void *comm
 int kzg_srs_setup_g2(kzg_ctx *ctx, const void *s, int sfmt, size_t n, kzg_srs_g2 **out);
 /* [L_i(s)] H over the size-d domain (lagrange_basis_h of KZGVerifierEvalForm::new, src/eval_form.rs:150). */
 int kzg_srs_setup_lagrange_g2(kzg_ctx *ctx, const void *s, int sfmt, size_t d, kzg_srs_g2 **out);
-/* compute_lagrange_basis, G2 half, from hs alone (src/eval_form.rs:254-280); d = len(hs) a power of two <= 1024. */
+/* compute_lagrange_basis, G2 half, from hs alone (src/eval_form.rs:254-280); d = len(hs) a power of two <= 2^20 (KZG_ERR_SHAPE
+ * otherwise).  Below option "g2_lagrange_dft_from" (default 2048) every row is one d-term G2 sum (d^2 scalar multiplications); from it
+ * on the basis is the G2 inverse DFT of hs (kzg_ntt_g2's kernels).  Both paths give the same group elements, so the same bytes. */
 int kzg_srs_lagrange_from_monomial_g2(kzg_ctx *ctx, const kzg_srs_g2 *hs, kzg_srs_g2 **out);
 /* KZGParams.hs supplied by the caller (Vec<G2Projective> = KZG_G2_JACOBIAN_MONT_288, or any G2 format);
  * KZG_ERR_BAD_POINT if a point does not decode / is not on the twist. */

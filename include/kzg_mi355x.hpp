@@ -114,6 +114,28 @@ inline G2Affine msm_g2_bucket(const Engine &e, const kzg_srs_g2 *hs, const std::
     return out;
 }
 
+// kzg_ntt_g1 / kzg_ntt_g2: the DFT over the group of points.size() / 2^log_n arrays of 2^log_n affine points back to back, over
+// compute_omega(2^log_n): out[m] = sum_j [w^(jm)] P[j], or with `inverse` out[j] = [1/d] sum_m [w^(-jm)] P[m] (the two undo each
+// other).  Natural order in and out.  Not a reference method.
+inline std::vector<G1Affine> ntt_g1(const Engine &e, const std::vector<G1Affine> &points, uint32_t log_n, bool inverse = false) {
+    static_assert(sizeof(G1Affine) == 96, "G1Affine is the 96-byte affine Montgomery encoding");
+    const size_t d = (size_t)1 << log_n;
+    if (log_n > 22 || points.size() % d != 0) throw ReferencePanic("ntt_g1: shape");
+    std::vector<G1Affine> out(points.size());
+    if (points.empty()) return out;
+    e.check(kzg_ntt_g1(e.ctx(), points.data(), log_n, points.size() / d, inverse ? 1 : 0, KZG_G1_AFFINE_MONT_96, 0, out.data(), KZG_G1_AFFINE_MONT_96));
+    return out;
+}
+inline std::vector<G2Affine> ntt_g2(const Engine &e, const std::vector<G2Affine> &points, uint32_t log_n, bool inverse = false) {
+    static_assert(sizeof(G2Affine) == 192, "G2Affine is the 192-byte affine Montgomery encoding");
+    const size_t d = (size_t)1 << log_n;
+    if (log_n > 20 || points.size() % d != 0) throw ReferencePanic("ntt_g2: shape");
+    std::vector<G2Affine> out(points.size());
+    if (points.empty()) return out;
+    e.check(kzg_ntt_g2(e.ctx(), points.data(), log_n, points.size() / d, inverse ? 1 : 0, KZG_G2_AFFINE_MONT_192, 0, out.data(), KZG_G2_AFFINE_MONT_192));
+    return out;
+}
+
 class PointTree;
 struct Polynomial {  // src/polynomial.rs:24-27
     size_t degree = 0;

@@ -142,6 +142,14 @@ int kzg_test_arith(kzg_ctx *ctx, int op, const void *in, size_t in_rec, size_t n
  * record, 64 per block: out[i] = acc[i] + pts[i].  acc: Jacobian Montgomery 288 B (any Z; Z = 0 the identity), pts and out: affine
  * Montgomery 192 B (all zero the identity).  1 <= n <= 4096 */
 int kzg_test_g2_madd(kzg_ctx *ctx, const void *acc_jacobian, const void *pts_affine, size_t n, void *out_affine);
+/* the twiddle multiplier of the G2 DFT alone (kzg_amd/csrc/g2ntt.hip): out[i] = [k_i] P_i.  pts_affine and out_affine: affine
+ * Montgomery 192 B (all zero the identity), P_i in the r-torsion; k_canonical: n scalars below r.  route 0 = the psi split and the joint
+ * chain, 1 = signed 4-bit digits over the whole scalar.  1 <= n <= 65536 */
+int kzg_test_g2_mul_gls(kzg_ctx *ctx, const void *pts_affine, const void *k_canonical, size_t n, int route, void *out_affine);
+/* the recoding of that multiplier for one canonical scalar k < r, on the calling thread (no GPU work): words[i] = k_i of
+ * k = k_0 + k_1 u + k_2 u^2 + k_3 u^3 (u = 0xd201000000010000), digits[17 i + j] = the signed 4-bit digit j of k_i in [-8, 7], least
+ * significant first, digits[17 i + 16] = the carry (0 or 1) */
+int kzg_test_g2_gls_recode(const void *k_canonical, uint64_t *words, int8_t *digits);
 /* pretend `srs` is resident on GPU `device` (the "SRS of another GPU" error of every MSM entry point, on a one-GPU box) */
 int kzg_test_srs_set_device(struct kzg_srs *srs, int device);
 /* the same for the G2 points and for a kzg_cosets_verifier (kzg_amd/csrc/verify_cosets.hip) */

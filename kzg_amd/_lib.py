@@ -74,6 +74,8 @@ def load(path=None):
         "kzg_msm_g1_batch": (i32, [vp, vp, sz, vp, sz, sz, i32, i32, vp, i32]),
         "kzg_g1_sum": (i32, [vp, vp, sz, i32, i32, vp, i32]),
         "kzg_g1_sum_batch": (i32, [vp, vp, sz, sz, i32, i32, vp, i32]),
+        "kzg_ntt_g1": (i32, [vp, vp, u32, sz, i32, i32, i32, vp, i32]),
+        "kzg_ntt_g2": (i32, [vp, vp, u32, sz, i32, i32, i32, vp, i32]),
         "kzg_mctx_create": (i32, [ctypes.POINTER(i32), i32, c_void_pp]),
         "kzg_mctx_unique_id": (i32, [vp]),
         "kzg_mctx_create_rank": (i32, [i32, i32, i32, vp, c_void_pp]),

@@ -222,6 +222,27 @@ class Engine:
             _raise(self, rc)
         return [out.raw[i * psz:(i + 1) * psz] for i in range(groups)]
 
+    def _ntt_group(self, fn, sizes, points, log_n, batch, inverse, pfmt, ofmt):
+        d = 1 << log_n
+        if batch is None:
+            batch = len(points) // (d * sizes[pfmt])
+        assert len(points) == batch * d * sizes[pfmt], "points must hold batch x 2^log_n points in pfmt"
+        out = ctypes.create_string_buffer(max(batch * d * sizes[ofmt], 1))
+        rc = fn(self.ctx, points, log_n, batch, 1 if inverse else 0, pfmt, 0, out, ofmt)
+        if rc:
+            _raise(self, rc)
+        return out.raw[: batch * d * sizes[ofmt]]
+
+    def ntt_g1(self, points, log_n, batch=None, inverse=False, pfmt=L.G1_AFFINE_MONT, ofmt=L.G1_AFFINE_MONT):
+        """kzg_ntt_g1: the DFT of `batch` arrays of 2^log_n G1 points (a blob in pfmt, arrays one after the other) over
+        compute_omega(2^log_n): out[m] = sum_j [w^(jm)] P[j]; inverse: out[j] = [1/d] sum_m [w^(-jm)] P[m].  Natural order in and out;
+        returns the blob in ofmt."""
+        return self._ntt_group(self.lib.kzg_ntt_g1, L.POINT_BYTES, points, log_n, batch, inverse, pfmt, ofmt)
+
+    def ntt_g2(self, points, log_n, batch=None, inverse=False, pfmt=L.G2_AFFINE_MONT, ofmt=L.G2_AFFINE_MONT):
+        """kzg_ntt_g2: the same over G2 (log_n <= 20)."""
+        return self._ntt_group(self.lib.kzg_ntt_g2, L.G2_POINT_BYTES, points, log_n, batch, inverse, pfmt, ofmt)
+
     def ntt(self, data, log_n, inverse=False):
         """data: DeviceBuffer (in place) or ints/blob (returns list of ints)."""
         if isinstance(data, DeviceBuffer):
@@ -780,6 +801,13 @@ class Srs:
             _raise(self.engine, rc)
         return out.raw[: 96 * n]
 
+    def dft(self, inverse=False):
+        """A new Srs holding the group DFT (kzg_ntt_g1) of these points; len(self) must be a power of two.  The inverse of a monomial
+        SRS is its Lagrange basis (compute_lagrange_basis), the forward transform goes back."""
+        n = len(self)
+        assert n and n & (n - 1) == 0, "the DFT needs a power-of-two number of points"
+        return Srs.upload(self.engine, self.engine.ntt_g1(self.download(), n.bit_length() - 1, 1, inverse), n)
+
     def free(self):
         if self.handle:
             self.engine.lib.kzg_srs_free(self.engine.ctx, self.handle)
@@ -1166,6 +1194,12 @@ class SrsG2:
             _raise(self.engine, rc)
         return out.raw
 
+    def dft(self, inverse=False):
+        """A new SrsG2 holding the group DFT (kzg_ntt_g2) of these points; len(self) must be a power of two, at most 2^20."""
+        n = len(self)
+        assert n and n & (n - 1) == 0, "the DFT needs a power-of-two number of points"
+        return SrsG2.upload(self.engine, self.engine.ntt_g2(self.download(), n.bit_length() - 1, 1, inverse), n)
+
     def free(self):
         if self.handle:
             self.engine.lib.kzg_srs_g2_free(self.engine.ctx, self.handle)
@@ -1253,7 +1287,9 @@ def compute_lagrange_basis(params):
 
 
 def compute_lagrange_basis_g2(params):
-    """compute_lagrange_basis (src/eval_form.rs:254-280), G2 half, from hs alone (hs must hold all d powers)."""
+    """compute_lagrange_basis (src/eval_form.rs:254-280), G2 half, from hs alone (hs must hold all d powers).  Any power-of-two d up
+    to 2^20: sizes from 2048 on (option "g2_lagrange_dft_from") run the G2 inverse DFT, smaller ones one d-term sum per row; with
+    compute_lagrange_basis this gives KZGVerifierEvalForm its two bases from a ceremony SRS, with no secret."""
     e = params.gs.engine
     if params.hs is None:
         raise ReferencePanic("KZGParams.hs is empty")

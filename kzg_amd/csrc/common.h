@@ -157,6 +157,10 @@ struct kzg_ctx {
     int opt_g2_msm_slots = 0;             // kzg_msm_g2_bucket: slice slots of the bucket arena = slices per chunk, 1..16 (0 = 16)
     int opt_host_pairing = 1;         // kzg_verify_cosets_batch, kzg_verify_eval_batch: the one pairing check runs on the calling thread (vcb_finish.h); 0 = in a one-thread kernel
     int opt_fk20_cosets_combine = 0;   // the coset combination of kzg_witness_cosets_*: 0 = Straus (shared doublings), 1 = mul256 per term
+    int opt_g2_ntt_mul = 0;            // the twiddle products of the G2 DFT: 0 = psi split and one joint chain, 1 = signed digits over the whole scalar
+    int opt_group_ntt_chunk_points = 0;   // kzg_ntt_g1 / kzg_ntt_g2: points per chunk of arrays, at most (0 = 2^21 for G1, 2^20 for G2)
+    int opt_group_ntt_threads = 0;        // ... threads of one grid-stride launch = scratch slots, a power of two >= 256 (0 = 2^18 for G1, 2^17 for G2)
+    int opt_g2_lagrange_dft_from = 2048;  // kzg_srs_lagrange_from_monomial_g2: sizes from this on run the G2 inverse DFT (below: one d-term sum per row)
     int opt_ntt_kernel = KZG_NTT_KERNEL_DEFAULT;  // 0: three-phase passes (k_ntt_pass1/2); 1: load/store fused into the first/last stage pair (k_ntt_tile); 2: 1 + two butterflies per thread
     int opt_ntt_three_from = 23;       // NTT sizes from 2^this on take three passes of <= 2^8 points (ntt_run3); 0 = never
     int opt_ntt_vec2_log = 1;          // pass 2: at most 2^v rows per tile (rows are contiguous: narrow tiles cost no coalescing on the load side)

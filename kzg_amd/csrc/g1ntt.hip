@@ -162,8 +162,8 @@ __global__ __launch_bounds__(64) void k_fk20_emit(const MsmPoint *P, size_t pstr
     }
 }
 
-static unsigned grid_for(size_t work, size_t block) {
-    size_t t = std::min(work, G1NTT_MAX_THREADS);
+static unsigned grid_for(size_t work, size_t block, size_t max_threads = G1NTT_MAX_THREADS) {
+    size_t t = std::min(work, max_threads);
     size_t g = (t + block - 1) / block;
     return (unsigned)(g ? g : 1);
 }
@@ -184,11 +184,12 @@ static int glv_table(kzg_ctx *ctx, hipStream_t st, const Fr &base, size_t count,
 
 // one G1 DFT of size d = 2^logd over `batch` arrays.  forward: DIF (natural -> bit-reversed); else DIT with inverse twiddles
 // (bit-reversed -> natural), half_out: only the first half of the last stage.  tw: recoded twiddles of a size-D table, tws = D / d.
+// max_threads: the threads of a launch = the slots `scratch` has (kzg_ntt_g1's option; everyone else has scratch_points)
 static int g1_dft(kzg_ctx *ctx, hipStream_t st, MsmPoint *P, size_t pstride, uint32_t logd, size_t batch, const GlvTw *tw, size_t tws,
-                  bool forward, bool half_out, MsmPoint *scratch, const Fq30 &beta) {
+                  bool forward, bool half_out, MsmPoint *scratch, const Fq30 &beta, size_t max_threads = G1NTT_MAX_THREADS) {
     const size_t d = (size_t)1 << logd;
     if (d < 2) return KZG_OK;
-    const unsigned g = grid_for(batch * d / 2, 256);
+    const unsigned g = grid_for(batch * d / 2, 256, max_threads);
     if (forward) {
         for (size_t m = d / 2; m >= 2; m /= 2)
             KZG_LAUNCH(ctx, st, "k_g1ntt_dif", k_g1ntt_dif, g, 256, 0, P, pstride, d, m, tw, tws, batch, scratch, beta);
@@ -699,6 +700,100 @@ extern "C" int kzg_srs_lagrange_from_monomial_g1(kzg_ctx *ctx, const kzg_srs *mo
         return rc;
     }
     *out = s;
+    return KZG_OK;
+}
+
+// ---- kzg_ntt_g1: the DFT above as a call of its own ------------------------------------------------------------------------------
+// Both directions run g1_dft as a DIF (natural in, bit-reversed out; the inverse over w^-1, as compute_lagrange_basis above), so the
+// decoded points are taken as they come and k_fk20_emit reads the result out bit-reversed; the inverse's 1/d is one mul256 per
+// point in between.  `batch` arrays in chunks of at most 2^21 points (option "group_ntt_chunk_points").
+namespace kzg {
+
+constexpr size_t G1NTT_CHUNK_POINTS = (size_t)1 << 21;
+
+// P[u] = [k] P[u], k canonical
+__global__ __launch_bounds__(256) void k_g1ntt_scale(MsmPoint *P, size_t count, Fr k, MsmPoint *scratch, Fq30 beta) {
+    const size_t nt = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (size_t u = tid; u < count; u += nt) P[u] = mul256(P[u], k, scratch + tid, nt, beta);
+}
+
+}  // namespace kzg
+
+extern "C" int kzg_ntt_g1(kzg_ctx *ctx, const void *points, uint32_t log_n, size_t batch, int inverse, int pfmt, int flags, void *out,
+                          int ofmt) {
+    if (!ctx) return KZG_ERR_SHAPE;
+    Guard g(ctx);
+    KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const size_t psz = point_format_bytes(pfmt), osz = point_format_bytes(ofmt);
+    if (!psz || !osz) return fail(ctx, KZG_ERR_SHAPE, "unknown G1 point format");
+    if (log_n > FK20_MAX_LOG) return fail(ctx, KZG_ERR_SHAPE, "kzg_ntt_g1: log_n <= 22 (documented limit)");
+    if (batch == 0) return KZG_OK;
+    if (!points || !out) return fail(ctx, KZG_ERR_SHAPE, "kzg_ntt_g1: NULL buffer");
+    const size_t d = (size_t)1 << log_n, half = d > 1 ? d / 2 : 1;
+    if (batch > (SIZE_MAX / 224) >> log_n) return fail(ctx, KZG_ERR_SHAPE, "batch too large");
+    if (out == points && psz != osz) return fail(ctx, KZG_ERR_SHAPE, "kzg_ntt_g1: in place needs formats of equal size");
+    const bool in_dev = (flags & KZG_IN_DEVICE) != 0, out_dev = (flags & KZG_OUT_DEVICE) != 0;
+    const size_t cpts = ctx->opt_group_ntt_chunk_points ? (size_t)ctx->opt_group_ntt_chunk_points : G1NTT_CHUNK_POINTS;
+    const size_t chunk = std::max<size_t>(1, cpts / d), B0 = std::min(chunk, batch), pts0 = B0 * d;
+    const size_t cap = ctx->opt_group_ntt_threads ? (size_t)ctx->opt_group_ntt_threads : G1NTT_MAX_THREADS;
+    const size_t scr = (size_t)grid_for(pts0, 256, cap) * 256 * G1NTT_TAB;  // the scaling's pts0 threads; the stages have half as many
+    KZG_TRY(lane_reserve(ctx, 0, align_up(pts0 * sizeof(MsmPoint), 256) + align_up(pts0 * sizeof(G1Xyzz), 256) + align_up(scr * sizeof(MsmPoint), 256) +
+                                     align_up(half * 32, 256) + align_up(half * sizeof(GlvTw), 256) + align_up(pts0 * osz, 256) +
+                                     (in_dev ? 0 : align_up(pts0 * psz, 256)) + 65536));
+    hipStream_t st = ctx->lanes[0].stream;
+    MsmPoint *P = (MsmPoint *)lane_alloc(ctx, 0, pts0 * sizeof(MsmPoint));
+    G1Xyzz *dec = (G1Xyzz *)lane_alloc(ctx, 0, pts0 * sizeof(G1Xyzz));
+    MsmPoint *scratch = (MsmPoint *)lane_alloc(ctx, 0, scr * sizeof(MsmPoint));
+    Fr *pw = (Fr *)lane_alloc(ctx, 0, half * 32);
+    GlvTw *tw = (GlvTw *)lane_alloc(ctx, 0, half * sizeof(GlvTw));
+    uint8_t *enc = (uint8_t *)lane_alloc(ctx, 0, pts0 * osz);  // also with KZG_OUT_DEVICE: `out` may be `points`
+    uint8_t *d_raw = in_dev ? nullptr : (uint8_t *)lane_alloc(ctx, 0, pts0 * psz);
+    int *bad = (int *)lane_alloc(ctx, 0, 256);
+    if (!P || !dec || !scratch || !pw || !tw || !enc || (!in_dev && !d_raw) || !bad) return fail(ctx, KZG_ERR_ALLOC, "workspace");
+    const Fq30 beta = beta30();
+    const Fr w = host_omega(log_n);
+    const Fr dinv = from_mont(inv(from_u64<FrParams>((uint64_t)d)));  // canonical
+    const uint8_t *src = (const uint8_t *)points;
+    uint8_t *dst = (uint8_t *)out;
+    const char *bad_msg = "a G1 point failed to decode, is not on the curve or not in the r-torsion subgroup";
+    KZG_HIP_CHECK(ctx, hipMemsetAsync(bad, 0, sizeof(int), st));
+    if (log_n >= 2) KZG_TRY(glv_table(ctx, st, inverse ? inv(w) : w, half, pw, tw));
+    // Nothing is written before every point has passed the check.  One chunk: decoded once, checked, transformed.  Several: a pass
+    // that only checks, then the transforms on points decoded again without the checks.
+    const bool two_pass = batch > chunk;
+    int hbad = 0;
+    for (int pass = two_pass ? 0 : 1; pass < 2; pass++) {
+        const int level = (two_pass && pass == 1) ? (int)POINTS_TRUSTED : untrusted_level(ctx);
+        for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+            const size_t B = std::min(chunk, batch - b0), n = B * d;
+            const uint8_t *raw = src + b0 * d * psz;
+            if (!in_dev) {
+                KZG_HIP_CHECK(ctx, hipMemcpyAsync(d_raw, raw, n * psz, hipMemcpyHostToDevice, st));
+                raw = d_raw;
+            }
+            KZG_TRY(decode_points(ctx, st, raw, n, pfmt, dec, bad, level));
+            if (pass == 0) continue;
+            if (!two_pass) {
+                KZG_HIP_CHECK(ctx, hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
+                KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+                if (hbad) return fail(ctx, KZG_ERR_BAD_POINT, bad_msg);
+            }
+            KZG_TRY(points_to30(ctx, st, dec, P, n));
+            KZG_TRY(g1_dft(ctx, st, P, d, log_n, B, tw, 1, true, false, scratch, beta, cap));
+            if (inverse && d > 1) KZG_LAUNCH(ctx, st, "k_g1ntt_scale", k_g1ntt_scale, grid_for(n, 256, cap), 256, 0, P, n, dinv, scratch, beta);
+            KZG_LAUNCH(ctx, st, "k_fk20_emit", k_fk20_emit, (unsigned)std::min<size_t>((n + 63) / 64, 16384), 64, 0, (const MsmPoint *)P, d,
+                       log_n, B, enc, ofmt, osz);
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(dst + b0 * d * osz, enc, n * osz, out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+        }
+        if (pass == 0) {
+            KZG_HIP_CHECK(ctx, hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
+            KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+            if (hbad) return fail(ctx, KZG_ERR_BAD_POINT, bad_msg);
+        }
+    }
+    KZG_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    KZG_HIP_CHECK(ctx, hipGetLastError());
+    if (ctx->prof) prof_collect(ctx);
     return KZG_OK;
 }
 

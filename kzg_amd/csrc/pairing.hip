@@ -394,6 +394,10 @@ int kzg::g2_encode_run(kzg_ctx *ctx, hipStream_t st, const G2Affine *d_in, size_
     if (n) KZG_LAUNCH(ctx, st, "k_g2_encode", k_g2_encode, (unsigned)((n + 63) / 64), 64, 0, d_in, n, fmt, d_out, g2_format_bytes(fmt));
     return KZG_OK;
 }
+int kzg::g2_decode_run(kzg_ctx *ctx, hipStream_t st, const uint8_t *d_raw, size_t n, int fmt, G2Affine *d_out, int *d_bad, int level) {
+    if (n) KZG_LAUNCH(ctx, st, "k_g2_decode", k_g2_decode, (unsigned)((n + 63) / 64), 64, 0, d_raw, n, fmt, d_out, d_bad, level);
+    return KZG_OK;
+}
 
 // ------------------------------------------------------------------------------------------------
 // C ABI: G2 SRS
@@ -517,17 +521,20 @@ static int g2_msm_device(kzg_ctx *ctx, const kzg_srs_g2 *srs, size_t offset, con
     return KZG_OK;
 }
 
-// compute_lagrange_basis (src/eval_form.rs:254-280), G2 half: row i = MSM(hs[..d], w^(-ij)/d), as for G1
-// (kzg_srs_lagrange_from_monomial_g1).  d*d scalar multiplications: meant for the sizes the reference's O(d^3)
-// construction can handle; larger bases come from kzg_srs_setup_lagrange_g2 or an upload.
+// compute_lagrange_basis (src/eval_form.rs:254-280), G2 half.  Below option "g2_lagrange_dft_from" (default 2048): row i =
+// MSM(hs[..d], w^(-ij)/d), d*d scalar multiplications, the sizes the reference's O(d^3) construction can handle.  From it on, up to
+// 2^20: the G2 inverse DFT of hs (g2ntt.hip), as kzg_srs_lagrange_from_monomial_g1 does for G1.  Both give the same affine points.
 extern "C" int kzg_srs_lagrange_from_monomial_g2(kzg_ctx *ctx, const kzg_srs_g2 *hs, kzg_srs_g2 **out) {
     if (!ctx || !hs || !out) return KZG_ERR_SHAPE;
     Lock g(ctx);
     KZG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     size_t d = hs->n;
     if (d == 0 || (d & (d - 1))) return fail(ctx, KZG_ERR_SHAPE, "assert!(d & (d - 1) == 0) (src/eval_form.rs:255-256)");
-    if (d > 1024) return fail(ctx, KZG_ERR_SHAPE, "compute_lagrange_basis (G2) from hs is limited to d <= 1024; use kzg_srs_setup_lagrange_g2 or upload the basis");
+    if (d > ((size_t)1 << G2NTT_MAX_LOG))
+        return fail(ctx, KZG_ERR_SHAPE, "compute_lagrange_basis (G2) from hs is limited to d <= 2^20; use kzg_srs_setup_lagrange_g2 or upload the basis");
+    if (hs->device != ctx->device) return fail(ctx, KZG_ERR_SHAPE, "the G2 points are resident on another GPU than this context's");
     uint32_t exp = (uint32_t)ilog2_ceil(d);
+    const bool by_dft = d >= (size_t)ctx->opt_g2_lagrange_dft_from;
     hipStream_t st = ctx->lanes[0].stream;
     kzg_srs_g2 *s = new kzg_srs_g2();
     s->n = d;
@@ -538,8 +545,8 @@ extern "C" int kzg_srs_lagrange_from_monomial_g2(kzg_ctx *ctx, const kzg_srs_g2 
     }
     Fr omega_inv = inv(host_omega(exp));
     Fr dinv = inv(from_u64<FrParams>((uint64_t)d));
-    int rc = KZG_OK;
-    for (size_t i = 0; i < d && rc == KZG_OK; i++) {
+    int rc = by_dft ? g2_lagrange_dft(ctx, hs->pts, exp, s->pts) : KZG_OK;
+    for (size_t i = 0; i < d && rc == KZG_OK && !by_dft; i++) {
         rc = lane_reserve(ctx, 0, d * 32 + (d + 64) * sizeof(G2Jacobian) + 65536);
         Fr *sc = rc == KZG_OK ? (Fr *)lane_alloc(ctx, 0, d * 32) : nullptr;
         if (rc == KZG_OK && !sc) rc = fail(ctx, KZG_ERR_ALLOC, "workspace");

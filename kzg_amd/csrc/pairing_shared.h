@@ -24,6 +24,12 @@ int fetch_ok(kzg_ctx *ctx, int lane, const uint8_t *d_ok, const int *d_bad, size
 // bytes of one G2 point in a KZG_G2_* format (0: unknown format); k_g2_encode: n affine points -> d_out, one after the other
 size_t g2_point_bytes(int fmt);
 int g2_encode_run(kzg_ctx *ctx, hipStream_t st, const G2Affine *d_in, size_t n, int fmt, uint8_t *d_out);
+// k_g2_decode: n points of a KZG_G2_* format at d_raw -> affine at d_out, checked at `level` (*d_bad |= 1 at a point that fails)
+int g2_decode_run(kzg_ctx *ctx, hipStream_t st, const uint8_t *d_raw, size_t n, int fmt, G2Affine *d_out, int *d_bad, int level);
+// g2ntt.hip, the G2 DFT: d_out[i] = (1/d) sum_j w^(-ij) d_in[j] over d = 2^log_d <= 2^20 affine points, on lane 0's stream and arena
+// (compute_lagrange_basis, G2 half); d_out may not overlap d_in
+constexpr uint32_t G2NTT_MAX_LOG = 20;
+int g2_lagrange_dft(kzg_ctx *ctx, const G2Affine *d_in, uint32_t log_d, G2Affine *d_out);
 // g2_msm.hip, the bucket method behind kzg_msm_g2_bucket: sum_i d_sc[i] srs[offset + i] -> d_out (affine) on lane 0's stream; d_sc
 // canonical and reduced (vcb_canon); takes g2_msm_bucket_workspace_bytes from lane 0's arena
 size_t g2_msm_bucket_workspace_bytes(const kzg_ctx *ctx);

@@ -421,6 +421,19 @@ extern "C" int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value) 
     } else if (k == "fk20_cosets_combine") {
         if (value != 0 && value != 1) return fail(ctx, KZG_ERR_SHAPE, "fk20_cosets_combine must be 0 (Straus) or 1 (per term)");
         ctx->opt_fk20_cosets_combine = (int)value;
+    } else if (k == "g2_ntt_mul") {
+        if (value != 0 && value != 1) return fail(ctx, KZG_ERR_SHAPE, "g2_ntt_mul must be 0 (psi split, joint chain) or 1 (signed digits over the whole scalar)");
+        ctx->opt_g2_ntt_mul = (int)value;
+    } else if (k == "group_ntt_chunk_points") {
+        if (value < 0 || value > (1 << 22)) return fail(ctx, KZG_ERR_SHAPE, "group_ntt_chunk_points must be 0 (2^21 for G1, 2^20 for G2) or 1..2^22 points");
+        ctx->opt_group_ntt_chunk_points = (int)value;
+    } else if (k == "group_ntt_threads") {
+        if (value != 0 && (value < 256 || value > (1 << 17) || (value & (value - 1))))
+            return fail(ctx, KZG_ERR_SHAPE, "group_ntt_threads must be 0 (2^18 for G1, 2^17 for G2) or a power of two in 256..2^17");
+        ctx->opt_group_ntt_threads = (int)value;
+    } else if (k == "g2_lagrange_dft_from") {
+        if (value < 2 || value > (1 << 20) || (value & (value - 1))) return fail(ctx, KZG_ERR_SHAPE, "g2_lagrange_dft_from must be a power of two in 2..2^20");
+        ctx->opt_g2_lagrange_dft_from = (int)value;
     } else if (k == "verify_cosets_chunk") {
         if (value < 0 || value > (1 << 20)) return fail(ctx, KZG_ERR_SHAPE, "verify_cosets_chunk must be 0 (the rule alone) or 1..2^20 cells");
         ctx->opt_verify_cosets_chunk = (int)value;
