@@ -388,7 +388,7 @@ int kzg_witness_coeff_sharded(kzg_mctx *m, const kzg_msrs *srs, const void *coef
                               int sfmt, int flags, void *out, int ofmt);
 /* KZGProver::create_witness_batched over the group (src/coeff_form.rs:83-111): interpolant and quotient (p - I)/Z replicated on
  * every GPU (NTTs do not shard), the quotient MSM sharded like the commit.  Arguments and errors as kzg_witness_coeff_batched;
- * coeffs as for kzg_witness_coeff_sharded.  out_w: one point (host), out_r: the interpolant, on every rank. */
+ * coeffs as for kzg_witness_coeff_sharded.  out_w: one point (host), out_r: the interpolant (host, sfmt), on every rank. */
 int kzg_witness_coeff_batched_sharded(kzg_mctx *m, const kzg_msrs *srs, const void *coeffs, size_t n, const void *xs,
                                       const void *ys, size_t k, int sfmt, int flags, void *out_w, int ofmt, void *out_r,
                                       size_t *out_r_len);
@@ -424,7 +424,7 @@ int kzg_coset_ntt_fr(kzg_ctx *ctx, void *data, uint32_t log_n, int inverse, int 
 int kzg_ntt_fr_batch(kzg_ctx *ctx, void *data, uint32_t log_n, size_t batch, size_t stride, int inverse, int flags);
 int kzg_coset_ntt_fr_batch(kzg_ctx *ctx, void *data, uint32_t log_n, size_t batch, size_t stride, int inverse, int sfmt, int flags);
 
-/* EvaluationDomain::z (src/ft.rs:182-187): tau^d - 1.  Host-only helper. */
+/* EvaluationDomain::z (src/ft.rs:182-187): tau^d - 1.  Host-only helper; tau (< r in canonical form) and out are both in sfmt. */
 int kzg_domain_z(size_t d, const void *tau, int sfmt, void *out);
 /* EvaluationDomain::divide_by_z_on_coset (src/ft.rs:192-217): data[i] *= 1 / (7^d - 1), d = 2^log_n. */
 int kzg_divide_by_z_on_coset(kzg_ctx *ctx, void *data, uint32_t log_n, int sfmt, int flags);
@@ -910,7 +910,7 @@ int kzg_verify_multiopen(kzg_ctx *ctx, const kzg_srs *gs, const kzg_srs_g2 *hs, 
                          const void *t, const void *d_point, const void *pi, int pfmt, int *ok);
 
 /* ---- Fr polynomial helpers on the path (device) ---------------------------------------------- */
-/* Polynomial::eval (src/polynomial.rs:156-165) at one point. */
+/* Polynomial::eval (src/polynomial.rs:156-165) at one point.  x is a host scalar in sfmt; y_out: one scalar in sfmt, always host memory. */
 int kzg_poly_eval(kzg_ctx *ctx, const void *coeffs, size_t n, const void *x, int sfmt, int flags, void *y_out);
 /* Polynomial::multi_eval (src/polynomial.rs:229-233) without its xs.len() > degree restriction, for `batch` polynomials at one
  * point set: ys_out[b * k + i] = p_b(xs[i]).  coeffs: batch x n scalars in sfmt, stride n (KZG_IN_DEVICE applies to it);
@@ -962,10 +962,11 @@ int kzg_point_tree_eval(kzg_ctx *ctx, const kzg_point_tree *plan, const void *co
 int kzg_point_tree_combine(kzg_ctx *ctx, const kzg_point_tree *plan, const void *cs, size_t batch, int sfmt, int flags, void *out);
 int kzg_point_tree_interpolate(kzg_ctx *ctx, const kzg_point_tree *plan, const void *ys, size_t batch, int sfmt, int flags, void *out);
 /* quotient of create_witness without the MSM: q = (p - y)/(X - x), n-1 scalars, in place allowed.
- * Returns KZG_ERR_POINT_NOT_ON_POLY if the remainder is non-zero. */
+ * Returns KZG_ERR_POINT_NOT_ON_POLY if the remainder is non-zero.  x, y: host scalars in sfmt (y is compared with p(x) in that form);
+ * q_out is in sfmt, host memory or device memory with KZG_OUT_DEVICE. */
 int kzg_quotient_linear(kzg_ctx *ctx, const void *coeffs, size_t n, const void *x, const void *y, int sfmt,
                         int flags, void *q_out);
-/* div_by_omega_i (src/eval_form.rs:58-84) applied to (evals - evals[i]). */
+/* div_by_omega_i (src/eval_form.rs:58-84) applied to (evals - evals[i]): d scalars in sfmt, host memory or device memory with KZG_OUT_DEVICE. */
 int kzg_quotient_eval(kzg_ctx *ctx, const void *evals, size_t d, size_t i, int sfmt, int flags, void *q_out);
 
 /* Polynomial::fft_mul / best_mul (src/polynomial.rs:167-191): out = a * b, na + nb - 1 coefficients, by three

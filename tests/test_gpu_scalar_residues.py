@@ -31,28 +31,17 @@ from oracle import kzg_model as M
 from tests import open_eval_model as OM
 from tests import residue_lift as RL
 from tests.fk20_common import eng  # noqa: F401 -- this module's fixture
+# the base inputs, oracle expectations and fixtures shared with tests/test_gpu_scalar_formats.py
+from tests.scalar_call_cases import (AFF, CAN, D, M_INDICES, M_ON, NC, NM, R, TAU, Z_OFF, g1, le, ok, omega, quotient_on_domain,  # noqa: F401
+                                     witness_at, evals, group, kit, poly)
+from tests.scalar_call_cases import coset_scale as _coset_scale, group_call as _group_call, vec_pair as _vec_pair
+from tests.scalar_call_cases import FK_LOG_L, FK_LOG_N, fk20_cosets_expect as _fk20_cosets_expect, fk20_points_expect as _fk20_points_expect
 
 pytestmark = pytest.mark.gpu
 
-R = M.R
-CAN = L.FR_CANONICAL
-AFF = L.G1_AFFINE_MONT
 MODES = RL.MODES
-TAU = 0x0123456789ABCDEF0FEDCBA987654321
 SENTINEL = b"\xa5"
 BAD_SCALARS = (R, (1 << 256) - 1)
-
-
-def le(v):
-    return int(v).to_bytes(32, "little")
-
-
-def g1(k):
-    return C.g1_mul(C.g1_generator(), k % R)
-
-
-def omega(d):
-    return M.compute_omega(d)[2]
 
 
 class Buf:
@@ -74,10 +63,6 @@ class Buf:
             self.d.free()
 
 
-def ok(e, rc):
-    assert rc == 0, (rc, e.last_error())
-
-
 def check_lifts(what, V, E, call, devs=(False, True), modes=MODES):
     """call(blob, dev) == E for the canonical V and for every lift of it, host- and device-resident; all the lifted cases run
     before the verdict so that one failure names every mode and placement that fails"""
@@ -93,38 +78,7 @@ def check_lifts(what, V, E, call, devs=(False, True), modes=MODES):
     assert not failed, "%s: inputs >= r give other bytes than their residues: %s" % (what, ", ".join(failed))
 
 
-@pytest.fixture(scope="module")
-def kit(eng):
-    """the SRSs the module shares, built on first use: kit("gs", n) = setup(TAU, n).gs, kit("lag", d) = the Lagrange SRS, kit("hs", n)"""
-    cache = {}
-
-    def get(kind, n):
-        if (kind, n) not in cache:
-            if kind == "gs":
-                cache[kind, n] = kzg_amd.setup(eng, TAU, n, g2_len=0).gs
-            elif kind == "lag":
-                cache[kind, n] = kzg_amd.setup_lagrange(eng, TAU, n)
-            else:
-                cache[kind, n] = kzg_amd.setup_g2(eng, TAU, n)
-        return cache[kind, n]
-    yield get
-    for s in cache.values():
-        s.free()
-
-
 # ---- element-wise vector operations -----------------------------------------------------------------------------------------------
-def _vec_pair(rng, n):
-    """a, b with a mod r below, above and equal to b mod r at lifted and at untouched positions alike"""
-    a = RL.base(rng, n)
-    b = RL.base(rng, n)
-    for i in range(n):
-        if i % 3 == 0:
-            b[i] = a[i]                     # equal residues: the difference is 0, never the word r
-        elif i % 3 == 1 and a[i] > b[i]:
-            a[i], b[i] = b[i], a[i]         # a < b: the subtraction borrows
-    return a, b
-
-
 @pytest.mark.parametrize("op", ["sub", "mul"])
 def test_fr_vec_sub_and_mul(eng, op):
     """kzg_fr_vec_sub / kzg_fr_vec_mul at n = 777 (four blocks, the last one ragged): every pairing of a canonical, fully lifted,
@@ -168,30 +122,6 @@ def test_divide_by_z_on_coset(eng):
 
 
 # ---- evaluation form on the domain: k_eval_quotient -------------------------------------------------------------------------------
-D = 1024
-# 0 and 7 are lifted by every mode / by "sparse"; 1 by "all" and "edges" only; D - 1 by "all" only: evals[m] itself is >= r or not
-M_INDICES = (0, 1, 7, D - 1)
-
-
-@pytest.fixture(scope="module")
-def evals():
-    """V (D values), its coefficients, p(TAU): computed once"""
-    V = RL.base(random.Random(3), D)
-    coeffs = C.fft(V, inverse=True)
-    assert C.fft(coeffs) == V
-    return V, coeffs, C.poly_eval(coeffs, TAU)
-
-
-def quotient_on_domain(V, m):
-    """the oracle's div_by_omega_i, which takes the numerator evals - evals[m]"""
-    return C.div_by_omega_i_bytes(RL.pack([(v - V[m]) % R for v in V]), len(V), m)
-
-
-def witness_at(evals, z, y):
-    """the known-tau identity of the eval-form tests: [(p(tau) - y) / (tau - z)]G"""
-    return g1((evals[2] - y) * pow(TAU - z, -1, R))
-
-
 @pytest.mark.parametrize("m", M_INDICES)
 def test_quotient_eval(eng, evals, m):
     V = evals[0]
@@ -238,10 +168,6 @@ def test_witness_eval_many(eng, kit, evals):
 
 
 # ---- evaluation form at any point: one z off the domain and one z = w^m in the same batch -----------------------------------------
-Z_OFF = 0x1F2E3D4C5B6A79881726354453627180AABBCCDDEEFF00112233445566778899 % R
-M_ON = 7                                   # evals[7] is lifted by "sparse" and "all"
-
-
 def test_eval_form_eval(eng, evals):
     V, coeffs, _ = evals
     zs = [Z_OFF, pow(omega(D), M_ON, R)]
@@ -357,14 +283,6 @@ def test_ntt_fr_three_passes_2_23(eng):
     buf.free()
 
 
-def _coset_scale(vals, g):
-    out, pw = [], 1
-    for v in vals:
-        out.append(v * pw % R)
-        pw = pw * g % R
-    return out
-
-
 @pytest.mark.parametrize("log_n", [10, 13])
 def test_coset_ntt_fr(eng, log_n):
     n = 1 << log_n
@@ -385,18 +303,6 @@ def test_coset_ntt_fr(eng, log_n):
 
 
 # ---- coefficient form: the Horner scan (one coefficient past a block of 2048) -----------------------------------------------------
-NC = 2049
-
-
-@pytest.fixture(scope="module")
-def poly():
-    """V (NC coefficients), an opening point, p(x), p(TAU)"""
-    rng = random.Random(5)
-    V = RL.base(rng, NC)
-    x = rng.randrange(R)
-    return V, x, C.poly_eval(V, x), C.poly_eval(V, TAU)
-
-
 def test_poly_eval(eng, poly):
     V, x, y, _ = poly
 
@@ -494,9 +400,6 @@ def test_poly_mul(eng, na, nb):
 
 
 # ---- commitments and MSMs at 2^12 -------------------------------------------------------------------------------------------------
-NM = 1 << 12
-
-
 @pytest.fixture(scope="module")
 def scalars():
     """V (NM values) and [sum V_i TAU^i]G, the commitment of V as coefficients"""
@@ -597,28 +500,6 @@ def test_msm_g2(eng, kit):
 
 
 # ---- FK20: every opening over the domain, points and cosets (the smallest plans of their own files) ---------------------------------
-FK_LOG_N, FK_LOG_L = 4, 2
-
-
-def _fk20_points_expect(coeffs, log_n):
-    """witness m = [(p(tau) - p(w^m)) / (tau - w^m)]G"""
-    N, w, ptau = 1 << log_n, omega(1 << log_n), C.poly_eval(coeffs, TAU)
-    return b"".join(g1((ptau - C.poly_eval(coeffs, pow(w, m, R))) * pow(TAU - pow(w, m, R), -1, R)) for m in range(N))
-
-
-def _fk20_cosets_expect(coeffs, log_n, log_l):
-    """coset i: r = p mod (X^l - w^(il)) (its l coefficients), witness = [(p(tau) - r(tau)) / (tau^l - w^(il))]G"""
-    N, l = 1 << log_n, 1 << log_l
-    w, ptau = omega(N), C.poly_eval(coeffs, TAU)
-    ws, rs = [], []
-    for i in range(N // l):
-        c = pow(w, i * l, R)
-        r = [sum(coeffs[j + k * l] * pow(c, k, R) for k in range((len(coeffs) - j + l - 1) // l)) % R for j in range(l)]
-        ws.append(g1((ptau - C.poly_eval(r, TAU)) * pow(pow(TAU, l, R) - c, -1, R)))
-        rs += r
-    return b"".join(ws), RL.pack(rs)
-
-
 @pytest.mark.parametrize("form", ["coeff", "eval"])
 def test_witness_all(eng, kit, form):
     N = 1 << FK_LOG_N
@@ -820,24 +701,6 @@ def test_verify_eval_all(eng, kit, vparams):
 
 
 # ---- the device group (one GPU, no collective needed): n = d = 1024 -------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def group():
-    g = kzg_amd.DeviceGroup([0])
-    yield g
-    g.close()
-
-
-def _group_call(group, fn, blob, dev):
-    """fn(argument) with the polynomial as a host blob, or resident on the group's one GPU"""
-    if not dev:
-        return fn(blob)
-    buf = group.engine(0).alloc_scalars(len(blob) // 32).upload(blob)
-    try:
-        return fn([buf])
-    finally:
-        buf.free()
-
-
 def test_sharded_commit_and_witness_coeff(group):
     n, rng = 1024, random.Random(30)
     V = RL.base(rng, n)
