@@ -13,7 +13,8 @@
  *   - a kzg_ctx is bound to one GPU and is thread-safe.  The reference's blocking calls -- kzg_commit_coeff,
  *     kzg_commit_eval, kzg_msm_g1, kzg_witness_coeff, kzg_witness_coeff_batched, kzg_witness_eval, kzg_verify_poly_coeff /
  *     _eval, kzg_ntt_fr, kzg_coset_ntt_fr, kzg_poly_mul, kzg_poly_divide, kzg_poly_eval, kzg_poly_multi_eval, kzg_interpolate, kzg_quotient_linear / _eval,
- *     kzg_point_tree_product, kzg_point_tree_eval, kzg_point_tree_combine, kzg_point_tree_interpolate, kzg_fr_vec_mul / _sub, kzg_divide_by_z_on_coset, kzg_fr_scan, kzg_fr_grand_product, kzg_fr_batch_inverse (KZGProver / KZGProverEvalForm / KZGVerifier are Clone + &self, src/coeff_form.rs:37-124; an
+ *     kzg_point_tree_product, kzg_point_tree_eval, kzg_point_tree_combine, kzg_point_tree_interpolate, kzg_fr_vec_mul / _sub, kzg_divide_by_z_on_coset, kzg_fr_scan, kzg_fr_grand_product, kzg_fr_batch_inverse,
+ *     kzg_lookup_setup, kzg_lookup_count, kzg_logup_terms (KZGProver / KZGProverEvalForm / KZGVerifier are Clone + &self, src/coeff_form.rs:37-124; an
  *     EvaluationDomain is the caller's own) -- run CONCURRENTLY on one ctx: each call leases one of the context's lanes
  *     (option "streams", default and maximum 16), submits its kernels there and waits for its own result only, so N host
  *     threads calling commit() / create_witness_batched() against one resident SRS fill the GPU like kzg_msm_g1_batch does.
@@ -95,6 +96,15 @@ extern "C" {
  *                                                                             tile of a chunk (<= 16 MiB at the default tile) beside one staged piece of
  *                                                                             host data (<= 64 MiB, or one vector -- with its 2 t columns) and does not
  *                                                                             grow with batch; the inversion: <= 64 MiB of scratch when in == out
+ *   kzg_lookup_setup                        1 <= n_t <= 2^26 table rows      (the plan holds 32 B per key plus the slot array, 8 B x next_pow2(n_t) x 2
+ *                                                                             by default -- option "lookup_spare_log" --: 48 to 64 B per row, 4.3 GB at 2^26)
+ *   kzg_lookup_count                        n <= 2^28; any batch: vectors go in chunks of min(65535, max(1, 2^24 / n_t)) (option "lookup_chunk");
+ *                                                                             the workspace is one uint32_t counter per table row and vector of a
+ *                                                                             chunk (<= 64 MiB, or one vector's) and 16 B per vector of a chunk, beside
+ *                                                                             one staged piece of host data (<= 64 MiB) each way; it does not grow with batch
+ *   kzg_logup_terms                         n <= 2^28; any t and batch: chunks of at most 2^21 denominators (whole vectors, or a run of one vector's
+ *                                                                             elements with its t + 1 columns), 64 B of workspace per denominator
+ *                                                                             (128 MiB) beside one staged piece of host data; it does not grow with batch
  *   kzg_point_tree_setup                    1 <= k <= 2^22 points             (the plan holds 32 x (3 log2 K + 1) bytes per point of the padded
  *                                                                             size K: 9.0 GB at 2^22); kzg_point_tree_eval: n <= 2^28; any batch:
  *                                                                             chunks of max(1, 2^21 / K) blocks, the workspace does not grow with it
@@ -218,6 +228,12 @@ int kzg_sync(kzg_ctx *ctx);
  *  1..256 threads of eight; read per call; the same bytes, for tests that reach tile and carry boundaries at n in the hundreds), "fr_scan_stage"
  *  (0 = default, 64 MiB; a multiple of 32 up to 64 MiB: the bytes of one staged piece of host data in those calls and kzg_fr_batch_inverse) and
  *  "fr_scan_chunk" (0 = the rule alone; 1..65535: at most that many vectors per chunk of launches); the same bytes, for tests,
+ * "lookup_spare_log" (0 = default, 2; 1..4: kzg_lookup_setup gives the plan next_pow2(n_t) << (v - 1) slots -- load <= 0.5 by default; with 1 a
+ *  power-of-two table of distinct keys fills every slot), "lookup_hash_bits" (0 = all; 1..32: only the low v - 1 bits of a key's hash and tag
+ *  are kept -- with 1 every key starts at slot 0 and the table is one probe chain that wraps, every compare a full-key compare); both are read
+ *  at setup and kept by the plan; "lookup_stage" (0 = default, 64 MiB; a multiple of 32 up to 64 MiB: the bytes of one staged piece of host
+ *  data in kzg_lookup_setup / kzg_lookup_count / kzg_logup_terms, and 1 / 32 of it the denominators of one chunk of kzg_logup_terms) and
+ *  "lookup_chunk" (0 = the rule alone; 1..65535: at most that many vectors per chunk), read per call; the same bytes, for tests,
  * "point_tree_leaf" (0 = default, 16; a power of two in 1..16: kzg_point_tree_setup multiplies nodes of up to that many points by its schoolbook
  *  kernels and the levels above through transforms; read at setup and kept by the plan; the same bytes, for tests that reach many levels at tiny k),
  * "g2_msm_slice" (0 = default, 2048; a power of two in 1..2048: the points one workgroup of kzg_msm_g2_bucket sorts by digit) and
@@ -599,6 +615,57 @@ int kzg_fr_scan(kzg_ctx *ctx, const void *in, size_t n, size_t batch, int op, in
  * is the model).  A zero in num is legal: z is zero from there on.  No element is inverted: one field inversion per vector. */
 int kzg_fr_grand_product(kzg_ctx *ctx, const void *num, const void *den, size_t n, size_t t, size_t batch, int sfmt, int flags,
                          void *z_out, void *totals, int *zero_den);
+/* ---- lookup arguments: multiplicities and the logUp column (not a reference method) -------------------------------------------------
+ * The column that the running sum of a logUp-style lookup argument runs over, without leaving the device: the multiplicity of every
+ * table row among the witness values, m_i = #{ j : w_j = t_i } -- a join of two vectors of field elements -- and the terms
+ * sum_j 1 / (beta + w_j[i]) - m_i / (beta + t_i).  kzg_fr_scan(..., KZG_SCAN_SUM, exclusive = 1, ...) over the terms is then the logUp
+ * accumulator, and its total is 0 for a valid lookup.  Tables of several columns are the caller's business: compress the rows (and the
+ * witness tuples) into one column with kzg_fr_lincomb first.
+ *
+ * A kzg_lookup is a table of n_t scalars prepared for membership queries: the keys stored once, reduced, and an open-addressing hash
+ * table of 64-bit slots (hash tag, table index) over them in HBM.  It is immutable after setup and may be queried by any number of
+ * threads.  Keys are residues modulo r: in KZG_FR_CANONICAL_LE_32 any 256-bit word counts as its residue, in KZG_FR_MONT_LE_32 inputs
+ * are below r; a plan set up in one format answers queries in the other.  The table may hold duplicates (a table padded to its domain
+ * by repeating its last row): `distinct` is the number of different residues, and a residue's OWNER is the lowest index that holds it.
+ *
+ * kzg_lookup_setup: table = n_t scalars in sfmt, host memory or device memory with KZG_IN_DEVICE; 1 <= n_t <= 2^26.
+ * kzg_lookup_shape: n_t, distinct and the bytes the plan holds in HBM (each optional).
+ * kzg_lookup_count: `batch` vectors of n scalars, vector b at values + b n (n <= 2^28).  For vector b
+ *   index_out[b n + j]   = the owner of values[b][j], or 0xFFFFFFFF if the value is not in the table;
+ *   mult_out[b n_t + i]  = the number of j whose owner is i, as a field element in sfmt (0 at rows that own nothing);
+ *   missing[b]           = the number of values that are not in the table;
+ *   first_missing[b]     = the lowest such j, or SIZE_MAX if there is none.
+ * Every output is a function of the inputs alone: two calls give the same bytes.  Each of the four is optional, not all NULL.
+ * KZG_IN_DEVICE covers table / values, KZG_OUT_DEVICE covers mult_out / index_out; missing / first_missing are ALWAYS host memory.
+ * With missing or first_missing given, values outside the table are reported there and the call returns KZG_OK; with both NULL the call
+ * returns KZG_ERR_SHAPE when any value is missing (the zero_den == NULL rule of kzg_fr_grand_product) -- the other outputs are still
+ * written in full.
+ * KZG_ERR_SHAPE, before any memory is touched: a NULL ctx or plan, an unknown sfmt, n_t == 0, n == 0 with batch > 0, n_t > 2^26,
+ * n > 2^28, batch x n x 32 or batch x n_t x 32 beyond size_t, a NULL table / out / values, every output NULL, a plan of another GPU.
+ * batch == 0: KZG_OK, nothing touched.  KZG_ERR_INTERNAL: the build found no free slot (every probe loop is bounded by the slot count).
+ * Setup and count are blocking calls that lease one lane (they run concurrently with the calls listed at the top).  Host data is staged
+ * in pieces of at most 64 MiB (option "lookup_stage"), and the vectors are worked off in chunks of min(65535, max(1, 2^24 / n_t)) (option
+ * "lookup_chunk"): the workspace does not grow with batch (Limits).  Options "lookup_spare_log" and "lookup_hash_bits" shape the slot
+ * array at setup, for tests; the bytes are the same under every setting. */
+typedef struct kzg_lookup kzg_lookup;
+int kzg_lookup_setup(kzg_ctx *ctx, const void *table, size_t n_t, int sfmt, int flags, kzg_lookup **out);
+void kzg_lookup_free(kzg_ctx *ctx, kzg_lookup *plan);
+int kzg_lookup_shape(const kzg_lookup *plan, size_t *n_t, size_t *distinct, size_t *bytes);
+int kzg_lookup_count(kzg_ctx *ctx, const kzg_lookup *plan, const void *values, size_t n, size_t batch, int sfmt, int flags,
+                     void *mult_out, uint32_t *index_out, size_t *missing, size_t *first_missing);
+/* values: batch x t x n scalars, column j of vector b at element (b*t + j)*n (the layout of kzg_fr_fold); table: n scalars shared by all
+ * vectors; mult: batch x n scalars; beta: one host scalar in sfmt, below r.
+ *   out[b*n + i] = sum_{j < t} 1 / (beta + values[b][j][i]) - mult[b][i] / (beta + table[i])
+ * table and mult may both be NULL (only the sum), t may be 0 when they are given (only the second term); both absent, or one of the
+ * two without the other, is KZG_ERR_SHAPE.  KZG_IN_DEVICE covers values / table / mult, KZG_OUT_DEVICE covers out, which overlaps no
+ * input; formats and residues as for kzg_fr_grand_product.  A vector with a zero denominator (beta = -x somewhere in its columns or
+ * in the table) has its row of out written as all zero; with zero_den given (batch ints, host) zero_den[b] = 1 for those vectors and
+ * 0 for the others and the call returns KZG_OK; with zero_den == NULL the call returns KZG_ERR_SHAPE if any vector has one.  No element is
+ * inverted on its own (Montgomery's trick, 16 denominators per inversion).  n <= 2^28, any t and batch; KZG_ERR_SHAPE, before any memory
+ * is touched, as for kzg_fr_grand_product (n == 0, an unknown sfmt, beta not below r, sizes beyond size_t); batch == 0: KZG_OK.  Leases
+ * one lane; works in chunks of at most 2^21 denominators (Limits). */
+int kzg_logup_terms(kzg_ctx *ctx, const void *values, const void *table, const void *mult, const void *beta, size_t n, size_t t, size_t batch,
+                    int sfmt, int flags, void *out, int *zero_den);
 /* Evaluation form: evals holds n_polys vectors of d values (stride d), d a power of two == kzg_srs_len(lagrange).  First phase:
  * ys_out[k] = p_{m(k)}(z_k) (host, count scalars: the values of kzg_eval_form_eval), g_out = the d values of g on the domain, D at out_d
  * in ofmt (each of the three optional, not all NULL).  evals and g / g_out are host memory, or device memory with KZG_IN_DEVICE; g has the

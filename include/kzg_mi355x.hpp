@@ -509,6 +509,75 @@ inline std::vector<Scalar> grand_product(const Engine &e, const std::vector<Scal
     return z;
 }
 
+// A table of scalars prepared for membership queries (kzg_lookup): built once, kept by the caller, queried by any number of threads.  The
+// table may hold duplicates; a value's owner is the lowest row that holds it.  The engine must outlive the table.  Not a reference type.
+class LookupTable {
+  public:
+    LookupTable(const Engine &e, const std::vector<Scalar> &table) : e_(&e) {
+        static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+        Scalar none;
+        e.check(kzg_lookup_setup(e.ctx(), table.empty() ? &none : table.data(), table.size(), KZG_FR_CANONICAL_LE_32, 0, &h_));
+    }
+    ~LookupTable() {
+        if (h_) kzg_lookup_free(e_->ctx(), h_);
+    }
+    LookupTable(const LookupTable &) = delete;
+    LookupTable &operator=(const LookupTable &) = delete;
+    LookupTable(LookupTable &&o) noexcept : e_(o.e_), h_(o.h_) { o.h_ = nullptr; }
+    const kzg_lookup *handle() const { return h_; }
+    const Engine &engine() const { return *e_; }
+    size_t len() const { return shape(0); }
+    size_t distinct() const { return shape(1); }
+    size_t bytes() const { return shape(2); }
+
+  private:
+    size_t shape(int which) const {
+        size_t v[3] = {0, 0, 0};
+        kzg_lookup_shape(h_, &v[0], &v[1], &v[2]);
+        return v[which];
+    }
+    const Engine *e_;
+    kzg_lookup *h_ = nullptr;
+};
+
+// kzg_lookup_count: values is values.size() / n vectors of n scalars back to back.  Returns the multiplicities, plan.len() per vector (the
+// number of values each row owns).  indices (optional): every value's owner row, 0xFFFFFFFF for a value that is not in the table.  missing,
+// first_missing (optional): per vector how many values are not in the table and the position of the first (SIZE_MAX if none); without
+// either a missing value throws ReferencePanic.  Not a reference method.
+inline std::vector<Scalar> lookup_count(const LookupTable &plan, const std::vector<Scalar> &values, size_t n, std::vector<uint32_t> *indices = nullptr,
+                                        std::vector<size_t> *missing = nullptr, std::vector<size_t> *first_missing = nullptr) {
+    if (n == 0 || values.size() % n != 0) throw ReferencePanic("lookup_count: shape");
+    const size_t batch = values.size() / n;
+    std::vector<Scalar> mult(batch * plan.len());
+    if (indices) indices->resize(values.size());
+    if (missing) missing->resize(batch);
+    if (first_missing) first_missing->resize(batch);
+    const Engine &e = plan.engine();
+    e.check(kzg_lookup_count(e.ctx(), plan.handle(), values.data(), n, batch, KZG_FR_CANONICAL_LE_32, 0, mult.data(), indices ? indices->data() : nullptr,
+                             missing ? missing->data() : nullptr, first_missing ? first_missing->data() : nullptr));
+    return mult;
+}
+
+// kzg_logup_terms: out[b n + i] = sum_{j < t} 1 / (beta + values[b][j][i]) - mult[b][i] / (beta + table[i]) for vectors of t columns of n
+// scalars (column j of vector b at element (b t + j) n); table (n scalars) and mult (batch x n) may both be empty: only the sum; t may be 0
+// when they are given.  zero_den (optional): the vectors with a zero denominator are flagged there and have zero rows; without it such a
+// vector throws ReferencePanic.  fr_scan(e, out, n, KZG_SCAN_SUM, true) is then the logUp accumulator.  Not a reference method.
+inline std::vector<Scalar> logup_terms(const Engine &e, const std::vector<Scalar> &values, const std::vector<Scalar> &table, const std::vector<Scalar> &mult,
+                                       const Scalar &beta, size_t n, size_t t, std::vector<int> *zero_den = nullptr) {
+    static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+    const bool side = !table.empty() || !mult.empty();
+    if (n == 0 || (t == 0 && !side) || (side && (table.size() != n || mult.size() % n != 0)) || values.size() % n != 0 || (t && (values.size() / n) % t != 0) ||
+        (!t && !values.empty()))
+        throw ReferencePanic("logup_terms: shape");
+    const size_t batch = t ? values.size() / n / t : mult.size() / n;
+    if (side && mult.size() != batch * n) throw ReferencePanic("logup_terms: one multiplicity per vector and row");
+    std::vector<Scalar> out(batch * n);
+    if (zero_den) zero_den->resize(batch);
+    e.check(kzg_logup_terms(e.ctx(), t ? values.data() : nullptr, side ? table.data() : nullptr, side ? mult.data() : nullptr, beta.le.data(), n, t, batch,
+                            KZG_FR_CANONICAL_LE_32, 0, out.data(), zero_den ? zero_den->data() : nullptr));
+    return out;
+}
+
 struct KZGBatchWitness {  // src/coeff_form.rs:12-35
     Polynomial r;
     G1Affine w;

@@ -8,7 +8,7 @@ from ._lib import (FR_CANONICAL, FR_MONT, G1_AFFINE_MONT, G1_JACOBIAN_MONT, G1_Z
                    G1_ZCASH_UNCOMPRESSED, G2_AFFINE_MONT, G2_COMPRESSED, G2_JACOBIAN_MONT, G2_UNCOMPRESSED, IN_DEVICE,
                    OUT_DEVICE, SO_PATH, load)
 from .api import (CosetVerifier, DeviceBuffer, DeviceGroup, Engine, EngineError, EvaluationDomain, FK20CosetPlan, FK20Plan, KZGBatchWitness, KZGError, KZGParams,
-                  KZGProver, KZGProverEvalForm, KZGVerifier, KZGVerifierEvalForm, PointNotOnPolynomial, PointTree, Polynomial,
+                  KZGProver, KZGProverEvalForm, KZGVerifier, KZGVerifierEvalForm, LookupTable, PointNotOnPolynomial, PointTree, Polynomial,
                   PolynomialDegreeTooLarge, ReferencePanic, ShardedSrs, Srs, SrsG2, compute_lagrange_basis, compute_lagrange_basis_g2, compute_omega,
                   pack_scalars, setup, setup_g2, setup_lagrange, setup_lagrange_g2, setup_shard, splitmix_scalar,
                   unpack_scalars)

@@ -166,6 +166,11 @@ def load(path=None):
         "kzg_fr_batch_inverse": (i32, [vp, vp, sz, i32, i32, vp, ctypes.POINTER(sz)]),
         "kzg_fr_scan": (i32, [vp, vp, sz, sz, i32, i32, i32, i32, vp, vp]),
         "kzg_fr_grand_product": (i32, [vp, vp, vp, sz, sz, sz, i32, i32, vp, vp, ctypes.POINTER(i32)]),
+        "kzg_lookup_setup": (i32, [vp, vp, sz, i32, i32, c_void_pp]),
+        "kzg_lookup_free": (None, [vp, vp]),
+        "kzg_lookup_shape": (i32, [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz)]),
+        "kzg_lookup_count": (i32, [vp, vp, vp, sz, sz, i32, i32, vp, ctypes.POINTER(u32), ctypes.POINTER(sz), ctypes.POINTER(sz)]),
+        "kzg_logup_terms": (i32, [vp, vp, vp, vp, vp, sz, sz, sz, i32, i32, vp, ctypes.POINTER(i32)]),
         "kzg_multiopen_eval_commit": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, i32, i32, vp, vp, vp, i32]),
         "kzg_multiopen_eval_finish": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, vp, vp, i32, i32, vp, vp, i32]),
         "kzg_multiopen_coeff_commit": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, i32, i32, vp, vp, vp, i32]),

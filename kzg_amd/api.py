@@ -623,6 +623,64 @@ class Engine:
         z = out if out is not None else [self._scalar_from(buf.raw[32 * k:32 * k + 32], sfmt) for k in range(batch * n)]
         return z, [self._scalar_from(tb.raw[32 * b:32 * b + 32], sfmt) for b in range(batch)], [0] * batch if zd is None else [int(v) for v in zd[:batch]]
 
+    def lookup_table(self, table):
+        """kzg_lookup_setup: a LookupTable over `table` (a list of ints, a canonical blob or a DeviceBuffer)."""
+        return LookupTable(self, table)
+
+    def logup_terms(self, values, n, t, beta, table=None, mult=None, out=None, strict=True):
+        """kzg_logup_terms: out[b n + i] = sum_{j < t} 1 / (beta + values[b][j][i]) - mult[b][i] / (beta + table[i]) for the
+        len(values) / (t n) vectors of t columns of n scalars (column j of vector b at element (b t + j) n; with t = 0 the batch is
+        len(mult) / n).  values, table, mult: flat lists of ints, canonical blobs or DeviceBuffers, all of one kind; table and mult
+        may both be None.  Returns (terms, zero_den): the terms as ints, or `out` (a DeviceBuffer of the inputs' scalar format) when
+        one is given.  strict: a zero denominator raises; otherwise the vectors that hold one are flagged and their rows are zero."""
+        if (table is None) != (mult is None):
+            raise ReferencePanic("logup_terms: table and mult go together")
+        if n <= 0 or t < 0 or (t == 0 and table is None):
+            raise ReferencePanic("logup_terms: n >= 1, and columns or a table")
+        args = [self._scalars_arg(x) if x is not None else None for x in ((values if t else None), table, mult)]
+        kinds = {(a[2], a[3]) for a in args if a is not None}
+        if len(kinds) != 1:
+            raise ReferencePanic("logup_terms: values, table and mult have one format and residence")
+        (sfmt, flags), = kinds
+        have = args[0][1] if t else args[2][1]
+        per = t * n if t else n
+        if have % per or (table is not None and (args[1][1] != n or args[2][1] * per != have * n)):
+            raise ReferencePanic("logup_terms: the sizes are no whole number of vectors of t = %d columns of n = %d" % (t, n))
+        batch = have // per
+        zd = None if strict else (ctypes.c_int * max(batch, 1))()
+        if out is not None:
+            if out.n < batch * n or out.sfmt != sfmt:
+                raise ReferencePanic("logup_terms: out holds %d scalars, batch * n = %d (and has the inputs' format)" % (out.n, batch * n))
+            buf, oflags = out.ptr, flags | L.OUT_DEVICE
+        else:
+            buf, oflags = ctypes.create_string_buffer(32 * max(batch * n, 1)), flags
+        ptrs = [a[0] if a is not None else None for a in args]
+        rc = self.lib.kzg_logup_terms(self.ctx, ptrs[0], ptrs[1], ptrs[2], self._enc_scalar(beta, sfmt), n, t, batch, sfmt, oflags, buf, zd)
+        if rc:
+            _raise(self, rc)
+        terms = out if out is not None else [self._scalar_from(buf.raw[32 * k:32 * k + 32], sfmt) for k in range(batch * n)]
+        return terms, [0] * batch if zd is None else [int(v) for v in zd[:batch]]
+
+    def logup_accumulator(self, plan, table, columns, beta):
+        """The logUp argument of `columns` (t lists of n ints each) against `table` (n ints, the rows `plan` was set up from), without
+        the data leaving the device between the three calls: the multiplicities m of the table rows among all t n values
+        (kzg_lookup_count; every value must be in the table), the terms sum_j 1 / (beta + columns[j][i]) - m_i / (beta + table[i])
+        (kzg_logup_terms) and their exclusive running sum (kzg_fr_scan).  Returns (m, accumulator, total) as ints; total is 0."""
+        n, t = len(table), len(columns)
+        if t == 0 or any(len(c) != n for c in columns) or len(plan) != n:
+            raise ReferencePanic("logup_accumulator: t >= 1 columns of len(table) values, and a plan over the table")
+        bufs = [DeviceBuffer(self, n).upload(pack_scalars(table)), DeviceBuffer(self, t * n).upload(pack_scalars([x for c in columns for x in c])),
+                DeviceBuffer(self, n), DeviceBuffer(self, n)]
+        try:
+            d_table, d_cols, d_m, d_acc = bufs
+            plan.count(d_cols, out=d_m, strict=True)
+            self.logup_terms(d_cols, n, t, beta, table=d_table, mult=d_m, out=d_acc)
+            _, totals = self.fr_scan(d_acc, n, "sum", True, out=d_acc)
+            return unpack_scalars(d_m.download()), unpack_scalars(d_acc.download()), totals[0]
+        finally:
+            for b in bufs:
+                b.free()
+
     def _multiopen_vectors_arg(self, vecs, length, pad):
         """(pointer, length, n_polys, sfmt, flags, keep-alive) of the polynomials of a multiopen call: a list of vectors (lists of ints,
         EvaluationDomains or Polynomials; with `pad` filled with zeros to the longest) or a flat blob / DeviceBuffer (length given)"""
@@ -965,6 +1023,73 @@ class PointTree:
 
     def __exit__(self, *exc):
         self.close()
+        return False
+
+
+class LookupTable:
+    """A table of scalars prepared for membership queries (kzg_lookup): its keys and an open-addressing hash table over them in HBM,
+    kept between calls.  The table may hold duplicates; a value's owner is the lowest row that holds it."""
+
+    def __init__(self, engine, table):
+        self.engine, self.handle = engine, None
+        ptr, n_t, sfmt, flags, _keep = engine._scalars_arg(table)
+        h = ctypes.c_void_p()
+        rc = engine.lib.kzg_lookup_setup(engine.ctx, ptr, n_t, sfmt, flags, ctypes.byref(h))
+        if rc:
+            _raise(engine, rc)
+        self.handle = h
+
+    def shape(self):
+        """(rows, distinct residues, bytes the plan holds in HBM)."""
+        n_t, distinct, nbytes = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+        rc = self.engine.lib.kzg_lookup_shape(self.handle, ctypes.byref(n_t), ctypes.byref(distinct), ctypes.byref(nbytes))
+        if rc:
+            _raise(self.engine, rc)
+        return n_t.value, distinct.value, nbytes.value
+
+    def __len__(self):
+        return self.shape()[0]
+
+    def count(self, values, n=None, out=None, strict=False):
+        """kzg_lookup_count: `values` (a flat list of ints, a canonical blob or a DeviceBuffer) is len(values) / n vectors of n scalars
+        (one vector by default).  Returns (multiplicities, indices, missing, first_missing): per vector the number of values each
+        row owns -- ints, or `out` (a DeviceBuffer of batch x rows scalars in the values' format) when one is given --, every
+        value's owner row (None for a value that is not in the table; no indices at all with `out`), how many values are not in
+        the table and the position of the first of them (None if there is none).  strict: a missing value raises."""
+        eng = self.engine
+        ptr, have, sfmt, flags, _keep = eng._scalars_arg(values)
+        n = have if n is None else n
+        if n <= 0 or have % n:
+            raise ReferencePanic("lookup count: %d scalars are no whole number of vectors of n = %d" % (have, n))
+        batch, n_t = have // n, len(self)
+        miss, first = (ctypes.c_size_t * batch)(), (ctypes.c_size_t * batch)()
+        report = (None, None) if strict else (miss, first)
+        if out is not None:
+            if out.n < batch * n_t or out.sfmt != sfmt:
+                raise ReferencePanic("lookup count: out holds %d scalars, batch * rows = %d (and has the values' format)" % (out.n, batch * n_t))
+            rc = eng.lib.kzg_lookup_count(eng.ctx, self.handle, ptr, n, batch, sfmt, flags | L.OUT_DEVICE, out.ptr, None, *report)
+            mults, idx = out, None
+        else:
+            mb, ib = ctypes.create_string_buffer(32 * batch * n_t), (ctypes.c_uint32 * have)()
+            rc = eng.lib.kzg_lookup_count(eng.ctx, self.handle, ptr, n, batch, sfmt, flags, mb, ib, *report)
+            mults = [eng._scalar_from(mb.raw[32 * k:32 * k + 32], sfmt) for k in range(batch * n_t)]
+            idx = [None if v == 0xFFFFFFFF else int(v) for v in ib]
+        if rc:
+            _raise(eng, rc)
+        return mults, idx, [int(v) for v in miss], [None if v == (1 << (8 * ctypes.sizeof(ctypes.c_size_t))) - 1 else int(v) for v in first] if not strict else [None] * batch
+
+    def free(self):
+        if self.handle:
+            self.engine.lib.kzg_lookup_free(self.engine.ctx, self.handle)
+            self.handle = None
+
+    close = free
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
         return False
 
 

@@ -152,6 +152,10 @@ struct kzg_ctx {
     int opt_fr_scan_tile = 0;             // kzg_fr_scan / kzg_fr_grand_product: elements one workgroup scans, a power of two in 8..2048 (0 = 2048)
     int opt_fr_scan_stage = 0;            // ... and kzg_fr_batch_inverse: bytes of one staged piece of host data, a multiple of 32 up to 64 MiB (0 = 64 MiB)
     int opt_fr_scan_chunk = 0;            // ... vectors per launch, at most, 1..65535 (0 = the rule min(65535, max(1, 65536 / tiles per vector)) alone)
+    int opt_lookup_spare_log = 0;         // kzg_lookup_setup: 1..4 gives next_pow2(n_t) << (v - 1) slots (0 = 2: load <= 0.5)
+    int opt_lookup_hash_bits = 0;         // ... 1..32 keeps the low v - 1 bits of a key's hash and tag (0 = all); both are kept by the plan
+    int opt_lookup_stage = 0;             // kzg_lookup_* / kzg_logup_terms: bytes of one staged piece of host data, a multiple of 32 up to 64 MiB (0 = 64 MiB)
+    int opt_lookup_chunk = 0;             // ... vectors per chunk, at most, 1..65535 (0 = the rule alone)
     int opt_point_tree_leaf = 0;          // kzg_point_tree_setup: nodes of up to this many points are multiplied by the schoolbook kernels, a power of two <= 16 (0 = 16)
     int opt_g2_msm_slice = 0;             // kzg_msm_g2_bucket: points one workgroup sorts by digit, a power of two <= 2048 (0 = 2048)
     int opt_g2_msm_slots = 0;             // kzg_msm_g2_bucket: slice slots of the bucket arena = slices per chunk, 1..16 (0 = 16)

@@ -461,6 +461,18 @@ extern "C" int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value) 
     } else if (k == "fr_scan_chunk") {
         if (value < 0 || value > 65535) return fail(ctx, KZG_ERR_SHAPE, "fr_scan_chunk must be 0 (the rule alone) or 1..65535 vectors");
         ctx->opt_fr_scan_chunk = (int)value;
+    } else if (k == "lookup_spare_log") {
+        if (value < 0 || value > 4) return fail(ctx, KZG_ERR_SHAPE, "lookup_spare_log must be 0 (2) or 1..4");
+        ctx->opt_lookup_spare_log = (int)value;
+    } else if (k == "lookup_hash_bits") {
+        if (value < 0 || value > 32) return fail(ctx, KZG_ERR_SHAPE, "lookup_hash_bits must be 0 (all) or 1..32");
+        ctx->opt_lookup_hash_bits = (int)value;
+    } else if (k == "lookup_stage") {
+        if (value != 0 && (value < 32 || value > (64 << 20) || (value & 31))) return fail(ctx, KZG_ERR_SHAPE, "lookup_stage must be 0 (64 MiB) or a multiple of 32 bytes up to 64 MiB");
+        ctx->opt_lookup_stage = (int)value;
+    } else if (k == "lookup_chunk") {
+        if (value < 0 || value > 65535) return fail(ctx, KZG_ERR_SHAPE, "lookup_chunk must be 0 (the rule alone) or 1..65535 vectors");
+        ctx->opt_lookup_chunk = (int)value;
     } else if (k == "point_tree_leaf") {
         if (value != 0 && (value < 1 || value > 16 || (value & (value - 1)))) return fail(ctx, KZG_ERR_SHAPE, "point_tree_leaf must be 0 (16) or a power of two in 1..16");
         ctx->opt_point_tree_leaf = (int)value;
