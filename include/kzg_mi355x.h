@@ -14,7 +14,7 @@
  *     kzg_commit_eval, kzg_msm_g1, kzg_witness_coeff, kzg_witness_coeff_batched, kzg_witness_eval, kzg_verify_poly_coeff /
  *     _eval, kzg_ntt_fr, kzg_coset_ntt_fr, kzg_poly_mul, kzg_poly_divide, kzg_poly_eval, kzg_poly_multi_eval, kzg_interpolate, kzg_quotient_linear / _eval,
  *     kzg_point_tree_product, kzg_point_tree_eval, kzg_point_tree_combine, kzg_point_tree_interpolate, kzg_fr_vec_mul / _sub, kzg_divide_by_z_on_coset, kzg_fr_scan, kzg_fr_grand_product, kzg_fr_batch_inverse,
- *     kzg_lookup_setup, kzg_lookup_count, kzg_logup_terms (KZGProver / KZGProverEvalForm / KZGVerifier are Clone + &self, src/coeff_form.rs:37-124; an
+ *     kzg_lookup_setup, kzg_lookup_count, kzg_logup_terms, kzg_fr_program_run (KZGProver / KZGProverEvalForm / KZGVerifier are Clone + &self, src/coeff_form.rs:37-124; an
  *     EvaluationDomain is the caller's own) -- run CONCURRENTLY on one ctx: each call leases one of the context's lanes
  *     (option "streams", default and maximum 16), submits its kernels there and waits for its own result only, so N host
  *     threads calling commit() / create_witness_batched() against one resident SRS fill the GPU like kzg_msm_g1_batch does.
@@ -105,6 +105,12 @@ extern "C" {
  *   kzg_logup_terms                         n <= 2^28; any t and batch: chunks of at most 2^21 denominators (whole vectors, or a run of one vector's
  *                                                                             elements with its t + 1 columns), 64 B of workspace per denominator
  *                                                                             (128 MiB) beside one staged piece of host data; it does not grow with batch
+ *   kzg_fr_program_setup                    1 <= n_insns <= 65,536; n_cols, n_consts <= 4,096; 1 <= n_out <= 64; at most 16 temporaries (the plan
+ *                                                                             holds the validated words on the host: 24 B per instruction)
+ *   kzg_fr_program_run                      n <= 2^28; the workspace holds the program (24 B per instruction), the const table (32 B per const),
+ *                                                                             16 B per column and 8 B per output, every HOST column whole
+ *                                                                             (32 B x col_len, uploaded once each) and, without KZG_OUT_DEVICE,
+ *                                                                             every output whole (32 B x n): KZG_ERR_ALLOC if they do not fit
  *   kzg_point_tree_setup                    1 <= k <= 2^22 points             (the plan holds 32 x (3 log2 K + 1) bytes per point of the padded
  *                                                                             size K: 9.0 GB at 2^22); kzg_point_tree_eval: n <= 2^28; any batch:
  *                                                                             chunks of max(1, 2^21 / K) blocks, the workspace does not grow with it
@@ -234,6 +240,8 @@ int kzg_sync(kzg_ctx *ctx);
  *  at setup and kept by the plan; "lookup_stage" (0 = default, 64 MiB; a multiple of 32 up to 64 MiB: the bytes of one staged piece of host
  *  data in kzg_lookup_setup / kzg_lookup_count / kzg_logup_terms, and 1 / 32 of it the denominators of one chunk of kzg_logup_terms) and
  *  "lookup_chunk" (0 = the rule alone; 1..65535: at most that many vectors per chunk), read per call; the same bytes, for tests,
+ * "fr_program_block" (0 = the rule: 256 threads a workgroup up to 4 temporaries, 128 up to 8, 64 above; 64 / 128 / 256: that many, whatever
+ *  the plan's temporaries take of the LDS; read per call of kzg_fr_program_run; the same bytes, for tests),
  * "point_tree_leaf" (0 = default, 16; a power of two in 1..16: kzg_point_tree_setup multiplies nodes of up to that many points by its schoolbook
  *  kernels and the levels above through transforms; read at setup and kept by the plan; the same bytes, for tests that reach many levels at tiny k),
  * "g2_msm_slice" (0 = default, 2048; a power of two in 1..2048: the points one workgroup of kzg_msm_g2_bucket sorts by digit) and
@@ -666,6 +674,54 @@ int kzg_lookup_count(kzg_ctx *ctx, const kzg_lookup *plan, const void *values, s
  * one lane; works in chunks of at most 2^21 denominators (Limits). */
 int kzg_logup_terms(kzg_ctx *ctx, const void *values, const void *table, const void *mult, const void *beta, size_t n, size_t t, size_t batch,
                     int sfmt, int flags, void *out, int *zero_den);
+/* ---- constraint expressions over columns in one pass (not a reference method) -----------------------------------------------------
+ * The quotient round of a PLONK-family prover evaluates its gate, permutation and lookup constraints row by row on the extended
+ * coset: polynomial expressions in the columns and in rotations of them.  A kzg_fr_program is a small straight-line program over Fr,
+ * validated once and kept; kzg_fr_program_run runs it for every row i < n of a set of columns in ONE pass over HBM: each column
+ * element an instruction names is read once, each output written once, the temporaries never leave the chip.  With it the sequence
+ * coset transforms -> constraints -> 1 / Z_H -> inverse coset transform -> commit stays in device memory.
+ *
+ * An instruction is KZG_FRP_WORDS = 6 uint32_t words:
+ *   word 0      op | dst_kind << 8 | a_kind << 16 | b_kind << 24
+ *   words 1..3  the indices dst, a, b
+ *   words 4, 5  the shifts of a and b, two's-complement int32_t; meaningful for KZG_FRP_COL operands, 0 otherwise
+ * and means, for row i, dst = a (op) b with op one of KZG_FRP_ADD / _SUB / _MUL.  Operands:
+ *   KZG_FRP_COL c, shift s   element (i + s) mod col_len[c] of cols[c]
+ *   KZG_FRP_CONST k          consts[k]: n_consts host scalars below r in sfmt, one set per run (the challenges; a plan is reused
+ *                            across proofs)
+ *   KZG_FRP_TEMP t           a per-row temporary, t < KZG_FRP_MAX_TEMPS = 16; read only after an earlier instruction wrote it
+ * Destinations: KZG_FRP_TEMP t (may equal a source) or KZG_FRP_OUT o, outs[o][i]: write-only, every output written by exactly one
+ * instruction of the program.
+ * Columns: col_len[c] is n (any n) or a power of two that divides n: a short column is periodic (the e values of 1 / Z_H on an e-fold
+ * extended coset are one column of length e).  A rotation by one row of the base domain on an e-fold extended domain is shift = e:
+ * the caller's arithmetic.  Any int32_t is a legal shift; no row performs a division.
+ * Formats are those of kzg_fr_scan: in KZG_FR_CANONICAL_LE_32 any 256-bit column word counts as its residue, in KZG_FR_MONT_LE_32
+ * column words are below r; outputs are in sfmt and below r; a product is the product of the represented values in both formats
+ * (Montgomery form is the fast path: canonical data pays one conversion per column load and one per store).  KZG_IN_DEVICE covers
+ * every cols[c], KZG_OUT_DEVICE every outs[o]; the arrays cols, col_len, outs themselves and consts are ALWAYS host memory.  Host
+ * columns are uploaded whole, once each (Limits).  An output overlaps no column and no other output -- rotations make in-place
+ * evaluation a race --: pointer equality is rejected, any other overlap is the caller's error.
+ * kzg_fr_program_shape: the sizes given at setup, the temporaries in use (highest index + 1) and the number of KZG_FRP_MUL
+ * instructions; every out-pointer is optional.
+ * KZG_ERR_SHAPE, before any memory is touched -- at setup (*out is left as it was): a NULL ctx, words or out; n_insns == 0 or above
+ * 65,536, n_cols or n_consts above 4,096, n_out == 0 or above 64; an unknown op or kind; KZG_FRP_OUT as a source, KZG_FRP_COL / _CONST as
+ * a destination; an index out of range, a temporary index >= 16; a temporary read before any instruction wrote it; a non-zero shift on
+ * an operand that is no column; an output written twice or never.  At run: a NULL plan, a plan of another GPU, n == 0 or n > 2^28, an
+ * unknown sfmt, a col_len that is 0 or neither n nor a power of two dividing n, a const not below r, a NULL cols / col_len (n_cols > 0),
+ * consts (n_consts > 0) or outs, a NULL pointer among the columns or outputs, an output equal to a column or to another output.
+ * The run is a blocking call that leases one lane (it runs concurrently with the calls listed at the top); setup and shape touch no GPU.
+ * A plan is immutable and may be run by any number of threads.  Option "fr_program_block" picks the workgroup size, for tests. */
+typedef struct kzg_fr_program kzg_fr_program;
+enum { KZG_FRP_ADD = 0, KZG_FRP_SUB = 1, KZG_FRP_MUL = 2 };                       /* op */
+enum { KZG_FRP_COL = 0, KZG_FRP_CONST = 1, KZG_FRP_TEMP = 2, KZG_FRP_OUT = 3 };  /* operand / destination kinds */
+enum { KZG_FRP_WORDS = 6, KZG_FRP_MAX_TEMPS = 16 };
+int kzg_fr_program_setup(kzg_ctx *ctx, const uint32_t *words, size_t n_insns, size_t n_cols, size_t n_consts, size_t n_out,
+                         kzg_fr_program **out);
+void kzg_fr_program_free(kzg_ctx *ctx, kzg_fr_program *plan);
+int kzg_fr_program_shape(const kzg_fr_program *plan, size_t *n_insns, size_t *n_cols, size_t *n_consts, size_t *n_out, size_t *n_temps,
+                         size_t *n_mul);
+int kzg_fr_program_run(kzg_ctx *ctx, const kzg_fr_program *plan, const void *const *cols, const size_t *col_len, const void *consts,
+                       size_t n, int sfmt, int flags, void *const *outs);
 /* Evaluation form: evals holds n_polys vectors of d values (stride d), d a power of two == kzg_srs_len(lagrange).  First phase:
  * ys_out[k] = p_{m(k)}(z_k) (host, count scalars: the values of kzg_eval_form_eval), g_out = the d values of g on the domain, D at out_d
  * in ofmt (each of the three optional, not all NULL).  evals and g / g_out are host memory, or device memory with KZG_IN_DEVICE; g has the

@@ -578,6 +578,65 @@ inline std::vector<Scalar> logup_terms(const Engine &e, const std::vector<Scalar
     return out;
 }
 
+// A straight-line program over Fr (kzg_fr_program), validated once and kept: the constraint expressions of a quotient round, run for
+// every row of a set of columns in one pass (fr_program_run).  words: KZG_FRP_WORDS per instruction (instruction() builds them).  The
+// engine must outlive the program.  Not a reference type.
+class FrProgram {
+  public:
+    FrProgram(const Engine &e, const std::vector<uint32_t> &words, size_t n_cols, size_t n_consts, size_t n_out) : e_(&e) {
+        if (words.size() % KZG_FRP_WORDS) throw ReferencePanic("FrProgram: whole instructions of six words");
+        const uint32_t none = 0;
+        e.check(kzg_fr_program_setup(e.ctx(), words.empty() ? &none : words.data(), words.size() / KZG_FRP_WORDS, n_cols, n_consts, n_out, &h_));
+    }
+    ~FrProgram() {
+        if (h_) kzg_fr_program_free(e_->ctx(), h_);
+    }
+    FrProgram(const FrProgram &) = delete;
+    FrProgram &operator=(const FrProgram &) = delete;
+    FrProgram(FrProgram &&o) noexcept : e_(o.e_), h_(o.h_) { o.h_ = nullptr; }
+    static std::array<uint32_t, KZG_FRP_WORDS> instruction(int op, int dst_kind, uint32_t dst, int a_kind, uint32_t a, int b_kind, uint32_t b,
+                                                           int32_t a_shift = 0, int32_t b_shift = 0) {
+        return {(uint32_t)op | (uint32_t)dst_kind << 8 | (uint32_t)a_kind << 16 | (uint32_t)b_kind << 24, dst, a, b, (uint32_t)a_shift, (uint32_t)b_shift};
+    }
+    const kzg_fr_program *handle() const { return h_; }
+    const Engine &engine() const { return *e_; }
+    size_t instructions() const { return shape(0); }
+    size_t columns() const { return shape(1); }
+    size_t consts() const { return shape(2); }
+    size_t outputs() const { return shape(3); }
+    size_t temps() const { return shape(4); }
+    size_t multiplications() const { return shape(5); }
+
+  private:
+    size_t shape(int which) const {
+        size_t v[6] = {0, 0, 0, 0, 0, 0};
+        kzg_fr_program_shape(h_, &v[0], &v[1], &v[2], &v[3], &v[4], &v[5]);
+        return v[which];
+    }
+    const Engine *e_;
+    kzg_fr_program *h_ = nullptr;
+};
+
+// kzg_fr_program_run on host vectors: one vector per column -- n elements, or a power of two that divides n (a periodic column) --,
+// one scalar per const; returns one vector of n scalars per output.  Not a reference method.
+inline std::vector<std::vector<Scalar>> fr_program_run(const FrProgram &plan, const std::vector<std::vector<Scalar>> &cols, const std::vector<Scalar> &consts,
+                                                       size_t n) {
+    static_assert(sizeof(Scalar) == 32, "Scalar is the 32-byte canonical encoding");
+    if (cols.size() != plan.columns() || consts.size() != plan.consts()) throw ReferencePanic("fr_program_run: the plan's columns and consts");
+    std::vector<const void *> cp;
+    std::vector<size_t> cl;
+    for (const std::vector<Scalar> &c : cols) {
+        cp.push_back(c.data());
+        cl.push_back(c.size());
+    }
+    std::vector<std::vector<Scalar>> outs(plan.outputs(), std::vector<Scalar>(n));
+    std::vector<void *> op;
+    for (std::vector<Scalar> &o : outs) op.push_back(o.data());
+    const Engine &e = plan.engine();
+    e.check(kzg_fr_program_run(e.ctx(), plan.handle(), cp.data(), cl.data(), consts.data(), n, KZG_FR_CANONICAL_LE_32, 0, op.data()));
+    return outs;
+}
+
 struct KZGBatchWitness {  // src/coeff_form.rs:12-35
     Polynomial r;
     G1Affine w;

@@ -29,6 +29,10 @@ IN_DEVICE = 1
 OUT_DEVICE = 2
 SCAN_PRODUCT = 0
 SCAN_SUM = 1
+FRP_ADD, FRP_SUB, FRP_MUL = 0, 1, 2                    # kzg_fr_program: op
+FRP_COL, FRP_CONST, FRP_TEMP, FRP_OUT = 0, 1, 2, 3     # ... operand / destination kinds
+FRP_WORDS = 6
+FRP_MAX_TEMPS = 16
 
 _lib = None
 
@@ -171,6 +175,10 @@ def load(path=None):
         "kzg_lookup_shape": (i32, [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz)]),
         "kzg_lookup_count": (i32, [vp, vp, vp, sz, sz, i32, i32, vp, ctypes.POINTER(u32), ctypes.POINTER(sz), ctypes.POINTER(sz)]),
         "kzg_logup_terms": (i32, [vp, vp, vp, vp, vp, sz, sz, sz, i32, i32, vp, ctypes.POINTER(i32)]),
+        "kzg_fr_program_setup": (i32, [vp, ctypes.POINTER(u32), sz, sz, sz, sz, c_void_pp]),
+        "kzg_fr_program_free": (None, [vp, vp]),
+        "kzg_fr_program_shape": (i32, [vp] + [ctypes.POINTER(sz)] * 6),
+        "kzg_fr_program_run": (i32, [vp, vp, c_void_pp, ctypes.POINTER(sz), vp, sz, i32, i32, c_void_pp]),
         "kzg_multiopen_eval_commit": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, i32, i32, vp, vp, vp, i32]),
         "kzg_multiopen_eval_finish": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, vp, vp, i32, i32, vp, vp, i32]),
         "kzg_multiopen_coeff_commit": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, i32, i32, vp, vp, vp, i32]),

@@ -681,6 +681,11 @@ class Engine:
             for b in bufs:
                 b.free()
 
+    def fr_program(self, program, n_cols=None, n_consts=None, n_out=None):
+        """kzg_fr_program_setup: a FrProgram from a kzg_amd.frp.Compiled (frp.compile([...])), or from a flat list of instruction
+        words with the three sizes."""
+        return FrProgram(self, program, n_cols, n_consts, n_out)
+
     def _multiopen_vectors_arg(self, vecs, length, pad):
         """(pointer, length, n_polys, sfmt, flags, keep-alive) of the polynomials of a multiopen call: a list of vectors (lists of ints,
         EvaluationDomains or Polynomials; with `pad` filled with zeros to the longest) or a flat blob / DeviceBuffer (length given)"""
@@ -1081,6 +1086,79 @@ class LookupTable:
     def free(self):
         if self.handle:
             self.engine.lib.kzg_lookup_free(self.engine.ctx, self.handle)
+            self.handle = None
+
+    close = free
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+
+class FrProgram:
+    """A straight-line program over Fr (kzg_fr_program), validated once and run for every row of a set of columns in one pass: the
+    constraint expressions of a quotient round.  The words come from kzg_amd.frp.compile or are written by hand (frp.insn)."""
+
+    def __init__(self, engine, program, n_cols=None, n_consts=None, n_out=None):
+        self.engine, self.handle = engine, None
+        if hasattr(program, "words"):
+            words, n_cols, n_consts, n_out = program.words, program.n_cols, program.n_consts, program.n_out
+        else:
+            words = list(program)
+        if None in (n_cols, n_consts, n_out) or len(words) % L.FRP_WORDS:
+            raise ReferencePanic("fr_program: whole instructions of %d words, and n_cols, n_consts, n_out" % L.FRP_WORDS)
+        arr = (ctypes.c_uint32 * max(len(words), 1))(*[int(w) & 0xFFFFFFFF for w in words])
+        h = ctypes.c_void_p()
+        rc = engine.lib.kzg_fr_program_setup(engine.ctx, arr, len(words) // L.FRP_WORDS, n_cols, n_consts, n_out, ctypes.byref(h))
+        if rc:
+            _raise(engine, rc)
+        self.handle = h
+
+    def shape(self):
+        """(instructions, columns, consts, outputs, temporaries in use, multiplications)"""
+        v = [ctypes.c_size_t() for _ in range(6)]
+        rc = self.engine.lib.kzg_fr_program_shape(self.handle, *[ctypes.byref(x) for x in v])
+        if rc:
+            _raise(self.engine, rc)
+        return tuple(x.value for x in v)
+
+    def run(self, cols, consts=(), n=None, outs=None):
+        """kzg_fr_program_run over rows 0 .. n - 1 (n: the longest column by default).  cols: one entry per column, all lists of ints
+        (or canonical blobs) or all DeviceBuffers of one scalar format; a column holds n elements, or a power of two that divides n
+        (periodic).  consts: ints in [0, R).  Returns one list of n ints per output, or `outs` (one DeviceBuffer of the columns'
+        format per output) when given."""
+        eng = self.engine
+        _, n_cols, n_consts, n_out, _, _ = self.shape()
+        if len(cols) != n_cols or len(consts) != n_consts or (outs is not None and len(outs) != n_out):
+            raise ReferencePanic("fr_program: the plan takes %d columns and %d consts and writes %d outputs" % (n_cols, n_consts, n_out))
+        args = [eng._scalars_arg(c) for c in cols]
+        kinds = {(a[2], a[3]) for a in args}
+        if len(kinds) > 1:
+            raise ReferencePanic("fr_program: the columns have one format and residence")
+        sfmt, flags = kinds.pop() if kinds else ((outs[0].sfmt if outs is not None else L.FR_CANONICAL), 0)
+        if outs is not None and any(o.sfmt != sfmt for o in outs):
+            raise ReferencePanic("fr_program: outs have the columns' format")
+        n = max([a[1] for a in args], default=0) if n is None else n
+        if outs is not None and any(o.n < n for o in outs):
+            raise ReferencePanic("fr_program: an output buffer is shorter than n = %d" % n)
+        cp = (ctypes.c_void_p * max(n_cols, 1))(*[ctypes.cast(a[0], ctypes.c_void_p) for a in args])
+        cl = (ctypes.c_size_t * max(n_cols, 1))(*[a[1] for a in args])
+        kb = b"".join(eng._enc_scalar(k, sfmt) for k in consts) or None
+        bufs = None if outs is not None else [ctypes.create_string_buffer(32 * max(n, 1)) for _ in range(n_out)]
+        op = (ctypes.c_void_p * n_out)(*[ctypes.cast(b, ctypes.c_void_p) for b in (bufs or [o.ptr for o in outs])])
+        rc = eng.lib.kzg_fr_program_run(eng.ctx, self.handle, cp, cl, kb, n, sfmt, flags | (L.OUT_DEVICE if outs is not None else 0), op)
+        if rc:
+            _raise(eng, rc)
+        if outs is not None:
+            return outs
+        return [[eng._scalar_from(b.raw[32 * k:32 * k + 32], sfmt) for k in range(n)] for b in bufs]
+
+    def free(self):
+        if self.handle:
+            self.engine.lib.kzg_fr_program_free(self.engine.ctx, self.handle)
             self.handle = None
 
     close = free

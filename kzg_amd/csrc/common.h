@@ -156,6 +156,7 @@ struct kzg_ctx {
     int opt_lookup_hash_bits = 0;         // ... 1..32 keeps the low v - 1 bits of a key's hash and tag (0 = all); both are kept by the plan
     int opt_lookup_stage = 0;             // kzg_lookup_* / kzg_logup_terms: bytes of one staged piece of host data, a multiple of 32 up to 64 MiB (0 = 64 MiB)
     int opt_lookup_chunk = 0;             // ... vectors per chunk, at most, 1..65535 (0 = the rule alone)
+    int opt_fr_program_block = 0;         // kzg_fr_program_run: threads of a workgroup, 64 / 128 / 256 (0 = the rule: 256 up to 4 temporaries, 128 up to 8, 64 above)
     int opt_point_tree_leaf = 0;          // kzg_point_tree_setup: nodes of up to this many points are multiplied by the schoolbook kernels, a power of two <= 16 (0 = 16)
     int opt_g2_msm_slice = 0;             // kzg_msm_g2_bucket: points one workgroup sorts by digit, a power of two <= 2048 (0 = 2048)
     int opt_g2_msm_slots = 0;             // kzg_msm_g2_bucket: slice slots of the bucket arena = slices per chunk, 1..16 (0 = 16)
@@ -203,7 +204,7 @@ struct kzg_ctx {
     int accum_blocks_single() const { return opt_accum_blocks ? opt_accum_blocks : 256 * KZG_ACCUM_WAVES; }
     int accum_blocks_batch() const { return opt_accum_blocks_batch ? opt_accum_blocks_batch : 240 * KZG_ACCUM_WAVES; }
     int num_cus = 256;
-    std::atomic<bool> attr_msm_set{false}, attr_ntt_set{false}, attr_wide_set{false}, attr_sort20_set{false}, attr_horner_set{false}, attr_group_set{false}, attr_frscan_set{false};  // > 64 KiB dynamic-LDS opt-in done for this device
+    std::atomic<bool> attr_msm_set{false}, attr_ntt_set{false}, attr_wide_set{false}, attr_sort20_set{false}, attr_horner_set{false}, attr_group_set{false}, attr_frscan_set{false}, attr_frprog_set{false};  // > 64 KiB dynamic-LDS opt-in done for this device
     // profiling
     bool prof = false;
     bool prof_only_accum = false;  // events around k_accum_affine only (bench.py's timed region: two events per kernel launch cost 1.4 % there)

@@ -473,6 +473,9 @@ extern "C" int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value) 
     } else if (k == "lookup_chunk") {
         if (value < 0 || value > 65535) return fail(ctx, KZG_ERR_SHAPE, "lookup_chunk must be 0 (the rule alone) or 1..65535 vectors");
         ctx->opt_lookup_chunk = (int)value;
+    } else if (k == "fr_program_block") {
+        if (value != 0 && value != 64 && value != 128 && value != 256) return fail(ctx, KZG_ERR_SHAPE, "fr_program_block must be 0 (the rule) or 64, 128 or 256 threads");
+        ctx->opt_fr_program_block = (int)value;
     } else if (k == "point_tree_leaf") {
         if (value != 0 && (value < 1 || value > 16 || (value & (value - 1)))) return fail(ctx, KZG_ERR_SHAPE, "point_tree_leaf must be 0 (16) or a power of two in 1..16");
         ctx->opt_point_tree_leaf = (int)value;
