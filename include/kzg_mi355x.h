@@ -14,7 +14,8 @@
  *     kzg_commit_eval, kzg_msm_g1, kzg_witness_coeff, kzg_witness_coeff_batched, kzg_witness_eval, kzg_verify_poly_coeff /
  *     _eval, kzg_ntt_fr, kzg_coset_ntt_fr, kzg_poly_mul, kzg_poly_divide, kzg_poly_eval, kzg_poly_multi_eval, kzg_interpolate, kzg_quotient_linear / _eval,
  *     kzg_point_tree_product, kzg_point_tree_eval, kzg_point_tree_combine, kzg_point_tree_interpolate, kzg_fr_vec_mul / _sub, kzg_divide_by_z_on_coset, kzg_fr_scan, kzg_fr_grand_product, kzg_fr_batch_inverse,
- *     kzg_lookup_setup, kzg_lookup_count, kzg_logup_terms, kzg_fr_program_run (KZGProver / KZGProverEvalForm / KZGVerifier are Clone + &self, src/coeff_form.rs:37-124; an
+ *     kzg_lookup_setup, kzg_lookup_count, kzg_logup_terms, kzg_fr_program_run,
+ *     kzg_mle_eq, kzg_mle_bind, kzg_mle_eval, kzg_sumcheck_round (KZGProver / KZGProverEvalForm / KZGVerifier are Clone + &self, src/coeff_form.rs:37-124; an
  *     EvaluationDomain is the caller's own) -- run CONCURRENTLY on one ctx: each call leases one of the context's lanes
  *     (option "streams", default and maximum 16), submits its kernels there and waits for its own result only, so N host
  *     threads calling commit() / create_witness_batched() against one resident SRS fill the GPU like kzg_msm_g1_batch does.
@@ -111,6 +112,19 @@ extern "C" {
  *                                                                             16 B per column and 8 B per output, every HOST column whole
  *                                                                             (32 B x col_len, uploaded once each) and, without KZG_OUT_DEVICE,
  *                                                                             every output whole (32 B x n): KZG_ERR_ALLOC if they do not fit
+ *   kzg_mle_eq                              m <= 28; the workspace holds the point and, without KZG_OUT_DEVICE, the table whole (32 B x 2^m)
+ *   kzg_mle_bind                            n <= 2^28, a power of two; n_cols <= 4,096; the workspace holds 16 B per column, every HOST column whole
+ *                                                                             (32 B x n, uploaded once each, folded in that copy) and, for device
+ *                                                                             columns with host outputs, every output whole (32 B x n / 2)
+ *   kzg_mle_eval                            m <= 28; any batch: tables go in chunks of min(65535, max(1, 2^21 / n)) (option "mle_eval_chunk");
+ *                                                                             the workspace is one chunk's first level (32 B x n / 2 per table, none
+ *                                                                             up to 2^10 scalars), a HOST chunk whole (32 B x n per table) and, without
+ *                                                                             KZG_OUT_DEVICE, the chunk's quotients (32 B x (n - 1) per table): it does
+ *                                                                             not grow with batch
+ *   kzg_sumcheck_round                      n <= 2^28, a power of two; n_eval <= 16, n_out x n_eval <= 32; the workspace holds the program (24 B per
+ *                                                                             instruction), the const table, 8 B per column, one partial sum of 32 B
+ *                                                                             per accumulator and wave of the grid (<= 8 MiB at the default grid) and every HOST column
+ *                                                                             whole (32 B x n, uploaded once each)
  *   kzg_point_tree_setup                    1 <= k <= 2^22 points             (the plan holds 32 x (3 log2 K + 1) bytes per point of the padded
  *                                                                             size K: 9.0 GB at 2^22); kzg_point_tree_eval: n <= 2^28; any batch:
  *                                                                             chunks of max(1, 2^21 / K) blocks, the workspace does not grow with it
@@ -242,6 +256,13 @@ int kzg_sync(kzg_ctx *ctx);
  *  "lookup_chunk" (0 = the rule alone; 1..65535: at most that many vectors per chunk), read per call; the same bytes, for tests,
  * "fr_program_block" (0 = the rule: 256 threads a workgroup up to 4 temporaries, 128 up to 8, 64 above; 64 / 128 / 256: that many, whatever
  *  the plan's temporaries take of the LDS; read per call of kzg_fr_program_run; the same bytes, for tests),
+ * "sumcheck_block" (0 = the rule of "fr_program_block" over temporaries + n_out x n_eval accumulators; 64 / 128 / 256: that many threads a
+ *  workgroup of kzg_sumcheck_round, halved while the slots would pass 128 KiB of LDS), "sumcheck_grid" (0 = default, what the chip holds at
+ *  once; 1..2^22: at most that many workgroups, so that every lane strides over many pairs), "mle_block" (0 = default, 256; 64 / 128 / 256:
+ *  the threads of a workgroup of kzg_mle_eq / _bind / _eval), "mle_local_log" (0 = default, 10; 1..10: kzg_mle_eq builds its first v levels,
+ *  and kzg_mle_eval binds its last v variables, inside one workgroup's LDS; the levels beyond run one launch each) and "mle_eval_chunk"
+ *  (0 = the rule alone; 1..65535: at most that many tables per chunk of kzg_mle_eval); read per call; the same bytes, for tests that reach
+ *  every boundary at m <= 13,
  * "point_tree_leaf" (0 = default, 16; a power of two in 1..16: kzg_point_tree_setup multiplies nodes of up to that many points by its schoolbook
  *  kernels and the levels above through transforms; read at setup and kept by the plan; the same bytes, for tests that reach many levels at tiny k),
  * "g2_msm_slice" (0 = default, 2048; a power of two in 1..2048: the points one workgroup of kzg_msm_g2_bucket sorts by digit) and
@@ -722,6 +743,57 @@ int kzg_fr_program_shape(const kzg_fr_program *plan, size_t *n_insns, size_t *n_
                          size_t *n_mul);
 int kzg_fr_program_run(kzg_ctx *ctx, const kzg_fr_program *plan, const void *const *cols, const size_t *col_len, const void *consts,
                        size_t n, int sfmt, int flags, void *const *outs);
+/* ---- sumcheck rounds on the device: multilinear tables (not reference methods) --------------------------------------------------------
+ * The provers that commit to a table of 2^m values with kzg_commit_coeff over the table itself and open it with HyperKZG / Gemini or
+ * Zeromorph -- HyperPlonk-style gate checks, Spartan, logUp-GKR -- spend their time in m rounds of: evaluate a constraint expression on
+ * every pair of rows at X = 0 .. D and add everything up; draw a challenge; fold every column with it.  The plan of the constraint is a
+ * kzg_fr_program (above); these calls run it on pairs, fold, build the eq table and evaluate.  Everything is Fr-only and bit-exact.
+ *
+ * Conventions
+ *   - a multilinear polynomial in m variables is a table f of n = 2^m scalars; f[i] is its value at the corner whose coordinate x_j is
+ *     bit j of i.
+ *   - rounds bind the TOP variable: with h = n / 2, lo = f[0, h) is x_{m-1} = 0 and hi = f[h, n) is x_{m-1} = 1; binding to rho gives
+ *     lo[i] + rho (hi[i] - lo[i]) in h elements.  That runs in place: lane i reads i and i + h and writes i.
+ *   - a point is m scalars, point[j] for variable j.  Round k of a sumcheck therefore fixes point[m - 1 - k].
+ *   - formats and residues are those of kzg_fr_scan: in KZG_FR_CANONICAL_LE_32 any 256-bit data word counts as its residue, in
+ *     KZG_FR_MONT_LE_32 data is below r; outputs are in sfmt and below r; a product is the product of the represented values in both.
+ *   - single scalars (point, rho, consts) are host memory and below r, else KZG_ERR_SHAPE.
+ *
+ * kzg_mle_eq: out[i] = prod_{j < m} (bit_j(i) ? point[j] : 1 - point[j]), 2^m scalars, 0 <= m <= 28 (m = 0: out[0] = 1).  KZG_OUT_DEVICE
+ *   covers out.  Built by doubling, t[i + 2^j] = t[i] u_j then t[i] -= t[i + 2^j]: one product per output element, not m.  The first 10
+ *   levels run inside one workgroup's LDS (option "mle_local_log"), the rest level by level.
+ * kzg_mle_bind: for every column c < n_cols and i < n / 2, outs[c][i] = cols[c][i] + rho (cols[c][i + n / 2] - cols[c][i]).  n a power of
+ *   two, 2 <= n <= 2^28; 1 <= n_cols <= 4,096; all columns in one launch.  outs[c] == cols[c] EXACTLY is allowed: in place, the upper half
+ *   left byte for byte as it was.  Otherwise outs[c] is a buffer of n / 2 scalars that overlaps no column and no other output: the
+ *   ranges are known, so any overlap is rejected (columns and outputs in different memories -- one of the two flags -- cannot meet; the
+ *   outputs are still compared with each other).  KZG_IN_DEVICE covers the columns, KZG_OUT_DEVICE the outputs; the pointer arrays are
+ *   host memory.  Host columns are uploaded whole.
+ * kzg_mle_eval: ys_out[b] = f_b(point) for `batch` tables, table b at element b 2^m; ys_out is ALWAYS host memory.  Binds from the top
+ *   variable down; the inputs are never written (the first level goes into the lane's workspace).  quotients_out (optional, follows
+ *   KZG_OUT_DEVICE): batch x (n - 1) scalars; for table b the 2^k values of q_k = hi - lo at the level where variable k is bound sit at
+ *   element b (n - 1) + 2^k - 1.  These are the Zeromorph quotients, f(X) - f(u) = sum_k (X_k - u_k) q_k(X_0 .. X_{k-1}); committing to
+ *   them is kzg_commit_coeff.  0 <= m <= 28; KZG_IN_DEVICE covers tables.  batch == 0: KZG_OK, nothing touched.
+ * kzg_fr_program_degree: degrees[o], o < n_out: an upper bound of the total degree of output o in the columns -- a const counts 0, a
+ *   column 1, add / sub the maximum, mul the sum, saturating at 2^32 - 1.  Host only.  A sumcheck needs n_eval = degree + 1.
+ * kzg_sumcheck_round: with h = n / 2 and v_c(i, X) = cols[c][i] + X (cols[c][i + h] - cols[c][i]), for X = 0 .. n_eval - 1 and every
+ *   output o of the plan: sums_out[o n_eval + X] = sum_{i < h} P_o(v_0(i, X), ..., v_{C-1}(i, X); consts).  sums_out is ALWAYS host
+ *   memory, in sfmt, below r.  Every column has n elements, n a power of two, 2 <= n <= 2^28; KZG_IN_DEVICE covers the columns, the
+ *   array cols and consts are host memory.  Each column element comes from HBM once per round; the sum is deterministic (no atomics).
+ * KZG_ERR_SHAPE, before any memory is touched: a NULL ctx; an unknown sfmt; m > 28; n no power of two or outside 2 .. 2^28; n_cols
+ * outside 1 .. 4,096; a point coordinate, rho or const not below r; NULL pointers (arrays, their entries, point with m > 0, rho,
+ * consts with n_consts > 0, out, ys_out, sums_out, degrees, the plan); an output of kzg_mle_bind that overlaps; for the round a plan
+ * with a non-zero shift (a rotation has no meaning on the hypercube), n_eval outside 1 .. 16, n_out x n_eval > 32, a plan of another GPU.
+ * All but kzg_fr_program_degree are blocking calls that lease one lane (they run concurrently with the calls listed at the top).
+ * Options, read per call, the same bytes under every setting: "sumcheck_block", "sumcheck_grid", "mle_block", "mle_local_log",
+ * "mle_eval_chunk" (kzg_ctx_set_option). */
+enum { KZG_SUMCHECK_MAX_EVAL = 16, KZG_SUMCHECK_MAX_ACC = 32 };
+int kzg_mle_eq(kzg_ctx *ctx, const void *point, size_t m, int sfmt, int flags, void *out);
+int kzg_mle_bind(kzg_ctx *ctx, const void *const *cols, size_t n_cols, size_t n, const void *rho, int sfmt, int flags, void *const *outs);
+int kzg_mle_eval(kzg_ctx *ctx, const void *tables, size_t m, size_t batch, const void *point, int sfmt, int flags, void *ys_out,
+                 void *quotients_out);
+int kzg_fr_program_degree(const kzg_fr_program *plan, size_t *degrees);
+int kzg_sumcheck_round(kzg_ctx *ctx, const kzg_fr_program *plan, const void *const *cols, const void *consts, size_t n, size_t n_eval,
+                       int sfmt, int flags, void *sums_out);
 /* Evaluation form: evals holds n_polys vectors of d values (stride d), d a power of two == kzg_srs_len(lagrange).  First phase:
  * ys_out[k] = p_{m(k)}(z_k) (host, count scalars: the values of kzg_eval_form_eval), g_out = the d values of g on the domain, D at out_d
  * in ofmt (each of the three optional, not all NULL).  evals and g / g_out are host memory, or device memory with KZG_IN_DEVICE; g has the

@@ -606,6 +606,12 @@ class FrProgram {
     size_t outputs() const { return shape(3); }
     size_t temps() const { return shape(4); }
     size_t multiplications() const { return shape(5); }
+    // kzg_fr_program_degree: per output an upper bound of its total degree in the columns (a sumcheck needs degree + 1 points)
+    std::vector<size_t> degrees() const {
+        std::vector<size_t> d(outputs());
+        e_->check(kzg_fr_program_degree(h_, d.data()));
+        return d;
+    }
 
   private:
     size_t shape(int which) const {
@@ -635,6 +641,57 @@ inline std::vector<std::vector<Scalar>> fr_program_run(const FrProgram &plan, co
     const Engine &e = plan.engine();
     e.check(kzg_fr_program_run(e.ctx(), plan.handle(), cp.data(), cl.data(), consts.data(), n, KZG_FR_CANONICAL_LE_32, 0, op.data()));
     return outs;
+}
+
+// Sumcheck rounds over multilinear tables on host vectors (kzg_mle_eq / _bind / _eval, kzg_sumcheck_round; the conventions are the C
+// header's: f[i] at the corner whose coordinate x_j is bit j of i, rounds bind the top variable).  Not reference methods.
+inline std::vector<Scalar> mle_eq(const Engine &e, const std::vector<Scalar> &point) {
+    std::vector<Scalar> out((size_t)1 << point.size());
+    e.check(kzg_mle_eq(e.ctx(), point.data(), point.size(), KZG_FR_CANONICAL_LE_32, 0, out.data()));
+    return out;
+}
+
+// every column (n scalars each) folded with rho: lo + rho (hi - lo), n / 2 scalars each
+inline std::vector<std::vector<Scalar>> mle_bind(const Engine &e, const std::vector<std::vector<Scalar>> &cols, const Scalar &rho) {
+    const size_t n = cols.empty() ? 0 : cols[0].size();
+    std::vector<const void *> cp;
+    for (const std::vector<Scalar> &c : cols) {
+        if (c.size() != n) throw ReferencePanic("mle_bind: columns of one length");
+        cp.push_back(c.data());
+    }
+    std::vector<std::vector<Scalar>> outs(cols.size(), std::vector<Scalar>(n / 2));
+    std::vector<void *> op;
+    for (std::vector<Scalar> &o : outs) op.push_back(o.data());
+    e.check(kzg_mle_bind(e.ctx(), cp.data(), cols.size(), n, rho.le.data(), KZG_FR_CANONICAL_LE_32, 0, op.data()));
+    return outs;
+}
+
+// f_b(point) for the tables.size() / 2^m tables of 2^m scalars; quotients (optional): per table the n - 1 Zeromorph quotient values
+inline std::vector<Scalar> mle_eval(const Engine &e, const std::vector<Scalar> &tables, const std::vector<Scalar> &point,
+                                    std::vector<Scalar> *quotients = nullptr) {
+    const size_t n = (size_t)1 << point.size();
+    if (tables.size() % n) throw ReferencePanic("mle_eval: whole tables of 2^m scalars");
+    const size_t batch = tables.size() / n;
+    std::vector<Scalar> ys(batch);
+    if (quotients) quotients->resize(batch * (n - 1));
+    e.check(kzg_mle_eval(e.ctx(), tables.data(), point.size(), batch, point.data(), KZG_FR_CANONICAL_LE_32, 0, ys.data(),
+                         quotients && !quotients->empty() ? quotients->data() : nullptr));
+    return ys;
+}
+
+// sums[o * n_eval + X]: output o of the plan at X over the pairs (i, i + n / 2) of the columns, summed
+inline std::vector<Scalar> sumcheck_round(const FrProgram &plan, const std::vector<std::vector<Scalar>> &cols, const std::vector<Scalar> &consts,
+                                          size_t n_eval) {
+    if (cols.size() != plan.columns() || consts.size() != plan.consts() || cols.empty()) throw ReferencePanic("sumcheck_round: the plan's columns and consts");
+    std::vector<const void *> cp;
+    for (const std::vector<Scalar> &c : cols) {
+        if (c.size() != cols[0].size()) throw ReferencePanic("sumcheck_round: columns of one length");
+        cp.push_back(c.data());
+    }
+    std::vector<Scalar> sums(plan.outputs() * n_eval);
+    const Engine &e = plan.engine();
+    e.check(kzg_sumcheck_round(e.ctx(), plan.handle(), cp.data(), consts.data(), cols[0].size(), n_eval, KZG_FR_CANONICAL_LE_32, 0, sums.data()));
+    return sums;
 }
 
 struct KZGBatchWitness {  // src/coeff_form.rs:12-35

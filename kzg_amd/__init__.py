@@ -13,3 +13,4 @@ from .api import (CosetVerifier, DeviceBuffer, DeviceGroup, Engine, EngineError,
                   PolynomialDegreeTooLarge, ReferencePanic, ShardedSrs, Srs, SrsG2, compute_lagrange_basis, compute_lagrange_basis_g2, compute_omega,
                   pack_scalars, setup, setup_g2, setup_lagrange, setup_lagrange_g2, setup_shard, splitmix_scalar,
                   unpack_scalars)
+from . import sumcheck

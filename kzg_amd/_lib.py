@@ -33,6 +33,7 @@ FRP_ADD, FRP_SUB, FRP_MUL = 0, 1, 2                    # kzg_fr_program: op
 FRP_COL, FRP_CONST, FRP_TEMP, FRP_OUT = 0, 1, 2, 3     # ... operand / destination kinds
 FRP_WORDS = 6
 FRP_MAX_TEMPS = 16
+SUMCHECK_MAX_EVAL, SUMCHECK_MAX_ACC = 16, 32            # kzg_sumcheck_round: points per output, accumulators (n_out x n_eval)
 
 _lib = None
 
@@ -179,6 +180,11 @@ def load(path=None):
         "kzg_fr_program_free": (None, [vp, vp]),
         "kzg_fr_program_shape": (i32, [vp] + [ctypes.POINTER(sz)] * 6),
         "kzg_fr_program_run": (i32, [vp, vp, c_void_pp, ctypes.POINTER(sz), vp, sz, i32, i32, c_void_pp]),
+        "kzg_mle_eq": (i32, [vp, vp, sz, i32, i32, vp]),
+        "kzg_mle_bind": (i32, [vp, c_void_pp, sz, sz, vp, i32, i32, c_void_pp]),
+        "kzg_mle_eval": (i32, [vp, vp, sz, sz, vp, i32, i32, vp, vp]),
+        "kzg_fr_program_degree": (i32, [vp, ctypes.POINTER(sz)]),
+        "kzg_sumcheck_round": (i32, [vp, vp, c_void_pp, vp, sz, sz, i32, i32, vp]),
         "kzg_multiopen_eval_commit": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, i32, i32, vp, vp, vp, i32]),
         "kzg_multiopen_eval_finish": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, vp, vp, i32, i32, vp, vp, i32]),
         "kzg_multiopen_coeff_commit": (i32, [vp, vp, vp, sz, sz, ctypes.POINTER(u32), vp, sz, vp, i32, i32, vp, vp, vp, i32]),

@@ -686,6 +686,80 @@ class Engine:
         words with the three sizes."""
         return FrProgram(self, program, n_cols, n_consts, n_out)
 
+    def _columns_arg(self, cols, what):
+        """(pointer array, elements per column, sfmt, flags, keep-alive) of a set of columns of one length, format and residence"""
+        args = [self._scalars_arg(c) for c in cols]
+        kinds = {(a[1], a[2], a[3]) for a in args}
+        if len(kinds) != 1:
+            raise ReferencePanic("%s: the columns have one length, format and residence" % what)
+        n, sfmt, flags = kinds.pop()
+        cp = (ctypes.c_void_p * len(args))(*[ctypes.cast(a[0], ctypes.c_void_p) for a in args])
+        return cp, n, sfmt, flags, args
+
+    def mle_eq(self, point, sfmt=L.FR_CANONICAL, out=None):
+        """kzg_mle_eq: the table eq(point, .) of 2^m values, point[j] for variable j (bit j of the index).  Returns ints, or `out` (a
+        DeviceBuffer of 2^m scalars, whose format then counts) when one is given."""
+        m = len(point)
+        sfmt = out.sfmt if out is not None else sfmt
+        if out is not None and out.n < (1 << m):
+            raise ReferencePanic("mle_eq: out holds %d scalars, 2^m = %d" % (out.n, 1 << m))
+        pb = b"".join(self._enc_scalar(u, sfmt) for u in point) or None
+        buf = None if out is not None else ctypes.create_string_buffer(32 << m)
+        rc = self.lib.kzg_mle_eq(self.ctx, pb, m, sfmt, L.OUT_DEVICE if out is not None else 0, out.ptr if out is not None else buf)
+        if rc:
+            _raise(self, rc)
+        return out if out is not None else [self._scalar_from(buf.raw[32 * k:32 * k + 32], sfmt) for k in range(1 << m)]
+
+    def mle_bind(self, cols, rho, outs=None):
+        """kzg_mle_bind: every column (n scalars each, n a power of two; all lists of ints or canonical blobs, or all DeviceBuffers of
+        one format) folded at its top variable, lo + rho (hi - lo).  Host columns: returns one list of n / 2 ints per column.
+        DeviceBuffers: folded IN PLACE (the first n / 2 scalars; the rest stay) unless `outs` gives one buffer of n / 2 scalars per
+        column; returns the buffers that hold the results."""
+        cp, n, sfmt, flags, keep = self._columns_arg(cols, "mle_bind")
+        rb = self._enc_scalar(rho, sfmt)
+        if flags & L.IN_DEVICE:
+            dst = list(cols) if outs is None else list(outs)
+            if len(dst) != len(cols) or any(o.sfmt != sfmt or o.n < n // 2 for o in dst):
+                raise ReferencePanic("mle_bind: one output of n / 2 scalars in the columns' format per column")
+            op = (ctypes.c_void_p * len(dst))(*[o.ptr.value for o in dst])
+            rc = self.lib.kzg_mle_bind(self.ctx, cp, len(cols), n, rb, sfmt, flags | L.OUT_DEVICE, op)
+            if rc:
+                _raise(self, rc)
+            return dst
+        if outs is not None:
+            raise ReferencePanic("mle_bind: outs go with device columns")
+        bufs = [ctypes.create_string_buffer(16 * max(n, 2)) for _ in cols]
+        op = (ctypes.c_void_p * max(len(bufs), 1))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
+        rc = self.lib.kzg_mle_bind(self.ctx, cp, len(cols), n, rb, sfmt, flags, op)
+        if rc:
+            _raise(self, rc)
+        return [[self._scalar_from(b.raw[32 * k:32 * k + 32], sfmt) for k in range(n // 2)] for b in bufs]
+
+    def mle_eval(self, tables, point, batch=1, quotients=False):
+        """kzg_mle_eval: f_b(point) for `batch` tables of 2^m scalars each (m = len(point)), contiguous: a list of ints, a canonical
+        blob or a DeviceBuffer.  Returns the values, or (values, quotients) with quotients=True: per table the n - 1 Zeromorph
+        quotient values, q_k at [2^k - 1, 2^(k + 1) - 1)."""
+        m = len(point)
+        n = 1 << m
+        ptr, have, sfmt, flags, _keep = self._scalars_arg(tables)
+        if have < batch * n:
+            raise ReferencePanic("mle_eval: %d scalars are fewer than batch x 2^m = %d" % (have, batch * n))
+        pb = b"".join(self._enc_scalar(u, sfmt) for u in point) or None
+        ys = ctypes.create_string_buffer(32 * max(batch, 1))
+        qb = ctypes.create_string_buffer(32 * max(batch * (n - 1), 1)) if quotients else None
+        rc = self.lib.kzg_mle_eval(self.ctx, ptr, m, batch, pb, sfmt, flags, ys, qb)
+        if rc:
+            _raise(self, rc)
+        vals = [self._scalar_from(ys.raw[32 * b:32 * b + 32], sfmt) for b in range(batch)]
+        if not quotients:
+            return vals
+        return vals, [[self._scalar_from(qb.raw[32 * k:32 * k + 32], sfmt) for k in range(b * (n - 1), (b + 1) * (n - 1))] for b in range(batch)]
+
+    def sumcheck_round(self, plan, cols, consts=(), n_eval=None):
+        """kzg_sumcheck_round: for every output o of `plan` (a FrProgram without rotations) the sums over the pairs (i, i + n / 2) of
+        the output at X = 0 .. n_eval - 1 (default: the largest degree + 1).  Returns one list of n_eval ints per output."""
+        return plan.sumcheck_round(cols, consts, n_eval)
+
     def _multiopen_vectors_arg(self, vecs, length, pad):
         """(pointer, length, n_polys, sfmt, flags, keep-alive) of the polynomials of a multiopen call: a list of vectors (lists of ints,
         EvaluationDomains or Polynomials; with `pad` filled with zeros to the longest) or a flat blob / DeviceBuffer (length given)"""
@@ -1155,6 +1229,33 @@ class FrProgram:
         if outs is not None:
             return outs
         return [[eng._scalar_from(b.raw[32 * k:32 * k + 32], sfmt) for k in range(n)] for b in bufs]
+
+    def degrees(self):
+        """kzg_fr_program_degree: per output an upper bound of its total degree in the columns (a sumcheck needs degree + 1 points)"""
+        n_out = self.shape()[3]
+        d = (ctypes.c_size_t * n_out)()
+        rc = self.engine.lib.kzg_fr_program_degree(self.handle, d)
+        if rc:
+            _raise(self.engine, rc)
+        return [int(x) for x in d]
+
+    def sumcheck_round(self, cols, consts=(), n_eval=None):
+        """Engine.sumcheck_round"""
+        eng = self.engine
+        _, n_cols, n_consts, n_out, _, _ = self.shape()
+        if len(cols) != n_cols or len(consts) != n_consts:
+            raise ReferencePanic("sumcheck_round: the plan takes %d columns and %d consts" % (n_cols, n_consts))
+        n_eval = max(self.degrees()) + 1 if n_eval is None else n_eval
+        if n_cols:
+            cp, n, sfmt, flags, _keep = eng._columns_arg(cols, "sumcheck_round")
+        else:
+            raise ReferencePanic("sumcheck_round: a plan without columns has no rows")
+        kb = b"".join(eng._enc_scalar(k, sfmt) for k in consts) or None
+        sums = ctypes.create_string_buffer(32 * max(n_out * n_eval, 1))
+        rc = eng.lib.kzg_sumcheck_round(eng.ctx, self.handle, cp, kb, n, n_eval, sfmt, flags, sums)
+        if rc:
+            _raise(eng, rc)
+        return [[eng._scalar_from(sums.raw[32 * k:32 * k + 32], sfmt) for k in range(o * n_eval, (o + 1) * n_eval)] for o in range(n_out)]
 
     def free(self):
         if self.handle:

@@ -19,7 +19,7 @@ HOOK_SOURCES = ["capi.hip", "mgpu.hip", "g1ntt.hip", "verify_cosets.hip", "verif
 # translation units of the hooks library only (no product counterpart): kzg_test_arith, the device twin of tests/host_math.cpp, and
 # kzg_test_tower, the device twin of tests/host_tower.cpp (NOT in VIA_ASM: built the way pairing.hip is)
 HOOK_ONLY_SOURCES = ["arith_hooks.hip", "tower_hooks.hip"]
-SOURCES = ["capi.hip", "runtime.hip", "msm.hip", "srs.hip", "ntt.hip", "poly.hip", "witness.hip", "pairing.hip", "msm_wide.hip", "msm_tail.hip", "mgpu.hip", "g1ntt.hip", "recover.hip", "verify_cosets.hip", "verify_cosets_batch.hip", "verify_eval_batch.hip", "open_eval.hip", "fold.hip", "multiopen.hip", "multi_eval.hip", "poly_divide.hip", "point_tree.hip", "g2_msm.hip", "witness_tree.hip", "fr_scan.hip", "g2ntt.hip", "lookup.hip", "fr_program.hip"]
+SOURCES = ["capi.hip", "runtime.hip", "msm.hip", "srs.hip", "ntt.hip", "poly.hip", "witness.hip", "pairing.hip", "msm_wide.hip", "msm_tail.hip", "mgpu.hip", "g1ntt.hip", "recover.hip", "verify_cosets.hip", "verify_cosets_batch.hip", "verify_eval_batch.hip", "open_eval.hip", "fold.hip", "multiopen.hip", "multi_eval.hip", "poly_divide.hip", "point_tree.hip", "g2_msm.hip", "witness_tree.hip", "fr_scan.hip", "g2ntt.hip", "lookup.hip", "fr_program.hip", "mle.hip"]
 # per-file extra flags (none at present; out-of-line multiplies for the tail kernels were measured: no gain)
 EXTRA_FLAGS = {}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]

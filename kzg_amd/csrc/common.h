@@ -157,6 +157,11 @@ struct kzg_ctx {
     int opt_lookup_stage = 0;             // kzg_lookup_* / kzg_logup_terms: bytes of one staged piece of host data, a multiple of 32 up to 64 MiB (0 = 64 MiB)
     int opt_lookup_chunk = 0;             // ... vectors per chunk, at most, 1..65535 (0 = the rule alone)
     int opt_fr_program_block = 0;         // kzg_fr_program_run: threads of a workgroup, 64 / 128 / 256 (0 = the rule: 256 up to 4 temporaries, 128 up to 8, 64 above)
+    int opt_sumcheck_block = 0;           // kzg_sumcheck_round: threads of a workgroup, 64 / 128 / 256 (0 = the rule by temporaries + accumulators, as above)
+    int opt_sumcheck_grid = 0;            // ... workgroups of the strided grid, at most (0 = what the LDS lets the chip hold at once)
+    int opt_mle_block = 0;                // kzg_mle_eq / _bind / _eval: threads of a workgroup of the level kernels, 64 / 128 / 256 (0 = 256)
+    int opt_mle_local_log = 0;            // kzg_mle_eq / _eval: 1..10 levels (tables of up to 2^v scalars) inside one workgroup's LDS (0 = 10)
+    int opt_mle_eval_chunk = 0;           // kzg_mle_eval: tables per chunk, at most, 1..65535 (0 = the rule min(65535, max(1, 2^21 / n)) alone)
     int opt_point_tree_leaf = 0;          // kzg_point_tree_setup: nodes of up to this many points are multiplied by the schoolbook kernels, a power of two <= 16 (0 = 16)
     int opt_g2_msm_slice = 0;             // kzg_msm_g2_bucket: points one workgroup sorts by digit, a power of two <= 2048 (0 = 2048)
     int opt_g2_msm_slots = 0;             // kzg_msm_g2_bucket: slice slots of the bucket arena = slices per chunk, 1..16 (0 = 16)
@@ -204,7 +209,7 @@ struct kzg_ctx {
     int accum_blocks_single() const { return opt_accum_blocks ? opt_accum_blocks : 256 * KZG_ACCUM_WAVES; }
     int accum_blocks_batch() const { return opt_accum_blocks_batch ? opt_accum_blocks_batch : 240 * KZG_ACCUM_WAVES; }
     int num_cus = 256;
-    std::atomic<bool> attr_msm_set{false}, attr_ntt_set{false}, attr_wide_set{false}, attr_sort20_set{false}, attr_horner_set{false}, attr_group_set{false}, attr_frscan_set{false}, attr_frprog_set{false};  // > 64 KiB dynamic-LDS opt-in done for this device
+    std::atomic<bool> attr_msm_set{false}, attr_ntt_set{false}, attr_wide_set{false}, attr_sort20_set{false}, attr_horner_set{false}, attr_group_set{false}, attr_frscan_set{false}, attr_frprog_set{false}, attr_sumcheck_set{false};  // > 64 KiB dynamic-LDS opt-in done for this device
     // profiling
     bool prof = false;
     bool prof_only_accum = false;  // events around k_accum_affine only (bench.py's timed region: two events per kernel launch cost 1.4 % there)

@@ -22,55 +22,13 @@
 #include <new>
 
 #include "common.h"
+#include "fr_program.h"
 
 namespace kzg {
 
 constexpr size_t FRP_MAX_N = (size_t)1 << 28;
 constexpr size_t FRP_MAX_INSNS = 65536, FRP_MAX_COLS = 4096, FRP_MAX_CONSTS = 4096, FRP_MAX_OUT = 64;
 constexpr int FRP_LDS_MAX = KZG_FRP_MAX_TEMPS * 32 * 256;   // sixteen temporaries at 256 threads: 128 KiB of the CU's 160
-
-struct FrpCol {
-    const Fr *p;
-    uint32_t len;
-    uint32_t mask;   // len - 1 of a periodic column (a power of two); 0xFFFFFFFF: a full-length column, len == n
-};
-
-typedef uint32_t frp_v4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) frp_v4 frp_g4;   // column and output words are global memory: no flat access, whose loads would wait for LDS too
-
-__device__ __forceinline__ Fr frp_load(const Fr *p) {
-    const frp_g4 *g = (const frp_g4 *)p;
-    const frp_v4 lo = g[0], hi = g[1];
-    Fr v;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        v.v[k] = lo[k];
-        v.v[4 + k] = hi[k];
-    }
-    return v;
-}
-
-__device__ __forceinline__ void frp_store(Fr *p, const Fr &v) {
-    frp_g4 *g = (frp_g4 *)p;
-    g[0] = frp_v4{v.v[0], v.v[1], v.v[2], v.v[3]};
-    g[1] = frp_v4{v.v[4], v.v[5], v.v[6], v.v[7]};
-}
-
-__device__ __forceinline__ void frp_put(uint2 *lds, uint32_t T, uint32_t t, const Fr &v) {
-#pragma unroll
-    for (int k = 0; k < 4; k++) lds[(t * 4 + k) * T + threadIdx.x] = make_uint2(v.v[2 * k], v.v[2 * k + 1]);
-}
-
-__device__ __forceinline__ Fr frp_get(const uint2 *lds, uint32_t T, uint32_t t) {
-    Fr v;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint2 w = lds[(t * 4 + k) * T + threadIdx.x];
-        v.v[2 * k] = w.x;
-        v.v[2 * k + 1] = w.y;
-    }
-    return v;
-}
 
 template <bool CANON>
 __device__ __forceinline__ Fr frp_fetch(const FrpCol *__restrict__ cols, const Fr *__restrict__ consts, uint32_t kind, uint32_t idx, uint32_t shift,
@@ -133,12 +91,6 @@ static int frp_block(const kzg_ctx *ctx, size_t n_temps) {
 }
 
 }  // namespace kzg
-
-struct kzg_fr_program {
-    int device = 0;
-    size_t n_cols = 0, n_consts = 0, n_out = 0, n_temps = 0, n_mul = 0;
-    std::vector<uint32_t> words;   // validated, as given
-};
 
 using namespace kzg;
 

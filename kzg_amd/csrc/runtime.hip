@@ -476,6 +476,21 @@ extern "C" int kzg_ctx_set_option(kzg_ctx *ctx, const char *key, int64_t value) 
     } else if (k == "fr_program_block") {
         if (value != 0 && value != 64 && value != 128 && value != 256) return fail(ctx, KZG_ERR_SHAPE, "fr_program_block must be 0 (the rule) or 64, 128 or 256 threads");
         ctx->opt_fr_program_block = (int)value;
+    } else if (k == "sumcheck_block") {
+        if (value != 0 && value != 64 && value != 128 && value != 256) return fail(ctx, KZG_ERR_SHAPE, "sumcheck_block must be 0 (the rule) or 64, 128 or 256 threads");
+        ctx->opt_sumcheck_block = (int)value;
+    } else if (k == "sumcheck_grid") {
+        if (value < 0 || value > (1 << 22)) return fail(ctx, KZG_ERR_SHAPE, "sumcheck_grid must be 0 (default) or 1..2^22 workgroups");
+        ctx->opt_sumcheck_grid = (int)value;
+    } else if (k == "mle_block") {
+        if (value != 0 && value != 64 && value != 128 && value != 256) return fail(ctx, KZG_ERR_SHAPE, "mle_block must be 0 (256) or 64, 128 or 256 threads");
+        ctx->opt_mle_block = (int)value;
+    } else if (k == "mle_local_log") {
+        if (value < 0 || value > 10) return fail(ctx, KZG_ERR_SHAPE, "mle_local_log must be 0 (10) or 1..10 levels");
+        ctx->opt_mle_local_log = (int)value;
+    } else if (k == "mle_eval_chunk") {
+        if (value < 0 || value > 65535) return fail(ctx, KZG_ERR_SHAPE, "mle_eval_chunk must be 0 (the rule alone) or 1..65535 tables");
+        ctx->opt_mle_eval_chunk = (int)value;
     } else if (k == "point_tree_leaf") {
         if (value != 0 && (value < 1 || value > 16 || (value & (value - 1)))) return fail(ctx, KZG_ERR_SHAPE, "point_tree_leaf must be 0 (16) or a power of two in 1..16");
         ctx->opt_point_tree_leaf = (int)value;
